@@ -35,6 +35,10 @@ Prints ONE JSON line on rank 0:
                         and at the bench batch, and the `_dev` path on buffers / a stream owned through the C ABI
   per_rank              (N > 1) every rank's own ops/s and the max/min skew
   cpu_baseline          (N = 1) the plain-C port of the reference algorithm on this box's host cores
+
+`--dump-outputs DIR` also writes a seeded sample of the last timed step's product ciphertexts to DIR/*.npy (float64,
+exact; see dump_outputs), so that two builds' runs with the same arguments can be compared output for output
+(bench_outputs/<name> inside the tree is ignored by git).
 """
 import argparse
 import json
@@ -461,6 +465,39 @@ def emit(result):
     sys.stdout.write("DETAIL " + json.dumps(result) + "\n")
     sys.stdout.write(compact_record(result) + "\n")
     sys.stdout.flush()
+
+
+DUMP_BYTES = 48 << 20       # --dump-outputs budget (the files stay below 64 MB)
+
+
+def dump_outputs(path, torch, out, ct0, total, dist, rank):
+    """--dump-outputs: what the timed path handed its caller in its last step -- product ciphertexts [2][L][N] of u64
+    residues -- as float64 .npy files that two builds' runs can be compared by.  A fixed, seeded sample of the global
+    batch (the same ciphertexts for the same arguments); every residue is split into its low and high 32-bit halves,
+    which float64 holds exactly.  Every rank contributes its part of the sample; rank 0 writes:
+      product_index.npy  [S]            global ciphertext index of each sampled product
+      product_lo32.npy   [S][2][L][N]   residue & 0xffffffff
+      product_hi32.npy   [S][2][L][N]   residue >> 32"""
+    import numpy as np
+    k = min(total, max(1, DUMP_BYTES // (out[0].numel() * 2 * 8)))
+    pick = np.sort(np.random.default_rng(SEED).choice(total, size=k, replace=False))
+    mine = [int(i) for i in pick if ct0 <= i < ct0 + out.shape[0]]
+    part = (mine, out[torch.tensor([i - ct0 for i in mine], dtype=torch.long, device=out.device)].cpu())
+    parts = [part]
+    if dist is not None:
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, part)
+    if rank != 0:
+        return None
+    index = np.array([i for ids, _ in parts for i in ids], dtype=np.float64)
+    v = torch.cat([x for _, x in parts]).numpy().view(np.uint64)
+    os.makedirs(path, exist_ok=True)
+    files = {"product_index": index, "product_lo32": (v & np.uint64(0xFFFFFFFF)).astype(np.float64),
+             "product_hi32": (v >> np.uint64(32)).astype(np.float64)}
+    for name, a in files.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return dict(dir=os.path.abspath(path), ciphertexts=len(index), files=sorted(n + ".npy" for n in files),
+                bytes=int(sum(a.nbytes for a in files.values())))
 
 
 def short_symbol(sym):
@@ -1041,7 +1078,9 @@ def c5_chain(fhe, torch, batch=16):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5,
+                    help="timed steps of one repeat of the timed region (it runs 3 repeats; `ms_per_step` is the median "
+                         "repeat's time over this number)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=0,
                     help="ciphertext pairs per GPU per step (default: 1024 = C2 with one GPU, 8192 = C4's shard with more)")
@@ -1055,7 +1094,12 @@ def main():
                     help="seconds of a sustained event-free leg after the timed region (0: none)")
     ap.add_argument("--spawn-check", action="store_true",
                     help="rendezvous only: start the ranks, all-reduce their ranks, print a JSON line (no GPU work)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write a seeded sample of the last timed step's product ciphertexts to "
+                         "DIR/*.npy (float64, see dump_outputs); inside the tree, bench_outputs/<name> is kept out of git")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -1202,6 +1246,8 @@ def main():
     REPEATS = 3
     elapsed_all = [timed(step, args.steps) for _ in range(REPEATS)]
     fhe.prof_enable(False)
+    # `out` holds the last timed step's products until the legs below run the step again
+    dumped = dump_outputs(args.dump_outputs, torch, out, ct0, world * batch, dist, rank) if args.dump_outputs else None
     prof_entries = fhe.prof_entries()                 # (label, kernel symbol, launches, ms) per instantiation
     # the library labels the two tensor_intt instances separately (rows below 2^60: narrow passes); the roofline's
     # families fold them, `dominant_by_symbol` below keeps every instantiation apart
@@ -1388,6 +1434,8 @@ def main():
         "roofline": roofline,
     }
     result.update(extras)
+    if dumped is not None:
+        result["dump_outputs"] = dumped
     if sustained is not None:
         result["sustained"] = sustained
     if per_rank is not None:

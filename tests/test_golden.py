@@ -1,7 +1,7 @@
 """The committed golden vectors of tests/golden/ (made by tests/golden/make_golden.py) against
 every implementation in the tree: the Python oracle, the plain-C oracle, the kernel sources
 under host emulation, and -- `gpu`-marked -- the HIP build on the MI355X.  None of these reads
-/root/reference."""
+the reference checkout."""
 import hashlib
 import json
 import os

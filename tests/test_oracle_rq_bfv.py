@@ -25,13 +25,10 @@ def rand_poly(ctx, rng, rep=POWER_BASIS):
 
 
 def test_rq_moduli_constant_matches_reference():
-    """rq/mod.rs:687-693."""
-    import re, os
-    src = "/root/reference/crates/fhe-math/src/rq/mod.rs"
-    if os.path.exists(src):
-        text = open(src).read()
-        m = re.search(r"const MODULI: &\[u64; 5\] = &\[(.*?)\];", text, re.S)
-        assert [int(x) for x in re.findall(r"\d+", m.group(1))] == MODULI
+    """rq/mod.rs:687-693, as recorded in tests/golden/reference_index.json (tests/golden/make_reference_index.py)."""
+    import json, os
+    gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_index.json")
+    assert json.load(open(gold))["rq_moduli"] == MODULI
 
 
 @pytest.mark.parametrize("n,d", [(n, d) for n in (1, 2, 3, 100, 1000, 4611686018326724610)
