@@ -4,6 +4,7 @@
 // nothing throws across the boundary.
 #include "../../include/fhe_hip.h"
 
+#include <array>
 #include <cstdio>
 #include <map>
 
@@ -97,7 +98,43 @@ void set_device(const Ctx &c) {
     if (c.device >= 0) FHE_HIP_CHECK(hipSetDevice(c.device));
 }
 
-// Host-pointer convenience: copy in, run `body(device_ptrs...)` on the null stream, copy out.
+// Paired entry points.  Every operation exported as a host-pointer form fhe_X and a device-pointer form fhe_X_dev is
+// one struct derived from Paired:
+//  - its constructor makes every argument check, in one order: handles, then device / level / context, then buffers.
+//    Checks the engine repeats stay here when staging depends on them: the device check (a host-only handle is refused
+//    before the host form takes workspace for it), checks whose values size a staged array or decide whether the
+//    buffers are needed (NoMoreContext, InvalidLevel, ContextNotReachable, EmptyDotProduct, MulPolyCount), and the
+//    buffer checks themselves.  The rest (key levels, moduli agreement, expansion size) is left to the engine;
+//  - `io` lists the arrays it reads and writes with their sizes;
+//  - run(d, batch, stream) is the device body on the arrays of `io`, in that order.
+// run_dev() calls the body on the caller's pointers and stream, run_host() stages `io` through the workspace.
+struct Io {
+    enum { IN = 1, OUT = 2, INOUT = IN | OUT, ZEROED = 4, SECRET = 8 };
+    const void *p;   // the caller's array; NULL (no array, or an empty batch) is passed through and never staged
+    size_t items;    // the batch, or 1 for an array the batch shares
+    size_t bytes;    // per item
+    int kind;        // ZEROED: an output cleared before the body; SECRET: cleared before its staging block is released
+    // arrays of u64 words
+    static Io in(const void *p, size_t items, size_t words, int flags = 0) { return {p, items, words * sizeof(u64), IN | flags}; }
+    static Io out(void *p, size_t items, size_t words, int flags = 0) { return {p, items, words * sizeof(u64), OUT | flags}; }
+    static Io inout(void *p, size_t items, size_t words) { return {p, items, words * sizeof(u64), INOUT}; }
+};
+// (an input with the same host array and size as an earlier one is staged once: fhe_bfv_mul's lhs == rhs squaring)
+static bool shares(const Io &a, const Io &b) {
+    return a.kind == Io::IN && b.kind == Io::IN && a.p == b.p && a.items == b.items && a.bytes == b.bytes;
+}
+struct Paired {
+    static constexpr bool sliced = false;   // true: a large host-form batch goes through host_sliced
+    const Ctx *dev = nullptr;               // the context whose device runs the body
+    size_t batch = 0;
+    void on(const Ctx &c, size_t b) {       // the device check
+        c.need_device();
+        dev = &c;
+        batch = b;
+    }
+};
+template <size_t K> using Ptrs = std::array<u64 *, K>;
+
 // Staging blocks come from the engine's workspace pool (null stream), not from hipMalloc / hipFree per call: a host
 // call is synchronous, so a block released here is idle by the time the next call takes it.
 struct HostIO {
@@ -108,40 +145,31 @@ struct HostIO {
         if (!secrets.empty()) (void)hipStreamSynchronize(nullptr);
         for (void *p : bufs) Workspace::get().release(p);
     }
-    u64 *secret(u64 *d, size_t count) {
-        secrets.emplace_back(d, std::max<size_t>(count, 1) * sizeof(u64));
-        return d;
-    }
-    u64 *in(const u64 *h, size_t count) {
-        u64 *d = out(count);
-        if (count) FHE_HIP_CHECK(hipMemcpy(d, h, count * sizeof(u64), hipMemcpyHostToDevice));
-        return d;
-    }
-    u64 *out(size_t count) {
-        void *d = Workspace::get().acquire(std::max<size_t>(count, 1) * sizeof(u64), nullptr);
+    u64 *take(size_t bytes) {   // at least one word
+        void *d = Workspace::get().acquire(std::max<size_t>((bytes + 7) / 8, 1) * sizeof(u64), nullptr);
         bufs.push_back(d);
         return (u64 *)d;
     }
-    void back(u64 *h, const u64 *d, size_t count) {
-        FHE_HIP_CHECK(hipStreamSynchronize(nullptr));
-        if (count) FHE_HIP_CHECK(hipMemcpy(h, d, count * sizeof(u64), hipMemcpyDeviceToHost));
+    u64 *stage(const Io &a) {
+        const size_t bytes = a.items * a.bytes;
+        u64 *d = take(bytes);
+        if (a.kind & Io::SECRET) secrets.emplace_back(d, std::max<size_t>((bytes + 7) / 8, 1) * sizeof(u64));
+        if ((a.kind & Io::IN) && bytes) FHE_HIP_CHECK(hipMemcpy(d, a.p, bytes, hipMemcpyHostToDevice));
+        if (a.kind & Io::ZEROED)
+            FHE_HIP_CHECK(hipMemsetAsync(d, 0, std::max<size_t>((bytes + 7) / 8, 1) * sizeof(u64), nullptr));
+        return d;
     }
 };
 
-
 // Host-pointer calls on a large batch of independent items: the batch goes through in slices whose upload, kernels and
 // download overlap (three internal streams: the link is full duplex and the GPU works on slice i while slice i + 1
-// arrives and slice i - 1 leaves).  Values are those of the one-shot path.  `ins`: host arrays with their words per
-// item (equal pointers share one device copy: squaring); body(device inputs of the slice, device output of the slice,
-// items, stream).  Returns false -- nothing done -- when the batch is smaller than three slices of >= 32 MiB.
-struct HostIn {
-    const u64 *h;
-    size_t words;
-};
-template <class Body>
-static bool host_sliced(int dev, size_t batch, const std::vector<HostIn> &ins, u64 *out, size_t out_words, Body body) {
-    size_t widest = out_words;
-    for (const HostIn &in : ins) widest = std::max(widest, in.words);
+// arrives and slice i - 1 leaves).  Values are those of the one-shot path.  Every array of `io` holds `batch` items;
+// body(device arrays of the slice, items, stream).  Returns false -- nothing done -- when the batch is smaller than three
+// slices of >= 32 MiB.
+template <size_t K, class Body>
+static bool host_sliced(int dev, size_t batch, const std::array<Io, K> &io, Body body) {
+    size_t widest = 0;
+    for (const Io &a : io) widest = std::max(widest, a.bytes / sizeof(u64));
     if (!widest) return false;
 #if defined(FHE_HOST_EMULATION)
     const size_t slice = 2;   // (so that the emulated suite walks the sliced path: batches of 6 and more)
@@ -157,14 +185,15 @@ static bool host_sliced(int dev, size_t batch, const std::vector<HostIn> &ins, u
     // used them has returned -- but an asynchronous `_dev` call on the null stream may still be running in them, and
     // the three internal streams are non-blocking: they do not order against the null stream by themselves.
     FHE_HIP_CHECK(hipStreamSynchronize(nullptr));
-    HostIO io;
-    std::vector<u64 *> din(ins.size(), nullptr);
-    for (size_t k = 0; k < ins.size(); k++) {
+    HostIO h;
+    Ptrs<K> din{};
+    std::array<bool, K> upload{};
+    for (size_t k = 0; k < K; k++) {
         for (size_t j = 0; j < k; j++)
-            if (ins[j].h == ins[k].h && ins[j].words == ins[k].words) din[k] = din[j];
-        if (!din[k]) din[k] = io.out(batch * ins[k].words);
+            if (shares(io[j], io[k])) din[k] = din[j];
+        upload[k] = (io[k].kind & Io::IN) && !din[k];
+        if (!din[k]) din[k] = h.take(batch * io[k].bytes);
     }
-    u64 *dout = io.out(batch * out_words);
     const size_t nsl = (batch + slice - 1) / slice;
     std::vector<hipEvent_t> up(nsl, nullptr), done(nsl, nullptr);
     auto finish = [&] {   // nothing may still use the buffers when HostIO gives them back
@@ -179,30 +208,29 @@ static bool host_sliced(int dev, size_t batch, const std::vector<HostIn> &ins, u
         for (size_t i = 0; i < nsl + 2; i++) {
             if (i < nsl) {
                 const size_t o = i * slice, n = std::min(slice, batch - o);
-                for (size_t k = 0; k < ins.size(); k++) {
-                    bool first = true;
-                    for (size_t j = 0; j < k; j++) first = first && din[j] != din[k];
-                    if (first)
-                        FHE_HIP_CHECK(hipMemcpyAsync(din[k] + o * ins[k].words, ins[k].h + o * ins[k].words,
-                                                     n * ins[k].words * sizeof(u64), hipMemcpyHostToDevice, s_up));
-                }
+                for (size_t k = 0; k < K; k++)
+                    if (upload[k])
+                        FHE_HIP_CHECK(hipMemcpyAsync((char *)din[k] + o * io[k].bytes, (const char *)io[k].p + o * io[k].bytes,
+                                                     n * io[k].bytes, hipMemcpyHostToDevice, s_up));
                 up[i] = ax.take_event();
                 FHE_HIP_CHECK(hipEventRecord(up[i], s_up));
             }
             if (i >= 1 && i - 1 < nsl) {
                 const size_t c = i - 1, o = c * slice, n = std::min(slice, batch - o);
                 FHE_HIP_CHECK(hipStreamWaitEvent(s_comp, up[c], 0));
-                std::vector<const u64 *> ds(ins.size());
-                for (size_t k = 0; k < ins.size(); k++) ds[k] = din[k] + o * ins[k].words;
-                body(ds, dout + o * out_words, n, s_comp);
+                Ptrs<K> ds;
+                for (size_t k = 0; k < K; k++) ds[k] = din[k] + o * (io[k].bytes / sizeof(u64));
+                body(ds, n, s_comp);
                 done[c] = ax.take_event();
                 FHE_HIP_CHECK(hipEventRecord(done[c], s_comp));
             }
             if (i >= 2) {
                 const size_t c = i - 2, o = c * slice, n = std::min(slice, batch - o);
                 FHE_HIP_CHECK(hipStreamWaitEvent(s_down, done[c], 0));
-                FHE_HIP_CHECK(hipMemcpyAsync(out + o * out_words, dout + o * out_words, n * out_words * sizeof(u64),
-                                             hipMemcpyDeviceToHost, s_down));
+                for (size_t k = 0; k < K; k++)
+                    if (io[k].kind & Io::OUT)
+                        FHE_HIP_CHECK(hipMemcpyAsync((char *)io[k].p + o * io[k].bytes, (char *)din[k] + o * io[k].bytes,
+                                                     n * io[k].bytes, hipMemcpyDeviceToHost, s_down));
             }
         }
     } catch (...) {
@@ -211,6 +239,46 @@ static bool host_sliced(int dev, size_t batch, const std::vector<HostIn> &ins, u
     }
     finish();
     return true;
+}
+
+template <class Op>
+void run_dev(const Op &op, void *stream) {
+    set_device(*op.dev);
+    Ptrs<std::tuple_size<decltype(op.io)>::value> d;
+    for (size_t k = 0; k < d.size(); k++) d[k] = (u64 *)op.io[k].p;
+    op.run(d, op.batch, as_stream(stream));
+}
+// The host form: copy in, run the body on the null stream, copy out.
+template <class Op>
+void run_host(const Op &op) {
+    set_device(*op.dev);
+    constexpr size_t K = std::tuple_size<decltype(op.io)>::value;
+    const std::array<Io, K> &io = op.io;
+    if (Op::sliced && host_sliced(op.dev->device, op.batch, io,
+                                  [&](const Ptrs<K> &d, size_t n, hipStream_t s) { op.run(d, n, s); }))
+        return;
+    HostIO h;
+    Ptrs<K> d{};
+    for (size_t k = 0; k < K; k++) {
+        if (!io[k].p) continue;
+        for (size_t j = 0; j < k; j++)
+            if (shares(io[j], io[k])) d[k] = d[j];
+        if (!d[k]) d[k] = h.stage(io[k]);
+    }
+    op.run(d, op.batch, nullptr);
+    FHE_HIP_CHECK(hipStreamSynchronize(nullptr));
+    for (size_t k = 0; k < K; k++) {
+        const size_t bytes = io[k].items * io[k].bytes;
+        if ((io[k].kind & Io::OUT) && io[k].p && bytes) FHE_HIP_CHECK(hipMemcpy((void *)io[k].p, d[k], bytes, hipMemcpyDeviceToHost));
+    }
+}
+template <class Op, class... A>
+fhe_status dev_call(void *stream, A... a) {
+    return guard([&] { run_dev(Op(a...), stream); });
+}
+template <class Op, class... A>
+fhe_status host_call(A... a) {
+    return guard([&] { run_host(Op(a...)); });
 }
 
 std::unique_ptr<Ksk> make_ksk(const Ctx &ct, const Ctx &kc, size_t ndigits, size_t log_base) {
@@ -465,117 +533,78 @@ fhe_status fhe_ctx_get_table(const fhe_ctx *ctx, int which, uint64_t *out) {
     });
 }
 
-#define FHE_POLY_IO_PROLOGUE(ctxh)      \
-    need(ctxh, "ctx");                  \
-    const Ctx &c = *(ctxh)->c;          \
-    c.need_device();                    \
-    set_device(c);                      \
-    const size_t pe = c.L * c.n
-
-fhe_status fhe_ntt_forward_dev(const fhe_ctx *ctx, uint64_t *polys, size_t batch, void *stream) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        (void)pe;
+struct Ntt : Paired {   // NttOperator::{forward,backward}, in place
+    bool inverse;
+    std::array<Io, 1> io;
+    Ntt(const fhe_ctx *ctx, uint64_t *polys, size_t batch, bool inverse) : inverse(inverse) {
+        need(ctx, "ctx");
+        on(*ctx->c, batch);
         if (batch) need(polys, "polys");
-        ntt_polys(c, false, polys, polys, batch, as_stream(stream));
-    });
+        io = {Io::inout(polys, batch, dev->L * dev->n)};
+    }
+    void run(const Ptrs<1> &d, size_t n, hipStream_t s) const { ntt_polys(*dev, inverse, d[0], d[0], n, s); }
+};
+fhe_status fhe_ntt_forward(const fhe_ctx *ctx, uint64_t *polys, size_t batch) { return host_call<Ntt>(ctx, polys, batch, false); }
+fhe_status fhe_ntt_backward(const fhe_ctx *ctx, uint64_t *polys, size_t batch) { return host_call<Ntt>(ctx, polys, batch, true); }
+fhe_status fhe_ntt_forward_dev(const fhe_ctx *ctx, uint64_t *polys, size_t batch, void *stream) {
+    return dev_call<Ntt>(stream, ctx, polys, batch, false);
 }
 fhe_status fhe_ntt_backward_dev(const fhe_ctx *ctx, uint64_t *polys, size_t batch, void *stream) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        (void)pe;
-        if (batch) need(polys, "polys");
-        ntt_polys(c, true, polys, polys, batch, as_stream(stream));
-    });
-}
-fhe_status fhe_ntt_forward(const fhe_ctx *ctx, uint64_t *polys, size_t batch) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        if (batch) need(polys, "polys");
-        HostIO io;
-        u64 *d = io.in(polys, batch * pe);
-        ntt_polys(c, false, d, d, batch, nullptr);
-        io.back(polys, d, batch * pe);
-    });
-}
-fhe_status fhe_ntt_backward(const fhe_ctx *ctx, uint64_t *polys, size_t batch) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        if (batch) need(polys, "polys");
-        HostIO io;
-        u64 *d = io.in(polys, batch * pe);
-        ntt_polys(c, true, d, d, batch, nullptr);
-        io.back(polys, d, batch * pe);
-    });
+    return dev_call<Ntt>(stream, ctx, polys, batch, true);
 }
 
-static fhe_status ew_host(const fhe_ctx *ctx, uint64_t *a, const uint64_t *b, size_t batch, uint32_t op) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
+struct Ew : Paired {   // a op= b (b absent for neg)
+    uint32_t op;
+    std::array<Io, 2> io;
+    Ew(const fhe_ctx *ctx, uint64_t *a, const uint64_t *b, size_t batch, uint32_t op) : op(op) {
+        need(ctx, "ctx");
+        on(*ctx->c, batch);
         if (batch) {
             need(a, "a");
             if (op != k::EW_NEG) need(b, "b");
         }
-        HostIO io;
-        u64 *da = io.in(a, batch * pe);
-        u64 *db = op != k::EW_NEG ? io.in(b, batch * pe) : nullptr;
-        ew_op(c, da, db, batch, op, nullptr);
-        io.back(a, da, batch * pe);
-    });
-}
-static fhe_status ew_dev(const fhe_ctx *ctx, uint64_t *a, const uint64_t *b, size_t batch, uint32_t op, void *stream) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        (void)pe;
+        const size_t pe = dev->L * dev->n;
+        io = {Io::inout(a, batch, pe), Io::in(b, batch, pe)};
+    }
+    void run(const Ptrs<2> &d, size_t n, hipStream_t s) const { ew_op(*dev, d[0], d[1], n, op, s); }
+};
+fhe_status fhe_poly_add(const fhe_ctx *c, uint64_t *a, const uint64_t *b, size_t n) { return host_call<Ew>(c, a, b, n, k::EW_ADD); }
+fhe_status fhe_poly_sub(const fhe_ctx *c, uint64_t *a, const uint64_t *b, size_t n) { return host_call<Ew>(c, a, b, n, k::EW_SUB); }
+fhe_status fhe_poly_mul(const fhe_ctx *c, uint64_t *a, const uint64_t *b, size_t n) { return host_call<Ew>(c, a, b, n, k::EW_MUL); }
+fhe_status fhe_poly_neg(const fhe_ctx *c, uint64_t *a, size_t n) { return host_call<Ew>(c, a, nullptr, n, k::EW_NEG); }
+fhe_status fhe_poly_add_dev(const fhe_ctx *c, uint64_t *a, const uint64_t *b, size_t n, void *s) { return dev_call<Ew>(s, c, a, b, n, k::EW_ADD); }
+fhe_status fhe_poly_sub_dev(const fhe_ctx *c, uint64_t *a, const uint64_t *b, size_t n, void *s) { return dev_call<Ew>(s, c, a, b, n, k::EW_SUB); }
+fhe_status fhe_poly_mul_dev(const fhe_ctx *c, uint64_t *a, const uint64_t *b, size_t n, void *s) { return dev_call<Ew>(s, c, a, b, n, k::EW_MUL); }
+fhe_status fhe_poly_neg_dev(const fhe_ctx *c, uint64_t *a, size_t n, void *s) { return dev_call<Ew>(s, c, a, nullptr, n, k::EW_NEG); }
+
+struct MulShoup : Paired {   // MulAssign<&Poly<NttShoup>>
+    std::array<Io, 3> io;
+    MulShoup(const fhe_ctx *ctx, uint64_t *a, const uint64_t *b, const uint64_t *b_shoup, size_t batch) {
+        need(ctx, "ctx");
+        on(*ctx->c, batch);
         if (batch) {
             need(a, "a");
-            if (op != k::EW_NEG) need(b, "b");
+            need(b, "b");
+            need(b_shoup, "b_shoup");
         }
-        ew_op(c, a, b, batch, op, as_stream(stream));
-    });
-}
-fhe_status fhe_poly_add(const fhe_ctx *c, uint64_t *a, const uint64_t *b, size_t n) { return ew_host(c, a, b, n, k::EW_ADD); }
-fhe_status fhe_poly_sub(const fhe_ctx *c, uint64_t *a, const uint64_t *b, size_t n) { return ew_host(c, a, b, n, k::EW_SUB); }
-fhe_status fhe_poly_mul(const fhe_ctx *c, uint64_t *a, const uint64_t *b, size_t n) { return ew_host(c, a, b, n, k::EW_MUL); }
-fhe_status fhe_poly_neg(const fhe_ctx *c, uint64_t *a, size_t n) { return ew_host(c, a, nullptr, n, k::EW_NEG); }
-fhe_status fhe_poly_add_dev(const fhe_ctx *c, uint64_t *a, const uint64_t *b, size_t n, void *s) { return ew_dev(c, a, b, n, k::EW_ADD, s); }
-fhe_status fhe_poly_sub_dev(const fhe_ctx *c, uint64_t *a, const uint64_t *b, size_t n, void *s) { return ew_dev(c, a, b, n, k::EW_SUB, s); }
-fhe_status fhe_poly_mul_dev(const fhe_ctx *c, uint64_t *a, const uint64_t *b, size_t n, void *s) { return ew_dev(c, a, b, n, k::EW_MUL, s); }
-fhe_status fhe_poly_neg_dev(const fhe_ctx *c, uint64_t *a, size_t n, void *s) { return ew_dev(c, a, nullptr, n, k::EW_NEG, s); }
-
-static void mul_shoup_run(const Ctx &c, u64 *a, const u64 *b, const u64 *bs, size_t batch, hipStream_t s) {
-    const u64 total = (u64)batch * c.L * c.n;
-    if (!total) return;
-    FHE_LAUNCH("mul_shoup", k::mul_shoup_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s, a, b, bs,
-               c.dmods(), (uint32_t)c.L, (uint32_t)c.logn, total);
+        const size_t pe = dev->L * dev->n;
+        io = {Io::inout(a, batch, pe), Io::in(b, batch, pe), Io::in(b_shoup, batch, pe)};
+    }
+    void run(const Ptrs<3> &d, size_t n, hipStream_t s) const {
+        const Ctx &c = *dev;
+        const u64 total = (u64)n * c.L * c.n;
+        if (!total) return;
+        FHE_LAUNCH("mul_shoup", k::mul_shoup_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s, d[0],
+                   d[1], d[2], c.dmods(), (uint32_t)c.L, (uint32_t)c.logn, total);
+    }
+};
+fhe_status fhe_poly_mul_shoup(const fhe_ctx *ctx, uint64_t *a, const uint64_t *b, const uint64_t *b_shoup,
+                              size_t batch) {
+    return host_call<MulShoup>(ctx, a, b, b_shoup, batch);
 }
 fhe_status fhe_poly_mul_shoup_dev(const fhe_ctx *ctx, uint64_t *a, const uint64_t *b, const uint64_t *b_shoup,
                                   size_t batch, void *stream) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        (void)pe;
-        if (batch) {
-            need(a, "a");
-            need(b, "b");
-            need(b_shoup, "b_shoup");
-        }
-        mul_shoup_run(c, a, b, b_shoup, batch, as_stream(stream));
-    });
-}
-fhe_status fhe_poly_mul_shoup(const fhe_ctx *ctx, uint64_t *a, const uint64_t *b, const uint64_t *b_shoup,
-                              size_t batch) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        if (batch) {
-            need(a, "a");
-            need(b, "b");
-            need(b_shoup, "b_shoup");
-        }
-        HostIO io;
-        u64 *da = io.in(a, batch * pe), *db = io.in(b, batch * pe), *dbs = io.in(b_shoup, batch * pe);
-        mul_shoup_run(c, da, db, dbs, batch, nullptr);
-        io.back(a, da, batch * pe);
-    });
+    return dev_call<MulShoup>(stream, ctx, a, b, b_shoup, batch);
 }
 fhe_status fhe_poly_shoup(const fhe_ctx *ctx, const uint64_t *a, uint64_t *a_shoup, size_t batch) {
     return guard([&] {
@@ -595,152 +624,142 @@ fhe_status fhe_poly_shoup(const fhe_ctx *ctx, const uint64_t *a, uint64_t *a_sho
     });
 }
 
+struct Substitute : Paired {   // Poly::substitute; `out` is written only (the host form stages it separately)
+    size_t exponent;
+    bool ntt;
+    std::array<Io, 2> io;
+    Substitute(const fhe_ctx *ctx, size_t exponent, const uint64_t *in, uint64_t *out, size_t batch, int repr_is_ntt)
+        : exponent(exponent), ntt(repr_is_ntt != 0) {
+        need(ctx, "ctx");
+        on(*ctx->c, batch);
+        if (batch) {
+            need(in, "in");
+            need(out, "out");
+        }
+        const size_t pe = dev->L * dev->n;
+        io = {Io::in(in, batch, pe), Io::out(out, batch, pe)};
+    }
+    void run(const Ptrs<2> &d, size_t n, hipStream_t s) const { substitute_polys(*dev, exponent, d[0], d[1], n, ntt, s); }
+};
+fhe_status fhe_poly_substitute(const fhe_ctx *ctx, size_t exponent, const uint64_t *in, uint64_t *out, size_t batch,
+                               int repr_is_ntt) {
+    return host_call<Substitute>(ctx, exponent, in, out, batch, repr_is_ntt);
+}
 fhe_status fhe_poly_substitute_dev(const fhe_ctx *ctx, size_t exponent, const uint64_t *in, uint64_t *out,
                                    size_t batch, int repr_is_ntt, void *stream) {
     return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        (void)pe;
-        if (batch) {
-            need(in, "in");
-            need(out, "out");
-        }
+        Substitute op(ctx, exponent, in, out, batch, repr_is_ntt);
+        // (device form only: the kernel does not work in place, and here `in` and `out` are the kernel's own arrays;
+        // the host form stages them into separate blocks and so accepts in == out)
         if (in == out) throw StatusError(FHE_E_ARG, "substitute is not in-place");
-        substitute_polys(c, exponent, in, out, batch, repr_is_ntt != 0, as_stream(stream));
-    });
-}
-fhe_status fhe_poly_substitute(const fhe_ctx *ctx, size_t exponent, const uint64_t *in, uint64_t *out, size_t batch,
-                               int repr_is_ntt) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        if (batch) {
-            need(in, "in");
-            need(out, "out");
-        }
-        HostIO io;
-        u64 *di = io.in(in, batch * pe), *dout = io.out(batch * pe);
-        substitute_polys(c, exponent, di, dout, batch, repr_is_ntt != 0, nullptr);
-        io.back(out, dout, batch * pe);
+        run_dev(op, stream);
     });
 }
 
 size_t fhe_poly_serialized_size(const fhe_ctx *ctx) { return ctx ? wire_poly_bytes(*ctx->c) : 0; }
+// Rq wire format: the byte arrays are staged in bytes
+struct Serialize : Paired {
+    bool from_ntt;
+    std::array<Io, 2> io;
+    Serialize(const fhe_ctx *ctx, const uint64_t *polys, uint8_t *bytes, size_t batch, int from_ntt)
+        : from_ntt(from_ntt != 0) {
+        need(ctx, "ctx");
+        on(*ctx->c, batch);
+        if (batch) {
+            need(polys, "polys");
+            need(bytes, "bytes");
+        }
+        io = {Io::in(polys, batch, dev->L * dev->n), Io{bytes, batch, wire_poly_bytes(*dev), Io::OUT}};
+    }
+    void run(const Ptrs<2> &d, size_t n, hipStream_t s) const {
+        wire_serialize(*dev, d[0], reinterpret_cast<uint8_t *>(d[1]), n, from_ntt, s);
+    }
+};
+fhe_status fhe_poly_serialize(const fhe_ctx *ctx, const uint64_t *polys, uint8_t *bytes, size_t batch, int from_ntt) {
+    return host_call<Serialize>(ctx, polys, bytes, batch, from_ntt);
+}
 fhe_status fhe_poly_serialize_dev(const fhe_ctx *ctx, const uint64_t *polys, uint8_t *bytes, size_t batch, int from_ntt,
                                   void *stream) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        (void)pe;
-        if (batch) {
-            need(polys, "polys");
-            need(bytes, "bytes");
-        }
-        wire_serialize(c, polys, bytes, batch, from_ntt != 0, as_stream(stream));
-    });
+    return dev_call<Serialize>(stream, ctx, polys, bytes, batch, from_ntt);
 }
-fhe_status fhe_poly_serialize(const fhe_ctx *ctx, const uint64_t *polys, uint8_t *bytes, size_t batch, int from_ntt) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
+struct Deserialize : Paired {
+    bool to_ntt;
+    std::array<Io, 2> io;
+    Deserialize(const fhe_ctx *ctx, const uint8_t *bytes, uint64_t *polys, size_t batch, int to_ntt) : to_ntt(to_ntt != 0) {
+        need(ctx, "ctx");
+        on(*ctx->c, batch);
         if (batch) {
             need(polys, "polys");
             need(bytes, "bytes");
         }
-        const size_t wb = wire_poly_bytes(c);
-        HostIO io;
-        u64 *di = io.in(polys, batch * pe);
-        uint8_t *db = reinterpret_cast<uint8_t *>(io.out((batch * wb + 7) / 8));
-        wire_serialize(c, di, db, batch, from_ntt != 0, nullptr);
-        FHE_HIP_CHECK(hipStreamSynchronize(nullptr));
-        if (batch) FHE_HIP_CHECK(hipMemcpy(bytes, db, batch * wb, hipMemcpyDeviceToHost));
-    });
+        io = {Io{bytes, batch, wire_poly_bytes(*dev), Io::IN}, Io::out(polys, batch, dev->L * dev->n)};
+    }
+    void run(const Ptrs<2> &d, size_t n, hipStream_t s) const {
+        wire_deserialize(*dev, reinterpret_cast<const uint8_t *>(d[0]), d[1], n, to_ntt, s);
+    }
+};
+fhe_status fhe_poly_deserialize(const fhe_ctx *ctx, const uint8_t *bytes, uint64_t *polys, size_t batch, int to_ntt) {
+    return host_call<Deserialize>(ctx, bytes, polys, batch, to_ntt);
 }
 fhe_status fhe_poly_deserialize_dev(const fhe_ctx *ctx, const uint8_t *bytes, uint64_t *polys, size_t batch, int to_ntt,
                                     void *stream) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        (void)pe;
-        if (batch) {
-            need(polys, "polys");
-            need(bytes, "bytes");
-        }
-        wire_deserialize(c, bytes, polys, batch, to_ntt != 0, as_stream(stream));
-    });
-}
-fhe_status fhe_poly_deserialize(const fhe_ctx *ctx, const uint8_t *bytes, uint64_t *polys, size_t batch, int to_ntt) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        if (batch) {
-            need(polys, "polys");
-            need(bytes, "bytes");
-        }
-        const size_t wb = wire_poly_bytes(c);
-        HostIO io;
-        uint8_t *db = reinterpret_cast<uint8_t *>(io.out((batch * wb + 7) / 8));
-        if (batch) FHE_HIP_CHECK(hipMemcpy(db, bytes, batch * wb, hipMemcpyHostToDevice));
-        u64 *dout = io.out(batch * pe);
-        wire_deserialize(c, db, dout, batch, to_ntt != 0, nullptr);
-        io.back(polys, dout, batch * pe);
-    });
+    return dev_call<Deserialize>(stream, ctx, bytes, polys, batch, to_ntt);
 }
 
-fhe_status fhe_poly_switch_down_dev(const fhe_ctx *ctx, const uint64_t *in, uint64_t *out, size_t batch, void *stream) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        if (!c.next) throw StatusError(FHE_E_NO_MORE_CONTEXT, "NoMoreContext");
+struct SwitchDown : Paired {   // Poly::<PowerBasis>::switch_down
+    std::array<Io, 2> io;
+    SwitchDown(const fhe_ctx *ctx, const uint64_t *in, uint64_t *out, size_t batch) {
+        need(ctx, "ctx");
+        on(*ctx->c, batch);
+        if (!dev->next) throw StatusError(FHE_E_NO_MORE_CONTEXT, "NoMoreContext");
         if (batch) {
             need(in, "in");
             need(out, "out");
         }
-        switch_down_polys(c, in, pe, out, pe - c.n, batch, as_stream(stream));
-    });
-}
+        const size_t pe = dev->L * dev->n;
+        io = {Io::in(in, batch, pe), Io::out(out, batch, pe - dev->n)};
+    }
+    void run(const Ptrs<2> &d, size_t n, hipStream_t s) const {
+        const size_t pe = dev->L * dev->n;
+        switch_down_polys(*dev, d[0], pe, d[1], pe - dev->n, n, s);
+    }
+};
 fhe_status fhe_poly_switch_down(const fhe_ctx *ctx, const uint64_t *in, uint64_t *out, size_t batch) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
+    return host_call<SwitchDown>(ctx, in, out, batch);
+}
+fhe_status fhe_poly_switch_down_dev(const fhe_ctx *ctx, const uint64_t *in, uint64_t *out, size_t batch, void *stream) {
+    return dev_call<SwitchDown>(stream, ctx, in, out, batch);
+}
+
+struct SwitchDownTo : Paired {   // Poly::<PowerBasis>::switch_down_to
+    size_t iters = 0;
+    std::array<Io, 2> io;
+    SwitchDownTo(const fhe_ctx *from, const fhe_ctx *to, const uint64_t *in, uint64_t *out, size_t batch) {
+        need(from, "from");
+        need(to, "to");
+        on(*from->c, batch);
+        const long it = from->c->niterations_to(*to->c);
+        if (it < 0) throw StatusError(FHE_E_CONTEXT_NOT_REACHABLE, "ContextNotReachable");
+        iters = (size_t)it;
         if (batch) {
             need(in, "in");
             need(out, "out");
         }
-        if (!c.next) throw StatusError(FHE_E_NO_MORE_CONTEXT, "NoMoreContext");
-        HostIO io;
-        u64 *di = io.in(in, batch * pe), *dout = io.out(batch * (pe - c.n));
-        switch_down_polys(c, di, pe, dout, pe - c.n, batch, nullptr);
-        io.back(out, dout, batch * (pe - c.n));
-    });
-}
-
-static size_t iterations_between(const Ctx &from, const Ctx &to) {
-    const long it = from.niterations_to(to);
-    if (it < 0) throw StatusError(FHE_E_CONTEXT_NOT_REACHABLE, "ContextNotReachable");
-    return (size_t)it;
+        const size_t pe = dev->L * dev->n;
+        io = {Io::in(in, batch, pe), Io::out(out, batch, pe - iters * dev->n)};
+    }
+    void run(const Ptrs<2> &d, size_t n, hipStream_t s) const {
+        const size_t pe = dev->L * dev->n;
+        switch_down_to_pb(*dev, iters, d[0], pe, d[1], pe - iters * dev->n, n, s);
+    }
+};
+fhe_status fhe_poly_switch_down_to(const fhe_ctx *from, const fhe_ctx *to, const uint64_t *in, uint64_t *out,
+                                   size_t batch) {
+    return host_call<SwitchDownTo>(from, to, in, out, batch);
 }
 fhe_status fhe_poly_switch_down_to_dev(const fhe_ctx *from, const fhe_ctx *to, const uint64_t *in, uint64_t *out,
                                        size_t batch, void *stream) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(from);
-        need(to, "to");
-        const size_t iters = iterations_between(c, *to->c);
-        if (batch) {
-            need(in, "in");
-            need(out, "out");
-        }
-        switch_down_to_pb(c, iters, in, pe, out, pe - iters * c.n, batch, as_stream(stream));
-    });
-}
-fhe_status fhe_poly_switch_down_to(const fhe_ctx *from, const fhe_ctx *to, const uint64_t *in, uint64_t *out,
-                                   size_t batch) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(from);
-        need(to, "to");
-        const size_t iters = iterations_between(c, *to->c);
-        if (batch) {
-            need(in, "in");
-            need(out, "out");
-        }
-        const size_t po = pe - iters * c.n;
-        HostIO io;
-        u64 *di = io.in(in, batch * pe), *dout = io.out(batch * po);
-        switch_down_to_pb(c, iters, di, pe, dout, po, batch, nullptr);
-        io.back(out, dout, batch * po);
-    });
+    return dev_call<SwitchDownTo>(stream, from, to, in, out, batch);
 }
 
 // -------------------------------------------------------------------------- scaler ----
@@ -858,119 +877,100 @@ fhe_status fhe_scaler_get_constants(const fhe_scaler *s, int which, uint64_t *ou
         }
     });
 }
+struct Scale : Paired {   // Scaler::scale
+    const Scaler *sc;
+    bool ntt;
+    std::array<Io, 2> io;
+    Scale(const fhe_scaler *s, const uint64_t *in, uint64_t *out, size_t batch, int repr_is_ntt) : ntt(repr_is_ntt != 0) {
+        need(s, "scaler");
+        sc = s->s.get();
+        on(*sc->from, batch);
+        if (batch) {
+            need(in, "in");
+            need(out, "out");
+        }
+        io = {Io::in(in, batch, sc->from->L * sc->from->n), Io::out(out, batch, sc->to->L * sc->to->n, Io::ZEROED)};
+    }
+    void run(const Ptrs<2> &d, size_t n, hipStream_t s) const { scale_polys(*sc, d[0], d[1], n, ntt, s); }
+};
+fhe_status fhe_poly_scale(const fhe_scaler *s, const uint64_t *in, uint64_t *out, size_t batch, int repr_is_ntt) {
+    return host_call<Scale>(s, in, out, batch, repr_is_ntt);
+}
 fhe_status fhe_poly_scale_dev(const fhe_scaler *s, const uint64_t *in, uint64_t *out, size_t batch, int repr_is_ntt,
                               void *stream) {
-    return guard([&] {
-        need(s, "scaler");
-        if (batch) {
-            need(in, "in");
-            need(out, "out");
-        }
-        set_device(*s->s->from);
-        scale_polys(*s->s, in, out, batch, repr_is_ntt != 0, as_stream(stream));
-    });
-}
-fhe_status fhe_poly_scale(const fhe_scaler *s, const uint64_t *in, uint64_t *out, size_t batch, int repr_is_ntt) {
-    return guard([&] {
-        need(s, "scaler");
-        if (batch) {
-            need(in, "in");
-            need(out, "out");
-        }
-        const Scaler &sc = *s->s;
-        sc.from->need_device();
-        set_device(*sc.from);
-        HostIO io;
-        const size_t ie = sc.from->L * sc.from->n, oe = sc.to->L * sc.to->n;
-        u64 *di = io.in(in, batch * ie), *dout = io.out(batch * oe);
-        FHE_HIP_CHECK(hipMemsetAsync(dout, 0, std::max<size_t>(batch * oe, 1) * sizeof(u64), nullptr));
-        scale_polys(sc, di, dout, batch, repr_is_ntt != 0, nullptr);
-        io.back(out, dout, batch * oe);
-    });
+    return dev_call<Scale>(stream, s, in, out, batch, repr_is_ntt);
 }
 
 // ----------------------------------------------------------------------------- ksk ----
+// fhe_ksk_create(_dev)'s checks: handles, the key's geometry and device (make_ksk), then the key arrays.
+static std::unique_ptr<fhe_ksk> ksk_new(const fhe_ctx *ct_ctx, const fhe_ctx *ksk_ctx, size_t ndigits, const void *c0,
+                                        const void *c1, size_t log_base, fhe_ksk **out) {
+    need(ct_ctx, "ct_ctx");
+    need(ksk_ctx, "ksk_ctx");
+    need(out, "out");
+    *out = nullptr;
+    set_device(*ksk_ctx->c);
+    auto h = std::make_unique<fhe_ksk>();
+    h->k = make_ksk(*ct_ctx->c, *ksk_ctx->c, ndigits, log_base);
+    need(c0, "c0");
+    need(c1, "c1");
+    return h;
+}
+// Uploads the key from HOST arrays.  Every coefficient must be a canonical residue (the Shoup quotient of an unreduced
+// value does not fit 64 bits and the key would silently give wrong results); supplied twins must be the twins, missing
+// ones are computed.
+static void ksk_upload(Ksk &k_, const u64 *c0, const u64 *c0_shoup, const u64 *c1, const u64 *c1_shoup) {
+    const Ctx &kc = *k_.ksk_ctx;
+    const size_t count = k_.ndigits * kc.L * kc.n;
+    auto up = [&](DevBuf<u64> &d, const u64 *src) {
+        d.alloc(count);
+        FHE_HIP_CHECK(hipMemcpy(d.p, src, count * sizeof(u64), hipMemcpyHostToDevice));
+    };
+    auto shoup_of = [&](const u64 *src, const u64 *given) {
+        std::vector<u64> v(count);
+        for (size_t i = 0; i < k_.ndigits; i++)
+            for (size_t r = 0; r < kc.L; r++)
+                for (size_t j = 0; j < kc.n; j++) {
+                    const size_t x = (i * kc.L + r) * kc.n + j;
+                    if (src[x] >= kc.moduli[r]) throw StatusError(FHE_E_ARG, "key coefficient not reduced");
+                    v[x] = shoup(src[x], kc.moduli[r]);
+                    if (given && given[x] != v[x])
+                        throw StatusError(FHE_E_ARG, "Shoup twin is not floor(c * 2^64 / q)");
+                }
+        return v;
+    };
+    up(k_.c0, c0);
+    up(k_.c1, c1);
+    {
+        auto v = shoup_of(c0, c0_shoup);
+        up(k_.c0s, v.data());
+    }
+    {
+        auto v = shoup_of(c1, c1_shoup);
+        up(k_.c1s, v.data());
+    }
+    ksk_fill_f64(k_, c0, c1);
+}
 fhe_status fhe_ksk_create(const fhe_ctx *ct_ctx, const fhe_ctx *ksk_ctx, size_t ndigits, const uint64_t *c0,
                           const uint64_t *c0_shoup, const uint64_t *c1, const uint64_t *c1_shoup, size_t log_base,
                           fhe_ksk **out) {
     return guard([&] {
-        need(ct_ctx, "ct_ctx");
-        need(ksk_ctx, "ksk_ctx");
-        need(out, "out");
-        *out = nullptr;
-        need(c0, "c0");
-        need(c1, "c1");
-        const Ctx &kc = *ksk_ctx->c;
-        set_device(kc);
-        auto h = std::make_unique<fhe_ksk>();
-        h->k = make_ksk(*ct_ctx->c, kc, ndigits, log_base);
-        const size_t count = ndigits * kc.L * kc.n;
-        auto up = [&](DevBuf<u64> &d, const u64 *src) {
-            d.alloc(count);
-            FHE_HIP_CHECK(hipMemcpy(d.p, src, count * sizeof(u64), hipMemcpyHostToDevice));
-        };
-        // every coefficient must be a canonical residue (the Shoup quotient of an unreduced value does not fit
-        // 64 bits and the key would silently give wrong results); supplied twins must be the twins
-        auto shoup_of = [&](const u64 *src, const u64 *given) {
-            std::vector<u64> v(count);
-            for (size_t i = 0; i < ndigits; i++)
-                for (size_t r = 0; r < kc.L; r++)
-                    for (size_t j = 0; j < kc.n; j++) {
-                        const size_t x = (i * kc.L + r) * kc.n + j;
-                        if (src[x] >= kc.moduli[r]) throw StatusError(FHE_E_ARG, "key coefficient not reduced");
-                        v[x] = shoup(src[x], kc.moduli[r]);
-                        if (given && given[x] != v[x])
-                            throw StatusError(FHE_E_ARG, "Shoup twin is not floor(c * 2^64 / q)");
-                    }
-            return v;
-        };
-        up(h->k->c0, c0);
-        up(h->k->c1, c1);
-        {
-            auto v = shoup_of(c0, c0_shoup);
-            up(h->k->c0s, v.data());
-        }
-        {
-            auto v = shoup_of(c1, c1_shoup);
-            up(h->k->c1s, v.data());
-        }
-        ksk_fill_f64(*h->k, c0, c1);
+        auto h = ksk_new(ct_ctx, ksk_ctx, ndigits, c0, c1, log_base, out);
+        ksk_upload(*h->k, c0, c0_shoup, c1, c1_shoup);
         *out = h.release();
     });
 }
 fhe_status fhe_ksk_create_dev(const fhe_ctx *ct_ctx, const fhe_ctx *ksk_ctx, size_t ndigits, const uint64_t *c0,
                               const uint64_t *c1, size_t log_base, void *stream, fhe_ksk **out) {
     return guard([&] {
-        need(ct_ctx, "ct_ctx");
-        need(ksk_ctx, "ksk_ctx");
-        need(out, "out");
-        *out = nullptr;
-        need(c0, "c0");
-        need(c1, "c1");
-        const Ctx &kc = *ksk_ctx->c;
-        set_device(kc);
-        auto h = std::make_unique<fhe_ksk>();
-        h->k = make_ksk(*ct_ctx->c, kc, ndigits, log_base);
-        const size_t count = ndigits * kc.L * kc.n;
-        hipStream_t s = as_stream(stream);
-        FHE_HIP_CHECK(hipStreamSynchronize(s));
-        std::vector<u64> h0(count), h1(count), s0(count), s1(count);
+        auto h = ksk_new(ct_ctx, ksk_ctx, ndigits, c0, c1, log_base, out);
+        // the device arrays come down once and take the host path (the checks and twins are host computations)
+        const size_t count = ndigits * ksk_ctx->c->L * ksk_ctx->c->n;
+        FHE_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
+        std::vector<u64> h0(count), h1(count);
         FHE_HIP_CHECK(hipMemcpy(h0.data(), c0, count * sizeof(u64), hipMemcpyDeviceToHost));
         FHE_HIP_CHECK(hipMemcpy(h1.data(), c1, count * sizeof(u64), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < ndigits; i++)
-            for (size_t r = 0; r < kc.L; r++)
-                for (size_t j = 0; j < kc.n; j++) {
-                    const size_t x = (i * kc.L + r) * kc.n + j;
-                    if (h0[x] >= kc.moduli[r] || h1[x] >= kc.moduli[r])
-                        throw StatusError(FHE_E_ARG, "key coefficient not reduced");
-                    s0[x] = shoup(h0[x], kc.moduli[r]);
-                    s1[x] = shoup(h1[x], kc.moduli[r]);
-                }
-        h->k->c0.upload(h0);
-        h->k->c1.upload(h1);
-        h->k->c0s.upload(s0);
-        h->k->c1s.upload(s1);
-        ksk_fill_f64(*h->k, h0.data(), h1.data());
+        ksk_upload(*h->k, h0.data(), nullptr, h1.data(), nullptr);
         *out = h.release();
     });
 }
@@ -991,424 +991,354 @@ fhe_status fhe_ksk_get_mode(const fhe_ksk *k_, int *mode, size_t *w_budget) {
     });
 }
 
+struct KeySwitch : Paired {   // KeySwitchingKey::key_switch: two outputs
+    const Ksk *ks;
+    std::array<Io, 3> io;
+    KeySwitch(const fhe_ksk *k_, const uint64_t *p, uint64_t *c0_out, uint64_t *c1_out, size_t batch) {
+        need(k_, "ksk");
+        ks = k_->k.get();
+        on(*ks->ksk_ctx, batch);
+        if (batch) {
+            need(p, "p");
+            need(c0_out, "c0_out");
+            need(c1_out, "c1_out");
+        }
+        const size_t ie = ks->ct_ctx->L * ks->ct_ctx->n, oe = ks->ksk_ctx->L * ks->ksk_ctx->n;
+        io = {Io::in(p, batch, ie), Io::out(c0_out, batch, oe), Io::out(c1_out, batch, oe)};
+    }
+    void run(const Ptrs<3> &d, size_t n, hipStream_t s) const {
+        key_switch_polys(*ks, d[0], (u64)ks->ct_ctx->L * ks->ct_ctx->n, d[1], d[2], (u64)ks->ksk_ctx->L * ks->ksk_ctx->n,
+                         nullptr, nullptr, 0, n, s);
+    }
+};
+fhe_status fhe_key_switch(const fhe_ksk *k_, const uint64_t *p, uint64_t *c0_out, uint64_t *c1_out, size_t batch) {
+    return host_call<KeySwitch>(k_, p, c0_out, c1_out, batch);
+}
 fhe_status fhe_key_switch_dev(const fhe_ksk *k_, const uint64_t *p, uint64_t *c0_out, uint64_t *c1_out, size_t batch,
                               void *stream) {
-    return guard([&] {
-        need(k_, "ksk");
-        if (batch) {
-            need(p, "p");
-            need(c0_out, "c0_out");
-            need(c1_out, "c1_out");
-        }
-        const Ksk &ks = *k_->k;
-        set_device(*ks.ksk_ctx);
-        key_switch_polys(ks, p, (u64)ks.ct_ctx->L * ks.ct_ctx->n, c0_out, c1_out, (u64)ks.ksk_ctx->L * ks.ksk_ctx->n,
-                         nullptr, nullptr, 0, batch, as_stream(stream));
-    });
-}
-fhe_status fhe_key_switch(const fhe_ksk *k_, const uint64_t *p, uint64_t *c0_out, uint64_t *c1_out, size_t batch) {
-    return guard([&] {
-        need(k_, "ksk");
-        if (batch) {
-            need(p, "p");
-            need(c0_out, "c0_out");
-            need(c1_out, "c1_out");
-        }
-        const Ksk &ks = *k_->k;
-        set_device(*ks.ksk_ctx);
-        HostIO io;
-        const size_t ie = ks.ct_ctx->L * ks.ct_ctx->n, oe = ks.ksk_ctx->L * ks.ksk_ctx->n;
-        u64 *dp = io.in(p, batch * ie), *d0 = io.out(batch * oe), *d1 = io.out(batch * oe);
-        key_switch_polys(ks, dp, ie, d0, d1, oe, nullptr, nullptr, 0, batch, nullptr);
-        io.back(c0_out, d0, batch * oe);
-        io.back(c1_out, d1, batch * oe);
-    });
+    return dev_call<KeySwitch>(stream, k_, p, c0_out, c1_out, batch);
 }
 
-// relinearizes: ct3 [b][3][L][N] -> out [b][2][L][N]
-static void relinearize_run(const Ksk &ks, const u64 *ct3, u64 *out, size_t batch, hipStream_t s) {
-    const Ctx &cc = *ks.ct_ctx;
-    const u64 PL = (u64)cc.L * cc.n;
-    if (!batch) return;
-    WsGuard c2(batch * PL * sizeof(u64), s);
-    k::RowMap m = full_map(cc, cc.L);
-    m.src_poly_stride = 3 * PL;
-    m.dst_poly_stride = PL;
-    launch_ntt(cc, true, ct3 + 2 * PL, c2.u(), m, batch, s);
-    // (c2 in Ntt form doubles as the transforms of digit j under key modulus j)
-    key_switch_add(ks, c2.u(), PL, ct3, ct3 + PL, 3 * PL, out, out + PL, 2 * PL, batch, s, ct3 + 2 * PL, 3 * PL);
+struct Relinearize : Paired {   // RelinearizationKey::relinearizes: ct3 [b][3][L][N] -> out [b][2][L][N]
+    static constexpr bool sliced = true;
+    const Ksk *ks;
+    std::array<Io, 2> io;
+    Relinearize(const fhe_ksk *rk, const uint64_t *ct3, uint64_t *out, size_t batch) {
+        need(rk, "rk");
+        ks = rk->k.get();
+        on(*ks->ksk_ctx, batch);
+        if (batch) {
+            need(ct3, "ct3");
+            need(out, "out");
+        }
+        const size_t pe = ks->ct_ctx->L * ks->ct_ctx->n;
+        io = {Io::in(ct3, batch, 3 * pe), Io::out(out, batch, 2 * pe)};
+    }
+    void run(const Ptrs<2> &d, size_t n, hipStream_t s) const {
+        const Ctx &cc = *ks->ct_ctx;
+        const u64 PL = (u64)cc.L * cc.n;
+        const u64 *ct3 = d[0];
+        if (!n) return;
+        WsGuard c2(n * PL * sizeof(u64), s);
+        k::RowMap m = full_map(cc, cc.L);
+        m.src_poly_stride = 3 * PL;
+        m.dst_poly_stride = PL;
+        launch_ntt(cc, true, ct3 + 2 * PL, c2.u(), m, n, s);
+        // (c2 in Ntt form doubles as the transforms of digit j under key modulus j)
+        key_switch_add(*ks, c2.u(), PL, ct3, ct3 + PL, 3 * PL, d[1], d[1] + PL, 2 * PL, n, s, ct3 + 2 * PL, 3 * PL);
+    }
+};
+fhe_status fhe_bfv_relinearize(const fhe_ksk *rk, const uint64_t *ct3, uint64_t *out, size_t batch) {
+    return host_call<Relinearize>(rk, ct3, out, batch);
 }
 fhe_status fhe_bfv_relinearize_dev(const fhe_ksk *rk, const uint64_t *ct3, uint64_t *out, size_t batch, void *stream) {
-    return guard([&] {
-        need(rk, "rk");
-        if (batch) {
-            need(ct3, "ct3");
-            need(out, "out");
-        }
-        set_device(*rk->k->ksk_ctx);
-        relinearize_run(*rk->k, ct3, out, batch, as_stream(stream));
-    });
-}
-fhe_status fhe_bfv_relinearize(const fhe_ksk *rk, const uint64_t *ct3, uint64_t *out, size_t batch) {
-    return guard([&] {
-        need(rk, "rk");
-        if (batch) {
-            need(ct3, "ct3");
-            need(out, "out");
-        }
-        const Ksk &ks = *rk->k;
-        set_device(*ks.ksk_ctx);
-        const size_t pe = ks.ct_ctx->L * ks.ct_ctx->n;
-        if (host_sliced(ks.ksk_ctx->device, batch, {{ct3, 3 * pe}}, out, 2 * pe,
-                        [&](const std::vector<const u64 *> &d, u64 *o, size_t n, hipStream_t st) {
-                            relinearize_run(ks, d[0], o, n, st);
-                        }))
-            return;
-        HostIO io;
-        u64 *di = io.in(ct3, batch * 3 * pe), *dout = io.out(batch * 2 * pe);
-        relinearize_run(ks, di, dout, batch, nullptr);
-        io.back(out, dout, batch * 2 * pe);
-    });
+    return dev_call<Relinearize>(stream, rk, ct3, out, batch);
 }
 
-static void galois_run(const Ksk &ks, size_t exponent, const u64 *ct, u64 *out, size_t batch, hipStream_t s) {
-    galois_apply(ks, exponent, ct, out, batch, s);
+struct Galois : Paired {   // GaloisKey::relinearize
+    static constexpr bool sliced = true;
+    const Ksk *ks;
+    size_t exponent;
+    std::array<Io, 2> io;
+    Galois(const fhe_ksk *gk, size_t exponent, const uint64_t *ct, uint64_t *out, size_t batch) : exponent(exponent) {
+        need(gk, "gk");
+        ks = gk->k.get();
+        on(*ks->ksk_ctx, batch);
+        if (batch) {
+            need(ct, "ct");
+            need(out, "out");
+        }
+        const size_t pe = ks->ct_ctx->L * ks->ct_ctx->n;
+        io = {Io::in(ct, batch, 2 * pe), Io::out(out, batch, 2 * pe)};
+    }
+    void run(const Ptrs<2> &d, size_t n, hipStream_t s) const { galois_apply(*ks, exponent, d[0], d[1], n, s); }
+};
+fhe_status fhe_bfv_galois(const fhe_ksk *gk, size_t exponent, const uint64_t *ct, uint64_t *out, size_t batch) {
+    return host_call<Galois>(gk, exponent, ct, out, batch);
 }
 fhe_status fhe_bfv_galois_dev(const fhe_ksk *gk, size_t exponent, const uint64_t *ct, uint64_t *out, size_t batch,
                               void *stream) {
-    return guard([&] {
-        need(gk, "gk");
-        if (batch) {
-            need(ct, "ct");
-            need(out, "out");
-        }
-        set_device(*gk->k->ksk_ctx);
-        galois_run(*gk->k, exponent, ct, out, batch, as_stream(stream));
-    });
-}
-fhe_status fhe_bfv_galois(const fhe_ksk *gk, size_t exponent, const uint64_t *ct, uint64_t *out, size_t batch) {
-    return guard([&] {
-        need(gk, "gk");
-        if (batch) {
-            need(ct, "ct");
-            need(out, "out");
-        }
-        const Ksk &ks = *gk->k;
-        set_device(*ks.ksk_ctx);
-        const size_t pe = ks.ct_ctx->L * ks.ct_ctx->n;
-        if (host_sliced(ks.ksk_ctx->device, batch, {{ct, 2 * pe}}, out, 2 * pe,
-                        [&](const std::vector<const u64 *> &d, u64 *o, size_t n, hipStream_t st) {
-                            galois_run(ks, exponent, d[0], o, n, st);
-                        }))
-            return;
-        HostIO io;
-        u64 *di = io.in(ct, batch * 2 * pe), *dout = io.out(batch * 2 * pe);
-        galois_run(ks, exponent, di, dout, batch, nullptr);
-        io.back(out, dout, batch * 2 * pe);
-    });
+    return dev_call<Galois>(stream, gk, exponent, ct, out, batch);
 }
 
+struct BfvSwitchDown : Paired {   // Ciphertext::switch_down
+    size_t nparts;
+    std::array<Io, 2> io;
+    BfvSwitchDown(const fhe_ctx *ctx, size_t nparts, const uint64_t *ct, uint64_t *out, size_t batch) : nparts(nparts) {
+        need(ctx, "ctx");
+        on(*ctx->c, batch);
+        if (!dev->next) throw StatusError(FHE_E_NO_MORE_CONTEXT, "NoMoreContext");
+        if (batch && nparts) {
+            need(ct, "ct");
+            need(out, "out");
+        }
+        const size_t pe = dev->L * dev->n;
+        io = {Io::in(ct, batch, nparts * pe), Io::out(out, batch, nparts * (pe - dev->n))};
+    }
+    void run(const Ptrs<2> &d, size_t n, hipStream_t s) const { bfv_switch_down(*dev, nparts, d[0], d[1], n, s); }
+};
+fhe_status fhe_bfv_switch_down(const fhe_ctx *ctx, size_t nparts, const uint64_t *ct, uint64_t *out, size_t batch) {
+    return host_call<BfvSwitchDown>(ctx, nparts, ct, out, batch);
+}
 fhe_status fhe_bfv_switch_down_dev(const fhe_ctx *ctx, size_t nparts, const uint64_t *ct, uint64_t *out, size_t batch,
                                    void *stream) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        (void)pe;
-        if (!c.next) throw StatusError(FHE_E_NO_MORE_CONTEXT, "NoMoreContext");
-        if (batch && nparts) {
-            need(ct, "ct");
-            need(out, "out");
-        }
-        bfv_switch_down(c, nparts, ct, out, batch, as_stream(stream));
-    });
-}
-fhe_status fhe_bfv_switch_down(const fhe_ctx *ctx, size_t nparts, const uint64_t *ct, uint64_t *out, size_t batch) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        if (batch && nparts) {
-            need(ct, "ct");
-            need(out, "out");
-        }
-        if (!c.next) throw StatusError(FHE_E_NO_MORE_CONTEXT, "NoMoreContext");
-        HostIO io;
-        u64 *di = io.in(ct, batch * nparts * pe), *dout = io.out(batch * nparts * (pe - c.n));
-        bfv_switch_down(c, nparts, di, dout, batch, nullptr);
-        io.back(out, dout, batch * nparts * (pe - c.n));
-    });
+    return dev_call<BfvSwitchDown>(stream, ctx, nparts, ct, out, batch);
 }
 
-// Ciphertext::switch_to_level (F/bfv/ciphertext.rs:164-183), `levels` = target_level - level
-static void check_levels(const Ctx &c, size_t levels) {
-    if (!c.at_level(levels))
-        throw StatusError(FHE_E_INVALID_LEVEL, "InvalidLevel: the context chain has " + std::to_string(c.L - 1) +
-                                                   " levels below this one, asked for " + std::to_string(levels));
+struct SwitchToLevel : Paired {   // Ciphertext::switch_to_level (F/bfv/ciphertext.rs:164-183), `levels` = target_level - level
+    size_t levels, nparts;
+    std::array<Io, 2> io;
+    SwitchToLevel(const fhe_ctx *ctx, size_t levels, size_t nparts, const uint64_t *ct, uint64_t *out, size_t batch)
+        : levels(levels), nparts(nparts) {
+        need(ctx, "ctx");
+        on(*ctx->c, batch);
+        if (!dev->at_level(levels))
+            throw StatusError(FHE_E_INVALID_LEVEL, "InvalidLevel: the context chain has " + std::to_string(dev->L - 1) +
+                                                       " levels below this one, asked for " + std::to_string(levels));
+        if (batch && nparts) {
+            need(ct, "ct");
+            need(out, "out");
+        }
+        const size_t pe = dev->L * dev->n;
+        io = {Io::in(ct, batch, nparts * pe), Io::out(out, batch, nparts * (pe - levels * dev->n))};
+    }
+    void run(const Ptrs<2> &d, size_t n, hipStream_t s) const { switch_down_to_ntt(*dev, levels, d[0], d[1], n * nparts, s); }
+};
+fhe_status fhe_bfv_switch_to_level(const fhe_ctx *ctx, size_t levels, size_t nparts, const uint64_t *ct, uint64_t *out,
+                                   size_t batch) {
+    return host_call<SwitchToLevel>(ctx, levels, nparts, ct, out, batch);
 }
 fhe_status fhe_bfv_switch_to_level_dev(const fhe_ctx *ctx, size_t levels, size_t nparts, const uint64_t *ct,
                                        uint64_t *out, size_t batch, void *stream) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        (void)pe;
-        check_levels(c, levels);
-        if (batch && nparts) {
-            need(ct, "ct");
-            need(out, "out");
-        }
-        switch_down_to_ntt(c, levels, ct, out, batch * nparts, as_stream(stream));
-    });
-}
-fhe_status fhe_bfv_switch_to_level(const fhe_ctx *ctx, size_t levels, size_t nparts, const uint64_t *ct, uint64_t *out,
-                                   size_t batch) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        check_levels(c, levels);
-        if (batch && nparts) {
-            need(ct, "ct");
-            need(out, "out");
-        }
-        const size_t po = pe - levels * c.n;
-        HostIO io;
-        u64 *di = io.in(ct, batch * nparts * pe), *dout = io.out(batch * nparts * po);
-        switch_down_to_ntt(c, levels, di, dout, batch * nparts, nullptr);
-        io.back(out, dout, batch * nparts * po);
-    });
+    return dev_call<SwitchToLevel>(stream, ctx, levels, nparts, ct, out, batch);
 }
 
 // ------------------------------------------------------ PIR / RGSW / inner sum ----
-fhe_status fhe_bfv_dot_product_scalar_dev(const fhe_ctx *ctx, size_t nparts, size_t count, const uint64_t *cts,
-                                          int cts_shared, const uint64_t *pts, int pts_shared, uint64_t *out,
-                                          size_t batch, void *stream) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        (void)pe;
-        if (batch && nparts && count) {
-            need(cts, "cts");
-            need(pts, "pts");
-            need(out, "out");
-        }
-        dot_product_scalar(c, nparts, count, cts, cts_shared != 0, pts, pts_shared != 0, out, batch, as_stream(stream));
-    });
-}
-fhe_status fhe_bfv_dot_product_scalar(const fhe_ctx *ctx, size_t nparts, size_t count, const uint64_t *cts,
-                                      int cts_shared, const uint64_t *pts, int pts_shared, uint64_t *out,
-                                      size_t batch) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
+struct DotProduct : Paired {   // bfv::dot_product_scalar; a shared operand is one item for the whole batch
+    size_t nparts, count;
+    bool cts_shared, pts_shared;
+    std::array<Io, 3> io;
+    DotProduct(const fhe_ctx *ctx, size_t nparts, size_t count, const uint64_t *cts, int cts_shared, const uint64_t *pts,
+               int pts_shared, uint64_t *out, size_t batch)
+        : nparts(nparts), count(count), cts_shared(cts_shared != 0), pts_shared(pts_shared != 0) {
+        need(ctx, "ctx");
+        on(*ctx->c, batch);
         if (count == 0) throw StatusError(FHE_E_EMPTY_DOT_PRODUCT, "EmptyDotProduct: no operands");
         if (batch && nparts) {
             need(cts, "cts");
             need(pts, "pts");
             need(out, "out");
         }
-        HostIO io;
-        u64 *dc = io.in(cts, (cts_shared ? 1 : batch) * count * nparts * pe);
-        u64 *dp = io.in(pts, (pts_shared ? 1 : batch) * count * pe);
-        u64 *dout = io.out(batch * nparts * pe);
-        dot_product_scalar(c, nparts, count, dc, cts_shared != 0, dp, pts_shared != 0, dout, batch, nullptr);
-        io.back(out, dout, batch * nparts * pe);
-    });
+        const size_t pe = dev->L * dev->n;
+        io = {Io::in(cts, this->cts_shared ? 1 : batch, count * nparts * pe),
+              Io::in(pts, this->pts_shared ? 1 : batch, count * pe), Io::out(out, batch, nparts * pe)};
+    }
+    void run(const Ptrs<3> &d, size_t n, hipStream_t s) const {
+        dot_product_scalar(*dev, nparts, count, d[0], cts_shared, d[1], pts_shared, d[2], n, s);
+    }
+};
+fhe_status fhe_bfv_dot_product_scalar(const fhe_ctx *ctx, size_t nparts, size_t count, const uint64_t *cts,
+                                      int cts_shared, const uint64_t *pts, int pts_shared, uint64_t *out,
+                                      size_t batch) {
+    return host_call<DotProduct>(ctx, nparts, count, cts, cts_shared, pts, pts_shared, out, batch);
+}
+fhe_status fhe_bfv_dot_product_scalar_dev(const fhe_ctx *ctx, size_t nparts, size_t count, const uint64_t *cts,
+                                          int cts_shared, const uint64_t *pts, int pts_shared, uint64_t *out,
+                                          size_t batch, void *stream) {
+    return dev_call<DotProduct>(stream, ctx, nparts, count, cts, cts_shared, pts, pts_shared, out, batch);
+}
+struct MulPlain : Paired {   // `Ciphertext * Plaintext`
+    size_t nparts;
+    bool pt_shared;
+    std::array<Io, 3> io;
+    MulPlain(const fhe_ctx *ctx, size_t nparts, const uint64_t *ct, const uint64_t *pt, int pt_shared, uint64_t *out,
+             size_t batch)
+        : nparts(nparts), pt_shared(pt_shared != 0) {
+        need(ctx, "ctx");
+        on(*ctx->c, batch);
+        if (batch && nparts) {
+            need(ct, "ct");
+            need(pt, "pt");
+            need(out, "out");
+        }
+        const size_t pe = dev->L * dev->n;
+        io = {Io::in(ct, batch, nparts * pe), Io::in(pt, this->pt_shared ? 1 : batch, pe), Io::out(out, batch, nparts * pe)};
+    }
+    void run(const Ptrs<3> &d, size_t n, hipStream_t s) const { mul_plain(*dev, nparts, d[0], d[1], pt_shared, d[2], n, s); }
+};
+fhe_status fhe_bfv_mul_plain(const fhe_ctx *ctx, size_t nparts, const uint64_t *ct, const uint64_t *pt, int pt_shared,
+                             uint64_t *out, size_t batch) {
+    return host_call<MulPlain>(ctx, nparts, ct, pt, pt_shared, out, batch);
 }
 fhe_status fhe_bfv_mul_plain_dev(const fhe_ctx *ctx, size_t nparts, const uint64_t *ct, const uint64_t *pt,
                                  int pt_shared, uint64_t *out, size_t batch, void *stream) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        (void)pe;
-        if (batch && nparts) {
-            need(ct, "ct");
-            need(pt, "pt");
-            need(out, "out");
-        }
-        mul_plain(c, nparts, ct, pt, pt_shared != 0, out, batch, as_stream(stream));
-    });
+    return dev_call<MulPlain>(stream, ctx, nparts, ct, pt, pt_shared, out, batch);
 }
-fhe_status fhe_bfv_mul_plain(const fhe_ctx *ctx, size_t nparts, const uint64_t *ct, const uint64_t *pt, int pt_shared,
-                             uint64_t *out, size_t batch) {
-    return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        if (batch && nparts) {
+struct RgswMul : Paired {   // `&Ciphertext * &RGSWCiphertext`
+    const Ksk *k0, *k1;
+    std::array<Io, 2> io;
+    RgswMul(const fhe_ksk *ksk0, const fhe_ksk *ksk1, const uint64_t *ct, uint64_t *out, size_t batch) {
+        need(ksk0, "ksk0");
+        need(ksk1, "ksk1");
+        k0 = ksk0->k.get(), k1 = ksk1->k.get();
+        on(*k0->ksk_ctx, batch);
+        if (batch) {
             need(ct, "ct");
-            need(pt, "pt");
             need(out, "out");
         }
-        HostIO io;
-        u64 *dc = io.in(ct, batch * nparts * pe), *dp = io.in(pt, (pt_shared ? 1 : batch) * pe);
-        u64 *dout = io.out(batch * nparts * pe);
-        mul_plain(c, nparts, dc, dp, pt_shared != 0, dout, batch, nullptr);
-        io.back(out, dout, batch * nparts * pe);
-    });
+        const size_t pe = k0->ct_ctx->L * k0->ct_ctx->n;
+        io = {Io::in(ct, batch, 2 * pe), Io::out(out, batch, 2 * pe)};
+    }
+    void run(const Ptrs<2> &d, size_t n, hipStream_t s) const { rgsw_mul(*k0, *k1, d[0], d[1], n, s); }
+};
+fhe_status fhe_bfv_rgsw_mul(const fhe_ksk *ksk0, const fhe_ksk *ksk1, const uint64_t *ct, uint64_t *out, size_t batch) {
+    return host_call<RgswMul>(ksk0, ksk1, ct, out, batch);
 }
 fhe_status fhe_bfv_rgsw_mul_dev(const fhe_ksk *ksk0, const fhe_ksk *ksk1, const uint64_t *ct, uint64_t *out,
                                 size_t batch, void *stream) {
-    return guard([&] {
-        need(ksk0, "ksk0");
-        need(ksk1, "ksk1");
-        if (batch) {
-            need(ct, "ct");
-            need(out, "out");
-        }
-        set_device(*ksk0->k->ksk_ctx);
-        rgsw_mul(*ksk0->k, *ksk1->k, ct, out, batch, as_stream(stream));
-    });
+    return dev_call<RgswMul>(stream, ksk0, ksk1, ct, out, batch);
 }
-fhe_status fhe_bfv_rgsw_mul(const fhe_ksk *ksk0, const fhe_ksk *ksk1, const uint64_t *ct, uint64_t *out, size_t batch) {
-    return guard([&] {
-        need(ksk0, "ksk0");
-        need(ksk1, "ksk1");
-        if (batch) {
-            need(ct, "ct");
-            need(out, "out");
-        }
-        const Ksk &k0 = *ksk0->k;
-        set_device(*k0.ksk_ctx);
-        const size_t pe = k0.ct_ctx->L * k0.ct_ctx->n;
-        HostIO io;
-        u64 *di = io.in(ct, batch * 2 * pe), *dout = io.out(batch * 2 * pe);
-        rgsw_mul(k0, *ksk1->k, di, dout, batch, nullptr);
-        io.back(out, dout, batch * 2 * pe);
-    });
-}
-static void inner_sum_args(const fhe_ksk *const *gks, const size_t *exponents, size_t ngk, std::vector<const Ksk *> &v) {
+// The key lists of inner sum and expand: the array, at least one key, every key.
+static std::vector<const Ksk *> key_list(const fhe_ksk *const *gks, size_t ngk, const char *empty) {
     need(gks, "gks");
-    need(exponents, "exponents");
-    if (ngk == 0) throw StatusError(FHE_E_ARG, "inner sum needs at least one Galois key");
+    if (ngk == 0) throw StatusError(FHE_E_ARG, empty);
+    std::vector<const Ksk *> v;
     for (size_t i = 0; i < ngk; i++) {
         need(gks[i], "gks[i]");
         v.push_back(gks[i]->k.get());
     }
+    return v;
+}
+struct InnerSum : Paired {   // EvaluationKey::computes_inner_sum
+    std::vector<const Ksk *> gks;
+    const size_t *exponents;
+    std::array<Io, 2> io;
+    InnerSum(const fhe_ksk *const *gks, const size_t *exponents, size_t ngk, const uint64_t *ct, uint64_t *out,
+             size_t batch)
+        : exponents(exponents) {
+        need(exponents, "exponents");
+        this->gks = key_list(gks, ngk, "inner sum needs at least one Galois key");
+        on(*this->gks[0]->ksk_ctx, batch);
+        if (batch) {
+            need(ct, "ct");
+            need(out, "out");
+        }
+        const size_t pe = this->gks[0]->ct_ctx->L * this->gks[0]->ct_ctx->n;
+        io = {Io::in(ct, batch, 2 * pe), Io::out(out, batch, 2 * pe)};
+    }
+    void run(const Ptrs<2> &d, size_t n, hipStream_t s) const {
+        inner_sum(gks.data(), exponents, gks.size(), d[0], d[1], n, s);
+    }
+};
+fhe_status fhe_bfv_inner_sum(const fhe_ksk *const *gks, const size_t *exponents, size_t ngk, const uint64_t *ct,
+                             uint64_t *out, size_t batch) {
+    return host_call<InnerSum>(gks, exponents, ngk, ct, out, batch);
 }
 fhe_status fhe_bfv_inner_sum_dev(const fhe_ksk *const *gks, const size_t *exponents, size_t ngk, const uint64_t *ct,
                                  uint64_t *out, size_t batch, void *stream) {
-    return guard([&] {
-        std::vector<const Ksk *> v;
-        inner_sum_args(gks, exponents, ngk, v);
-        if (batch) {
-            need(ct, "ct");
-            need(out, "out");
-        }
-        set_device(*v[0]->ksk_ctx);
-        inner_sum(v.data(), exponents, ngk, ct, out, batch, as_stream(stream));
-    });
-}
-fhe_status fhe_bfv_inner_sum(const fhe_ksk *const *gks, const size_t *exponents, size_t ngk, const uint64_t *ct,
-                             uint64_t *out, size_t batch) {
-    return guard([&] {
-        std::vector<const Ksk *> v;
-        inner_sum_args(gks, exponents, ngk, v);
-        if (batch) {
-            need(ct, "ct");
-            need(out, "out");
-        }
-        set_device(*v[0]->ksk_ctx);
-        const size_t pe = v[0]->ct_ctx->L * v[0]->ct_ctx->n;
-        HostIO io;
-        u64 *di = io.in(ct, batch * 2 * pe), *dout = io.out(batch * 2 * pe);
-        inner_sum(v.data(), exponents, ngk, di, dout, batch, nullptr);
-        io.back(out, dout, batch * 2 * pe);
-    });
+    return dev_call<InnerSum>(stream, gks, exponents, ngk, ct, out, batch);
 }
 
-fhe_status fhe_poly_from_seed_dev(const fhe_ctx *ctx, const uint8_t *seeds, uint64_t *out, size_t batch, void *stream) {
-    return guard([&] {
+struct FromSeed : Paired {   // Poly::<Ntt>::random_from_seed: 32-byte seeds, staged in bytes
+    std::array<Io, 2> io;
+    FromSeed(const fhe_ctx *ctx, const uint8_t *seeds, uint64_t *out, size_t batch) {
         need(ctx, "ctx");
+        on(*ctx->c, batch);
         if (batch) {
             need(seeds, "seeds");
             need(out, "out");
         }
-        set_device(*ctx->c);
-        polys_from_seeds(*ctx->c, seeds, out, batch, as_stream(stream));
-    });
-}
+        io = {Io{seeds, batch, 32, Io::IN}, Io::out(out, batch, dev->L * dev->n)};
+    }
+    void run(const Ptrs<2> &d, size_t n, hipStream_t s) const {
+        polys_from_seeds(*dev, reinterpret_cast<const uint8_t *>(d[0]), d[1], n, s);
+    }
+};
 fhe_status fhe_poly_from_seed(const fhe_ctx *ctx, const uint8_t *seeds, uint64_t *out, size_t batch) {
-    return guard([&] {
-        need(ctx, "ctx");
+    return host_call<FromSeed>(ctx, seeds, out, batch);
+}
+fhe_status fhe_poly_from_seed_dev(const fhe_ctx *ctx, const uint8_t *seeds, uint64_t *out, size_t batch, void *stream) {
+    return dev_call<FromSeed>(stream, ctx, seeds, out, batch);
+}
+struct Decrypt : Paired {   // SecretKey::try_decrypt
+    const Scaler *sc;
+    u64 t;
+    size_t nparts;
+    std::array<Io, 3> io;
+    Decrypt(const fhe_scaler *scaler, uint64_t t, const uint64_t *s_ntt, const uint64_t *ct, size_t nparts, uint64_t *out,
+            size_t batch)
+        : t(t), nparts(nparts) {
+        need(scaler, "cipher_plain_scaler");
+        sc = scaler->s.get();
+        on(*sc->from, batch);
+        need(s_ntt, "s_ntt");
         if (batch) {
-            need(seeds, "seeds");
+            need(ct, "ct");
             need(out, "out");
         }
-        const Ctx &c = *ctx->c;
-        c.need_device();
-        set_device(c);
-        const size_t pe = c.L * c.n;
-        HostIO io;
-        u64 *ds = io.out((batch * 32 + 7) / 8), *dout = io.out(batch * pe);
-        if (batch) FHE_HIP_CHECK(hipMemcpy(ds, seeds, batch * 32, hipMemcpyHostToDevice));
-        polys_from_seeds(c, reinterpret_cast<const uint8_t *>(ds), dout, batch, nullptr);
-        io.back(out, dout, batch * pe);
-    });
+        const Ctx &cc = *sc->from;
+        const size_t pe = cc.L * cc.n;
+        // the host form's staged secret key and plaintext are cleared on the device before their blocks are released
+        // (the reference wraps s, c and the result in Zeroizing, F/bfv/keys/secret_key.rs:198-226)
+        io = {Io::in(s_ntt, 1, pe, Io::SECRET), Io::in(ct, batch, nparts * pe), Io::out(out, batch, cc.n, Io::SECRET)};
+    }
+    void run(const Ptrs<3> &d, size_t n, hipStream_t s) const { decrypt(*sc, t, d[0], d[1], nparts, d[2], n, s); }
+};
+fhe_status fhe_bfv_decrypt(const fhe_scaler *sc, uint64_t t, const uint64_t *s_ntt, const uint64_t *ct, size_t nparts,
+                           uint64_t *out, size_t batch) {
+    return host_call<Decrypt>(sc, t, s_ntt, ct, nparts, out, batch);
 }
 fhe_status fhe_bfv_decrypt_dev(const fhe_scaler *sc, uint64_t t, const uint64_t *s_ntt, const uint64_t *ct, size_t nparts,
                                uint64_t *out, size_t batch, void *stream) {
-    return guard([&] {
-        need(sc, "cipher_plain_scaler");
-        need(s_ntt, "s_ntt");
-        if (batch) {
-            need(ct, "ct");
-            need(out, "out");
-        }
-        set_device(*sc->s->from);
-        decrypt(*sc->s, t, s_ntt, ct, nparts, out, batch, as_stream(stream));
-    });
-}
-fhe_status fhe_bfv_decrypt(const fhe_scaler *sc, uint64_t t, const uint64_t *s_ntt, const uint64_t *ct, size_t nparts,
-                           uint64_t *out, size_t batch) {
-    return guard([&] {
-        need(sc, "cipher_plain_scaler");
-        need(s_ntt, "s_ntt");
-        if (batch) {
-            need(ct, "ct");
-            need(out, "out");
-        }
-        const Ctx &cc = *sc->s->from;
-        cc.need_device();
-        set_device(cc);
-        const size_t pe = cc.L * cc.n;
-        HostIO io;
-        // the staged secret key and the plaintext are cleared on the device before their buffers are freed
-        // (the reference wraps s, c and the result in Zeroizing, F/bfv/keys/secret_key.rs:198-226)
-        u64 *ds = io.secret(io.in(s_ntt, pe), pe), *di = io.in(ct, batch * nparts * pe);
-        u64 *dout = io.secret(io.out(batch * cc.n), batch * cc.n);
-        decrypt(*sc->s, t, ds, di, nparts, dout, batch, nullptr);
-        io.back(out, dout, batch * cc.n);
-    });
+    return dev_call<Decrypt>(stream, sc, t, s_ntt, ct, nparts, out, batch);
 }
 
-static const Ctx &expand_args(const fhe_ksk *const *gks, size_t nlevels, std::vector<const Ksk *> &v) {
-    need(gks, "gks");
-    if (nlevels == 0) throw StatusError(FHE_E_ARG, "expansion needs at least one Galois key");
-    for (size_t i = 0; i < nlevels; i++) {
-        need(gks[i], "gks[i]");
-        v.push_back(gks[i]->k.get());
+struct Expand : Paired {   // EvaluationKey::expands: out [size][batch][2][L][N]
+    std::vector<const Ksk *> gks;
+    size_t size;
+    std::array<Io, 2> io;
+    Expand(const fhe_ksk *const *gks, size_t nlevels, const uint64_t *ct, uint64_t *out, size_t size, size_t batch)
+        : size(size) {
+        this->gks = key_list(gks, nlevels, "expansion needs at least one Galois key");
+        on(*this->gks[0]->ksk_ctx, batch);
+        if (batch && size) {
+            need(ct, "ct");
+            need(out, "out");
+        }
+        const Ctx &cc = *this->gks[0]->ct_ctx;
+        const size_t ce = 2 * cc.L * cc.n;
+        const bool ok = size >= 1 && size <= cc.n;  // (the engine reports the error; do not size buffers from it)
+        io = {Io::in(ct, batch, ce), Io::out(out, ok ? size * batch : 0, ce)};
     }
-    return *v[0]->ct_ctx;
+    void run(const Ptrs<2> &d, size_t n, hipStream_t s) const { expand(gks.data(), gks.size(), d[0], d[1], size, n, s); }
+};
+fhe_status fhe_bfv_expand(const fhe_ksk *const *gks, size_t nlevels, const uint64_t *ct, uint64_t *out, size_t size,
+                          size_t batch) {
+    return host_call<Expand>(gks, nlevels, ct, out, size, batch);
 }
 fhe_status fhe_bfv_expand_dev(const fhe_ksk *const *gks, size_t nlevels, const uint64_t *ct, uint64_t *out, size_t size,
                               size_t batch, void *stream) {
-    return guard([&] {
-        std::vector<const Ksk *> v;
-        expand_args(gks, nlevels, v);
-        if (batch && size) {
-            need(ct, "ct");
-            need(out, "out");
-        }
-        set_device(*v[0]->ksk_ctx);
-        expand(v.data(), nlevels, ct, out, size, batch, as_stream(stream));
-    });
-}
-fhe_status fhe_bfv_expand(const fhe_ksk *const *gks, size_t nlevels, const uint64_t *ct, uint64_t *out, size_t size,
-                          size_t batch) {
-    return guard([&] {
-        std::vector<const Ksk *> v;
-        const Ctx &cc = expand_args(gks, nlevels, v);
-        if (batch && size) {
-            need(ct, "ct");
-            need(out, "out");
-        }
-        set_device(*v[0]->ksk_ctx);
-        const size_t ce = 2 * cc.L * cc.n;
-        const bool ok = size >= 1 && size <= cc.n;  // (the engine reports the error; do not size buffers from it)
-        HostIO io;
-        u64 *di = io.in(ct, batch * ce), *dout = io.out(ok ? size * batch * ce : 0);
-        expand(v.data(), nlevels, di, dout, size, batch, nullptr);
-        io.back(out, dout, size * batch * ce);
-    });
+    return dev_call<Expand>(stream, gks, nlevels, ct, out, size, batch);
 }
 
 // ----------------------------------------------------------------------------- mul ----
@@ -1491,80 +1421,65 @@ fhe_status fhe_mul_get_options(const fhe_mul *m, size_t *chunk, size_t *streams)
         if (streams) *streams = m->m->streams.load(std::memory_order_relaxed);
     });
 }
+struct BfvMul : Paired {   // Multiplicator::multiply
+    static constexpr bool sliced = true;
+    const Mul *mm;
+    std::array<Io, 3> io;
+    BfvMul(const fhe_mul *m, const uint64_t *lhs, const uint64_t *rhs, uint64_t *out, size_t batch) {
+        need(m, "mul");
+        mm = m->m.get();
+        on(*mm->base, batch);
+        if (batch) {
+            need(lhs, "lhs");
+            need(rhs, "rhs");
+            need(out, "out");
+        }
+        const size_t ie = 2 * mm->base->L * mm->base->n, oe = mm->out_parts() * mm->out_rows() * mm->base->n;
+        // (lhs == rhs: one upload, and the squaring shortcut of bfv_mul)
+        io = {Io::in(lhs, batch, ie), Io::in(rhs, batch, ie), Io::out(out, batch, oe)};
+    }
+    void run(const Ptrs<3> &d, size_t n, hipStream_t s) const { bfv_mul(*mm, d[0], d[1], d[2], n, s); }
+};
+fhe_status fhe_bfv_mul(const fhe_mul *m, const uint64_t *lhs, const uint64_t *rhs, uint64_t *out, size_t batch) {
+    return host_call<BfvMul>(m, lhs, rhs, out, batch);
+}
 fhe_status fhe_bfv_mul_dev(const fhe_mul *m, const uint64_t *lhs, const uint64_t *rhs, uint64_t *out, size_t batch,
                            void *stream) {
-    return guard([&] {
-        need(m, "mul");
-        if (batch) {
-            need(lhs, "lhs");
-            need(rhs, "rhs");
-            need(out, "out");
-        }
-        set_device(*m->m->base);
-        bfv_mul(*m->m, lhs, rhs, out, batch, as_stream(stream));
-    });
-}
-fhe_status fhe_bfv_mul(const fhe_mul *m, const uint64_t *lhs, const uint64_t *rhs, uint64_t *out, size_t batch) {
-    return guard([&] {
-        need(m, "mul");
-        if (batch) {
-            need(lhs, "lhs");
-            need(rhs, "rhs");
-            need(out, "out");
-        }
-        const Mul &mm = *m->m;
-        mm.base->need_device();
-        set_device(*mm.base);
-        const size_t ie = 2 * mm.base->L * mm.base->n, oe = mm.out_parts() * mm.out_rows() * mm.base->n;
-        // a large batch goes through in slices whose copies and pipeline overlap (host_sliced)
-        if (host_sliced(mm.base->device, batch, {{lhs, ie}, {rhs, ie}}, out, oe,
-                        [&](const std::vector<const u64 *> &d, u64 *o, size_t n, hipStream_t st) {
-                            bfv_mul(mm, d[0], d[1], o, n, st);
-                        }))
-            return;
-        HostIO io;
-        u64 *dl = io.in(lhs, batch * ie), *dr = lhs == rhs ? dl : io.in(rhs, batch * ie), *dout = io.out(batch * oe);
-        bfv_mul(mm, dl, dr, dout, batch, nullptr);   // (lhs == rhs: one upload, and the squaring shortcut of bfv_mul)
-        io.back(out, dout, batch * oe);
-    });
+    return dev_call<BfvMul>(stream, m, lhs, rhs, out, batch);
 }
 
-fhe_status fhe_bfv_tensor_dev(const fhe_mul *m, size_t lhs_parts, size_t rhs_parts, const uint64_t *lhs,
-                              const uint64_t *rhs, uint64_t *out, size_t batch, void *stream) {
-    return guard([&] {
+struct Tensor : Paired {   // `Mul<&Ciphertext> for &Ciphertext` with any number of parts
+    const Mul *mm;
+    size_t lhs_parts, rhs_parts;
+    std::array<Io, 3> io;
+    Tensor(const fhe_mul *m, size_t lhs_parts, size_t rhs_parts, const uint64_t *lhs, const uint64_t *rhs, uint64_t *out,
+           size_t batch)
+        : lhs_parts(lhs_parts), rhs_parts(rhs_parts) {
         need(m, "mul");
-        if (batch) {
-            need(lhs, "lhs");
-            need(rhs, "rhs");
-            need(out, "out");
-        }
-        const Mul &mm = *m->m;
-        mm.base->need_device();
-        set_device(*mm.base);
-        bfv_tensor(mm, lhs_parts, rhs_parts, lhs, rhs, out, batch, as_stream(stream));
-    });
-}
-fhe_status fhe_bfv_tensor(const fhe_mul *m, size_t lhs_parts, size_t rhs_parts, const uint64_t *lhs, const uint64_t *rhs,
-                          uint64_t *out, size_t batch) {
-    return guard([&] {
-        need(m, "mul");
-        if (batch) {
-            need(lhs, "lhs");
-            need(rhs, "rhs");
-            need(out, "out");
-        }
+        mm = m->m.get();
+        on(*mm->base, batch);
         if (lhs_parts < 1 || rhs_parts < 1)
             throw StatusError(FHE_E_MUL_POLY_COUNT, "a ciphertext has at least one part");
-        const Mul &mm = *m->m;
-        mm.base->need_device();
-        set_device(*mm.base);
-        const size_t pe = mm.base->L * mm.base->n, lo = lhs_parts + rhs_parts - 1;
-        HostIO io;
-        u64 *dl = io.in(lhs, batch * lhs_parts * pe), *dr = io.in(rhs, batch * rhs_parts * pe);
-        u64 *dout = io.out(batch * lo * pe);
-        bfv_tensor(mm, lhs_parts, rhs_parts, dl, dr, dout, batch, nullptr);
-        io.back(out, dout, batch * lo * pe);
-    });
+        if (batch) {
+            need(lhs, "lhs");
+            need(rhs, "rhs");
+            need(out, "out");
+        }
+        const size_t pe = mm->base->L * mm->base->n;
+        io = {Io::in(lhs, batch, lhs_parts * pe), Io::in(rhs, batch, rhs_parts * pe),
+              Io::out(out, batch, (lhs_parts + rhs_parts - 1) * pe)};
+    }
+    void run(const Ptrs<3> &d, size_t n, hipStream_t s) const {
+        bfv_tensor(*mm, lhs_parts, rhs_parts, d[0], d[1], d[2], n, s);
+    }
+};
+fhe_status fhe_bfv_tensor(const fhe_mul *m, size_t lhs_parts, size_t rhs_parts, const uint64_t *lhs, const uint64_t *rhs,
+                          uint64_t *out, size_t batch) {
+    return host_call<Tensor>(m, lhs_parts, rhs_parts, lhs, rhs, out, batch);
+}
+fhe_status fhe_bfv_tensor_dev(const fhe_mul *m, size_t lhs_parts, size_t rhs_parts, const uint64_t *lhs,
+                              const uint64_t *rhs, uint64_t *out, size_t batch, void *stream) {
+    return dev_call<Tensor>(stream, m, lhs_parts, rhs_parts, lhs, rhs, out, batch);
 }
 
 // -------------------------------------------------------------------------- params ----
@@ -1703,8 +1618,11 @@ fhe_status fhe_generate_moduli(const size_t *sizes, size_t count, size_t degree,
 fhe_status fhe_synth_uniform_dev(const fhe_ctx *ctx, uint64_t seed, uint64_t ct0, uint64_t part0, size_t nparts,
                                  uint64_t *out, size_t batch, void *stream) {
     return guard([&] {
-        FHE_POLY_IO_PROLOGUE(ctx);
-        const u64 total = (u64)batch * nparts * pe;
+        need(ctx, "ctx");
+        const Ctx &c = *ctx->c;
+        c.need_device();
+        set_device(c);
+        const u64 total = (u64)batch * nparts * c.L * c.n;
         if (!total) return;
         need(out, "out");
         FHE_LAUNCH("synth", k::synth_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0,
