@@ -143,6 +143,11 @@ SIGNATURES = {
     "fhe_params_extender": (i32, [vp, sz, C.POINTER(vp)]),
     "fhe_params_down_scaler": (i32, [vp, sz, C.POINTER(vp)]),
     "fhe_mul_create_default": (i32, [vp, sz, vp, i32, C.POINTER(vp)]),
+    "fhe_encoder_create": (i32, [vp, NTT_TABLES_FN, vp, C.POINTER(vp)]),
+    "fhe_encoder_destroy": (None, [vp]),
+    "fhe_bfv_encode_dev": (i32, [vp, i32, i32, sz, vp, sz, vp, sz, vp]),
+    "fhe_bfv_decode_dev": (i32, [vp, i32, vp, vp, sz, vp]),
+    "fhe_bfv_add_plain_dev": (i32, [vp, i32, sz, vp, vp, i32, vp, sz, vp]),
     "fhe_generate_prime": (u64, [sz, u64, u64]),
     "fhe_supports_opt": (i32, [u64]),
     "fhe_is_prime": (i32, [u64]),

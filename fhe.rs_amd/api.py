@@ -514,6 +514,31 @@ class Context:
         check(L.fhe_bfv_mul_plain(self._h, parts, _ptr(x), _ptr(y), shared, _ptr(out), batch))
         return out
 
+    def _add_plain(self, ct, pt, subtract):
+        L = _lib.lib()
+        parts = ct.shape[-3]
+        batch = self._batch(ct) // parts
+        shared = 1 if len(pt.shape) == 2 and len(ct.shape) > 3 else 0
+        if _is_dev(ct):
+            out = _empty_dev(ct, ct.shape)
+            check(L.fhe_bfv_add_plain_dev(self._h, subtract, parts, _dptr(ct), _dptr(pt), shared, _dptr(out), batch,
+                                          _stream()))
+            return out
+        dev = max(self.device, 0)
+        x, y = DeviceArray.from_numpy(_np(ct), dev), DeviceArray.from_numpy(_np(pt), dev)
+        check(L.fhe_bfv_add_plain_dev(self._h, subtract, parts, _dptr(x), _dptr(y), shared, _dptr(x), batch, _stream()))
+        return x.download()
+
+    def add_plain(self, ct, pt):
+        """`&Ciphertext + &Plaintext` (ops/mod.rs:71-108): ct [..., parts, L, N] Ntt plus pt [..., L, N] (or [L, N]
+        shared by the batch) in its Delta-scaled form (`Encoder.encode(..., scaled=True)`): c0 + pt, other parts
+        unchanged."""
+        return self._add_plain(ct, pt, 0)
+
+    def sub_plain(self, ct, pt):
+        """`&Ciphertext - &Plaintext` (ops/mod.rs:166-203): c0 - pt, other parts unchanged."""
+        return self._add_plain(ct, pt, 1)
+
     def random_from_seed(self, seeds):
         """Poly::<Ntt>::random_from_seed (rq/mod.rs:276-292) per 32-byte seed: seeds [batch, 32] uint8 ->
         [batch, L, N]; numpy in -> numpy out, torch CUDA uint8 tensor in -> CUDA tensor out.
@@ -840,6 +865,88 @@ class RGSWCiphertext:
         return out
 
 
+_ENCODINGS = {"poly": 0, "simd": 1}
+
+
+def _encoding(name):
+    if name not in _ENCODINGS:
+        raise FheError(-1, f"unknown encoding {name!r} (poly / simd)")
+    return _ENCODINGS[name]
+
+
+def _tables_cb(tables_fn):
+    """fhe_ntt_tables_fn around a Python tables_fn(modulus, degree) -> dict (see BfvParameters)."""
+    def _cb(_user, modulus, deg, om, oms, zi, zis, si, sis):
+        try:
+            t = tables_fn(int(modulus), int(deg))
+            arrs = [_np(t[key]).reshape(-1) for key in ("omegas", "omegas_shoup", "zetas_inv", "zetas_inv_shoup")]
+            if any(a.size != deg for a in arrs):
+                return 1   # a short table would be read out of bounds: creation fails (NttOperatorUnavailable)
+            for dst, a in zip((om, oms, zi, zis), arrs):
+                C.memmove(dst, a.ctypes.data, 8 * deg)
+            si[0], sis[0] = int(t["size_inv"]), int(t["size_inv_shoup"])
+            return 0
+        except Exception:
+            return 1
+    return _lib.NTT_TABLES_FN(_cb)
+
+
+class Encoder:
+    """The encoding tables of bfv::BfvParameters (parameters.rs:598, 607-633, 711-725) on the device: made by
+    `BfvParameters.encoder()`.  numpy in -> numpy out (staged through `DeviceArray`s on the ABI's allocator); a device
+    array in -> a device array out, on the current stream."""
+
+    def __init__(self, params, tables_fn=None):
+        self._params = params   # (the C handle borrows the parameter set's contexts)
+        self.degree, self.plaintext = params.degree, params.plaintext
+        h = C.c_void_p()
+        cb = _tables_cb(tables_fn) if tables_fn is not None else _lib.NTT_TABLES_FN()
+        check(_lib.lib().fhe_encoder_create(params._h, cb, None, C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        if getattr(self, "_h", None) is not None and _lib._lib is not None:
+            _lib._lib.fhe_encoder_destroy(self._h)
+
+    def encode(self, values, encoding="simd", level=0, scaled=False):
+        """PlaintextVec::try_encode (plaintext_vec.rs:70-102): values [..., nvalues] (nvalues <= N) -> the
+        plaintexts' poly_ntt [..., L_level, N]; scaled=True gives Plaintext::to_poly (plaintext.rs:172-196), the
+        operand of Context.add_plain / sub_plain.  Values are reduced mod t."""
+        L = _lib.lib()
+        enc = _encoding(encoding)
+        nmod = len(self._params.moduli) - level if 0 <= level < len(self._params.moduli) else 1
+        lead, nvalues = tuple(values.shape[:-1]), int(values.shape[-1])
+        batch = int(np.prod(lead)) if lead else 1
+        oshape = lead + (nmod, self.degree)
+        if _is_dev(values):
+            out = _empty_dev(values, oshape)
+            check(L.fhe_bfv_encode_dev(self._h, enc, 1 if scaled else 0, level, _dptr(values), nvalues, _dptr(out), batch,
+                                       _stream()))
+            return out
+        x = DeviceArray.from_numpy(_np(values), max(self._params.device, 0))
+        out = DeviceArray(oshape, x.device)
+        check(L.fhe_bfv_encode_dev(self._h, enc, 1 if scaled else 0, level, _dptr(x), nvalues, _dptr(out), batch,
+                                   _stream()))
+        return out.download()
+
+    def decode(self, coeffs, encoding="simd"):
+        """Vec<u64>::try_decode (plaintext.rs:157-170, 408-431): coefficients mod t [..., N] (what decrypt returns)
+        -> values [..., N]."""
+        L = _lib.lib()
+        enc = _encoding(encoding)
+        if int(coeffs.shape[-1]) != self.degree:
+            raise FheError(-1, "coefficients: the last dimension must be the degree")
+        batch = int(np.prod(coeffs.shape[:-1])) if len(coeffs.shape) > 1 else 1
+        if _is_dev(coeffs):
+            out = _empty_dev(coeffs, tuple(coeffs.shape))
+            check(L.fhe_bfv_decode_dev(self._h, enc, _dptr(coeffs), _dptr(out), batch, _stream()))
+            return out
+        x = DeviceArray.from_numpy(_np(coeffs), max(self._params.device, 0))
+        out = DeviceArray(x.shape, x.device)
+        check(L.fhe_bfv_decode_dev(self._h, enc, _dptr(x), _dptr(out), batch, _stream()))
+        return out.download()
+
+
 class BfvParameters:
     """The device-table part of bfv::BfvParameters (crates/fhe/src/bfv/parameters.rs:560-738):
     per-level contexts, the extended multiplication basis and per-level mul parameters."""
@@ -859,19 +966,7 @@ class BfvParameters:
         if tables_fn is None:
             check(L.fhe_params_create(device, degree, len(m), _ptr(m), plaintext_modulus, C.byref(h)))
         else:
-            def _cb(_user, modulus, deg, om, oms, zi, zis, si, sis):
-                try:
-                    t = tables_fn(int(modulus), int(deg))
-                    arrs = [_np(t[key]).reshape(-1) for key in ("omegas", "omegas_shoup", "zetas_inv", "zetas_inv_shoup")]
-                    if any(a.size != deg for a in arrs):
-                        return 1   # a short table would be read out of bounds: creation fails (NttOperatorUnavailable)
-                    for dst, a in zip((om, oms, zi, zis), arrs):
-                        C.memmove(dst, a.ctypes.data, 8 * deg)
-                    si[0], sis[0] = int(t["size_inv"]), int(t["size_inv_shoup"])
-                    return 0
-                except Exception:
-                    return 1
-            cb = _lib.NTT_TABLES_FN(_cb)
+            cb = _tables_cb(tables_fn)
             check(L.fhe_params_create_with_tables(device, degree, len(m), _ptr(m), plaintext_modulus, cb, None,
                                                   C.byref(h)))
             # (the C side calls `cb` only while fhe_params_create_with_tables runs and caches every table per modulus:
@@ -902,6 +997,11 @@ class BfvParameters:
     def down_scaler(self, level):
         return Scaler(self.mul_context_at_level(level), self.context_at_level(level),
                       _handle=self._get("fhe_params_down_scaler", level), _owner=self)
+
+    def encoder(self, tables_fn=None):
+        """The parameter set's `Encoder` (fhe_encoder_create).  tables_fn(t, degree) -> the host's NttOperator tables
+        for t (same dict as the constructor's); None: the engine's own psi."""
+        return Encoder(self, tables_fn)
 
     def plaintext_context(self):
         """parameters.rs:578-595: the shortest prefix of the moduli with >= bits(t) + 60 bits."""

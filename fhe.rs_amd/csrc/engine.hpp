@@ -25,7 +25,8 @@ enum : int {
     E_CONTEXT_MISMATCH = -6, E_DEGREE_MISMATCH = -7, E_NO_MORE_CONTEXT = -8, E_CONTEXT_NOT_REACHABLE = -9,
     E_INVALID_SUBST = -10, E_PARAMETER_MISMATCH = -11, E_INVALID_LEVEL = -12, E_MUL_POLY_COUNT = -13,
     E_EMPTY_MODULI = -14, E_NON_COPRIME = -15, E_NOT_ENOUGH_PRIMES = -16, E_KEYSWITCH_UNSUPPORTED = -17,
-    E_NO_DEVICE = -18, E_EMPTY_DOT = -19, E_EXPANSION_SIZE = -20, E_EXPANSION_UNSUPPORTED = -21
+    E_NO_DEVICE = -18, E_EMPTY_DOT = -19, E_EXPANSION_SIZE = -20, E_EXPANSION_UNSUPPORTED = -21,
+    E_SIMD_UNAVAILABLE = -22, E_TOO_MANY_VALUES = -23
 };
 
 #define FHE_HIP_CHECK(expr)                                                                        \
@@ -2720,6 +2721,227 @@ inline void bfv_mul(const Mul &m, const u64 *lhs, const u64 *rhs, u64 *out, size
         }
         if (m.mod_switch) bfv_switch_down(b, parts, pre.u(), out + b0 * parts * (PL - N), nb, s);
     }
+}
+
+// ------------------------------------------------------------------- plaintext encoding ----
+// The encoding half of bfv::BfvParameters (F/bfv/parameters.rs:598, 607-633, 711-725) on one device: t's NTT operator
+// as a one-modulus context (the same tables, DevMod and F64 twins as any modulus), SEAL's index map and its inverse,
+// and per level q_mod_t and delta.
+struct Encoder {
+    const Ctx *top = nullptr;         // the parameter set's level-0 context (the encoder borrows it)
+    size_t n = 0, logn = 0;
+    u64 t = 0;
+    DevMod tm{};                      // t's constants (by value: the Poly path has no transform mod t)
+    std::unique_ptr<Ctx> tctx;        // null when t admits no degree-N NTT: SIMD unavailable
+    DevBuf<uint32_t> d_map, d_inv_map;
+    std::vector<u64> q_mod_t;         // per level (parameters.rs:616-633)
+    std::vector<std::unique_ptr<DevBuf<k::u64x2>>> d_delta;   // per level [L] {delta_i, shoup}, delta_i = (-t)^-1 mod q_i
+};
+
+// matrix_reps_index_map (parameters.rs:711-725): generator 3, m = 2N, bit-reversed positions
+inline std::vector<uint32_t> simd_index_map(size_t n, size_t logn) {
+    std::vector<uint32_t> map(n);
+    const u64 m = 2 * (u64)n;
+    u64 pos = 1;
+    for (size_t i = 0; i < n / 2; i++) {
+        map[i] = k::bitrev_n((uint32_t)((pos - 1) >> 1), (uint32_t)logn);
+        map[n / 2 + i] = k::bitrev_n((uint32_t)((m - pos - 1) >> 1), (uint32_t)logn);
+        pos = (pos * 3) & (m - 1);
+    }
+    return map;
+}
+
+// `tctx`: the context over {t} (null when t admits no degree-N NTT).
+inline std::unique_ptr<Encoder> encoder_create(const Ctx &top, u64 t, std::unique_ptr<Ctx> tctx) {
+    top.need_device();
+    auto e = std::make_unique<Encoder>();
+    e->top = &top;
+    e->n = top.n;
+    e->logn = top.logn;
+    e->t = t;
+    const ModConsts tmc = make_mod_consts(t);
+    static_assert(sizeof(DevMod) == sizeof(ModConsts), "DevMod layout");
+    std::memcpy(&e->tm, &tmc, sizeof(DevMod));
+    e->tctx = std::move(tctx);
+    if (e->tctx) {
+        const std::vector<uint32_t> map = simd_index_map(e->n, e->logn);
+        std::vector<uint32_t> inv(e->n);
+        for (size_t i = 0; i < e->n; i++) inv[map[i]] = (uint32_t)i;
+        e->d_map.upload(map);
+        e->d_inv_map.upload(inv);
+    }
+    for (const Ctx *c = &top; c; c = c->next.get()) {
+        u64 qt = 1 % t;
+        std::vector<k::u64x2> d(c->L);
+        for (size_t i = 0; i < c->L; i++) {
+            const u64 q = c->moduli[i];
+            qt = mulmod(qt, q % t, t);
+            const u64 neg_t = (q - t % q) % q;
+            require(neg_t != 0, E_INVALID_MODULUS, "the plaintext modulus must be invertible modulo every q_i");
+            const u64 inv = powmod(neg_t, q - 2, q);
+            d[i] = k::u64x2{inv, shoup(inv, q)};
+        }
+        e->q_mod_t.push_back(qt);
+        e->d_delta.push_back(std::make_unique<DevBuf<k::u64x2>>());
+        e->d_delta.back()->upload(d);
+    }
+    return e;
+}
+
+// {w, shoup(w)} or, for the F64 instances, the double pair {w, w / p} (Ctx's F64 tables)
+inline k::u64x2 scale_pair(u64 w, u64 p, bool f64) {
+    if (!f64) return k::u64x2{w, shoup(w, p)};
+    const double d = (double)w, q = d / (double)p;
+    k::u64x2 r;
+    std::memcpy(&r.x, &d, 8);
+    std::memcpy(&r.y, &q, 8);
+    return r;
+}
+
+// The whole-row (N <= 16384) instances of the encoding kernels: integer (NARROW: every modulus below 2^60) or F64 class hr.
+#define FHE_ENC_LAUNCH(KERNEL, LM, NRW, HR, name, grid, s, ...)                                                        \
+    do {                                                                                                           \
+        const size_t _lds = k::lds_words(1u << (LM)) * sizeof(u64);                                                \
+        allow_big_lds((k::KERNEL<LM, NRW, HR>), _lds);                                                             \
+        FHE_LAUNCH(name, (k::KERNEL<LM, NRW, HR>), dim3(grid), dim3(k::ntt_threads_c(LM)), _lds, s, __VA_ARGS__);  \
+    } while (0)
+#define FHE_ENC_CASE_INT(KERNEL, LM, narrow, name, grid, s, ...)                                                       \
+    case LM:                                                                                                       \
+        if (narrow) FHE_ENC_LAUNCH(KERNEL, LM, true, 0, name, grid, s, __VA_ARGS__);                               \
+        else FHE_ENC_LAUNCH(KERNEL, LM, false, 0, name, grid, s, __VA_ARGS__);                                     \
+        break;
+#define FHE_ENC_CASE_F64(KERNEL, LM, narrow, hr, name, grid, s, ...)                                                   \
+    case LM:                                                                                                       \
+        if (hr == 3) FHE_ENC_LAUNCH(KERNEL, LM, false, 3, name, grid, s, __VA_ARGS__);                             \
+        else if (hr == 4) FHE_ENC_LAUNCH(KERNEL, LM, false, 4, name, grid, s, __VA_ARGS__);                        \
+        else if (hr == 5) FHE_ENC_LAUNCH(KERNEL, LM, false, 5, name, grid, s, __VA_ARGS__);                        \
+        else if (narrow) FHE_ENC_LAUNCH(KERNEL, LM, true, 0, name, grid, s, __VA_ARGS__);                          \
+        else FHE_ENC_LAUNCH(KERNEL, LM, false, 0, name, grid, s, __VA_ARGS__);                                     \
+        break;
+#define FHE_ENC_SWITCH(KERNEL, logn, narrow, hr, name, grid, s, ...)                                                   \
+    switch (logn) {                                                                                                \
+        FHE_ENC_CASE_INT(KERNEL, 3, narrow, name, grid, s, __VA_ARGS__)                                            \
+        FHE_ENC_CASE_INT(KERNEL, 4, narrow, name, grid, s, __VA_ARGS__)                                            \
+        FHE_ENC_CASE_INT(KERNEL, 5, narrow, name, grid, s, __VA_ARGS__)                                            \
+        FHE_ENC_CASE_INT(KERNEL, 6, narrow, name, grid, s, __VA_ARGS__)                                            \
+        FHE_ENC_CASE_INT(KERNEL, 7, narrow, name, grid, s, __VA_ARGS__)                                            \
+        FHE_ENC_CASE_INT(KERNEL, 8, narrow, name, grid, s, __VA_ARGS__)                                            \
+        FHE_ENC_CASE_INT(KERNEL, 9, narrow, name, grid, s, __VA_ARGS__)                                            \
+        FHE_ENC_CASE_INT(KERNEL, 10, narrow, name, grid, s, __VA_ARGS__)                                           \
+        FHE_ENC_CASE_INT(KERNEL, 11, narrow, name, grid, s, __VA_ARGS__)                                           \
+        FHE_ENC_CASE_F64(KERNEL, 12, narrow, hr, name, grid, s, __VA_ARGS__)                                       \
+        FHE_ENC_CASE_F64(KERNEL, 13, narrow, hr, name, grid, s, __VA_ARGS__)                                       \
+        FHE_ENC_CASE_F64(KERNEL, 14, narrow, hr, name, grid, s, __VA_ARGS__)                                       \
+        default: throw StatusError(E_ARG, "unsupported encoding tile size");                                       \
+    }
+
+// the F64 class of the encoding kernels' rows (whole rows of 4096 ... 16384 points only, as launch_ntt_f64)
+inline int f64_rows(const Ctx &c, size_t first, size_t rows, bool f64_on) {
+    return f64_on && c.logn >= 12 && c.logn <= 14 ? c.f64_class(first, rows) : 0;
+}
+
+inline bool all_below_2p60(const Ctx &c) {
+    for (size_t i = 0; i < c.L; i++)
+        if (c.moduli[i] >> 60) return false;
+    return true;
+}
+
+// PlaintextVec::try_encode (F/bfv/plaintext_vec.rs:70-102) -> Plaintext::poly_ntt, or with `scaled` Plaintext::to_poly
+// (F/bfv/plaintext.rs:172-196): values [batch][nvalues] -> out [batch][L_level][N] Ntt.
+inline void encode(const Encoder &e, bool simd, bool scaled, size_t level, const u64 *values, size_t nvalues, u64 *out,
+                   size_t batch, hipStream_t s) {
+    const Ctx *qc = e.top->at_level(level);
+    if (!qc) throw StatusError(E_INVALID_LEVEL, "InvalidLevel");
+    if (simd && !e.tctx) throw StatusError(E_SIMD_UNAVAILABLE, "SimdUnavailable: the plaintext modulus admits no degree-N NTT");
+    if (nvalues > e.n) throw StatusError(E_TOO_MANY_VALUES, "TooManyValues: more values than the degree");
+    if (!batch) return;
+    require(batch * qc->L <= 0x7fffffffu, E_ARG, "encode: batch exceeds the grid limit");
+    const bool f64_on = !f64_disabled();   // (read once per call: every transform of the call takes the same kind)
+    const u64 qmt = e.q_mod_t[level];
+    k::LiftSrc ls{values, nvalues, nvalues, e.tm, k::u64x2{qmt, shoup(qmt, e.t)}, scaled ? 1u : 0u,
+                  scaled ? e.d_delta[level]->p : nullptr};
+    // the mod-t rows of a SIMD encoding are plaintext coefficients: cleared before the block returns to the pool
+    // (the reference zeroizes them, plaintext.rs:104, 178)
+    std::unique_ptr<WsGuard> trows;
+    if (simd) {
+        trows = std::make_unique<WsGuard>(batch * e.n * sizeof(u64), s, true);
+        const Ctx &tc = *e.tctx;
+        if (e.logn <= 14) {
+            // the inverse transform's N^-1 times q_mod_t for the scaled form (the same value mod t as multiplying after)
+            const int hr = f64_rows(tc, 0, 1, f64_on);
+            const NttTables &tt = tc.tab(0);
+            const u64 c = scaled ? mulmod(tt.size_inv, qmt, e.t) : tt.size_inv;
+            const u64 zc = mulmod(tt.zetas_inv[e.n - 2], c, e.t);
+            const k::u64x2 ns = scale_pair(c, e.t, hr > 0), zs = scale_pair(zc, e.t, hr > 0);
+            const k::u64x2 *itw = hr > 0 ? tc.ditw_f() : tc.ditw();
+            FHE_ENC_SWITCH(encode_simd_t_kernel, e.logn, (e.t >> 60) == 0, hr, "encode_simd_t", batch, s, values,
+                           (u64)nvalues, e.d_inv_map.p, trows->u(), tc.dmods(), itw, ns, zs);
+            ls.mul_t = 0;
+        } else {   // rows larger than one LDS tile: the gather as a pass of its own, then launch_ntt
+            const u64 total = (u64)batch * e.n;
+            FHE_LAUNCH("encode_gather", k::perm_reduce_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
+                       values, (u64)nvalues, (u64)nvalues, e.d_inv_map.p, trows->u(), e.tm, (uint32_t)e.logn, total);
+            launch_ntt(tc, true, trows->u(), trows->u(), full_map(tc, 1), batch, s);
+        }
+        ls.src = trows->u();
+        ls.stride = ls.nvalues = e.n;
+    }
+    if (qc->logn <= 14) {
+        const int hr = f64_rows(*qc, 0, qc->L, f64_on);
+        const k::u64x2 *tw = hr > 0 ? qc->dtw_f() : qc->dtw();
+        FHE_ENC_SWITCH(encode_lift_kernel, qc->logn, all_below_2p60(*qc), hr, "encode_lift", batch * qc->L, s, ls, out,
+                       (uint32_t)qc->L, qc->dmods(), tw);
+    } else {
+        const u64 total = (u64)batch * qc->L * e.n;
+        FHE_LAUNCH("encode_lift", k::encode_lift_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
+                   ls, out, (uint32_t)qc->L, qc->dmods(), (uint32_t)e.logn, total);
+        launch_ntt(*qc, false, out, out, full_map(*qc, qc->L), batch, s);
+    }
+}
+
+// Vec<u64>::try_decode (F/bfv/plaintext.rs:157-170, 408-431): coefficients mod t [batch][N] -> values [batch][N].
+inline void decode(const Encoder &e, bool simd, const u64 *coeffs, u64 *out, size_t batch, hipStream_t s) {
+    if (simd && !e.tctx) throw StatusError(E_SIMD_UNAVAILABLE, "SimdUnavailable: the plaintext modulus admits no degree-N NTT");
+    if (!batch) return;
+    require(batch <= 0x7fffffffu, E_ARG, "decode: batch exceeds the grid limit");
+    const u64 total = (u64)batch * e.n;
+    if (!simd) {
+        FHE_LAUNCH("decode_poly", k::perm_reduce_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
+                   coeffs, (u64)e.n, (u64)e.n, (const uint32_t *)nullptr, out, e.tm, (uint32_t)e.logn, total);
+        return;
+    }
+    const Ctx &tc = *e.tctx;
+    if (e.logn <= 14) {
+        const int hr = f64_rows(tc, 0, 1, !f64_disabled());
+        FHE_ENC_SWITCH(decode_simd_kernel, e.logn, (e.t >> 60) == 0, hr, "decode_simd", batch, s, coeffs, e.d_map.p, out,
+                       tc.dmods(), hr > 0 ? tc.dtw_f() : tc.dtw());
+        return;
+    }
+    // rows larger than one LDS tile: reduce, launch_ntt, then the index map as a gather pass
+    WsGuard tmp(total * sizeof(u64), s, true);
+    FHE_LAUNCH("decode_reduce", k::perm_reduce_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s, coeffs,
+               (u64)e.n, (u64)e.n, (const uint32_t *)nullptr, tmp.u(), e.tm, (uint32_t)e.logn, total);
+    launch_ntt(tc, false, tmp.u(), tmp.u(), full_map(tc, 1), batch, s);
+    FHE_LAUNCH("decode_gather", k::perm_reduce_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
+               (const u64 *)tmp.u(), (u64)e.n, (u64)e.n, (const uint32_t *)e.d_map.p, out, e.tm, (uint32_t)e.logn, total);
+}
+#undef FHE_ENC_SWITCH
+#undef FHE_ENC_CASE_F64
+#undef FHE_ENC_CASE_INT
+#undef FHE_ENC_LAUNCH
+
+// `&Ciphertext + &Plaintext` / `-` (F/bfv/ops/mod.rs:71-108, 166-203): c0 +- to_poly(pt), the other parts unchanged.
+// ct, out [batch][nparts][L][N]; pt [batch][L][N] Delta-scaled (pt_shared: [L][N]); out == ct allowed.
+inline void add_plain(const Ctx &c, bool subtract, size_t nparts, const u64 *ct, const u64 *pt, bool pt_shared, u64 *out,
+                      size_t batch, hipStream_t s) {
+    c.need_device();
+    require(nparts >= 1, E_ARG, "a ciphertext has at least one part");
+    if (!batch) return;
+    require(batch <= 65535, E_ARG, "add_plain: batch exceeds the grid limit");
+    const u64 pl = (u64)c.L * c.n;
+    FHE_LAUNCH("add_plain", k::add_plain_kernel, dim3(blocks_for(pl, EW_THREADS), (unsigned)batch), dim3(EW_THREADS), 0, s,
+               ct, pt, pt_shared ? (u64)0 : pl, out, c.dmods(), (uint32_t)nparts, (uint32_t)c.logn, pl,
+               subtract ? 1u : 0u, out != ct ? 1u : 0u);
 }
 
 }  // namespace fhe

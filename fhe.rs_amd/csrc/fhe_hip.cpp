@@ -51,6 +51,9 @@ struct fhe_params {
     std::vector<std::unique_ptr<fhe_scaler>> extender;  // per level
     std::vector<std::unique_ptr<fhe_scaler>> down;      // per level
 };
+struct fhe_encoder {
+    std::unique_ptr<Encoder> e;
+};
 
 namespace {
 thread_local std::string g_last_error;
@@ -1595,6 +1598,70 @@ fhe_status fhe_mul_create_default(const fhe_params *p, size_t level, const fhe_k
         }
         h->m = make_mul(ext, ext, down, rk_or_null ? rk_or_null->k.get() : nullptr, mod_switch != 0);
         *out = h.release();
+    });
+}
+
+// ------------------------------------------------------------------ plaintext encoding ----
+// Device-pointer forms only (like fhe_synth_uniform_dev): a host without PyTorch stages through fhe_buf_*.
+fhe_status fhe_encoder_create(const fhe_params *par, fhe_ntt_tables_fn tables, void *user, fhe_encoder **out) {
+    return guard([&] {
+        need(par, "params");
+        need(out, "out");
+        *out = nullptr;
+        const Ctx &top = *par->top->c;
+        top.need_device();
+        set_device(top);
+        // NttOperator::new(t, N) exists iff t supports it (parameters.rs:71-75, 598); otherwise SIMD is unavailable
+        std::unique_ptr<Ctx> tctx;
+        if (supports_ntt(par->plaintext, par->degree)) {
+            std::map<u64, HostTables> cache;
+            tctx = ctx_create_cb(par->device, par->degree, {par->plaintext}, tables, user, tables != nullptr, cache);
+        }
+        auto h = std::make_unique<fhe_encoder>();
+        h->e = encoder_create(top, par->plaintext, std::move(tctx));
+        *out = h.release();
+    });
+}
+void fhe_encoder_destroy(fhe_encoder *enc) { delete enc; }
+fhe_status fhe_bfv_encode_dev(const fhe_encoder *enc, int encoding, int scaled, size_t level, const uint64_t *values,
+                              size_t nvalues, uint64_t *out, size_t batch, void *stream) {
+    return guard([&] {
+        need(enc, "encoder");
+        require(encoding == FHE_ENCODING_POLY || encoding == FHE_ENCODING_SIMD, E_ARG, "unknown encoding");
+        if (batch) {
+            if (nvalues) need(values, "values");
+            need(out, "out");
+        }
+        set_device(*enc->e->top);
+        encode(*enc->e, encoding == FHE_ENCODING_SIMD, scaled != 0, level, values, nvalues, out, batch, as_stream(stream));
+    });
+}
+fhe_status fhe_bfv_decode_dev(const fhe_encoder *enc, int encoding, const uint64_t *coeffs, uint64_t *out, size_t batch,
+                              void *stream) {
+    return guard([&] {
+        need(enc, "encoder");
+        require(encoding == FHE_ENCODING_POLY || encoding == FHE_ENCODING_SIMD, E_ARG, "unknown encoding");
+        if (batch) {
+            need(coeffs, "coeffs");
+            need(out, "out");
+        }
+        set_device(*enc->e->top);
+        decode(*enc->e, encoding == FHE_ENCODING_SIMD, coeffs, out, batch, as_stream(stream));
+    });
+}
+fhe_status fhe_bfv_add_plain_dev(const fhe_ctx *ctx, int subtract, size_t nparts, const uint64_t *ct, const uint64_t *pt,
+                                 int pt_shared, uint64_t *out, size_t batch, void *stream) {
+    return guard([&] {
+        need(ctx, "ctx");
+        const Ctx &c = *ctx->c;
+        c.need_device();
+        if (batch) {
+            need(ct, "ct");
+            need(pt, "pt");
+            need(out, "out");
+        }
+        set_device(c);
+        add_plain(c, subtract != 0, nparts, ct, pt, pt_shared != 0, out, batch, as_stream(stream));
     });
 }
 

@@ -23,6 +23,9 @@
 //   phase_kernel, decrypt_tail_kernel   SecretKey::try_decrypt      F/bfv/keys/secret_key.rs:198-247
 //   wire_pack_kernel, wire_unpack_kernel  Rq payload bit packing    M/rq/convert.rs:17-99, fhe-util lib.rs:71-148
 //   synth_kernel            synthetic uniform residues (bench/test inputs)
+//   encode_simd_t_kernel, encode_lift_kernel, decode_simd_kernel   PlaintextVec::try_encode, Plaintext::to_poly, decoders
+//                                                                   F/bfv/plaintext_vec.rs:70-102, plaintext.rs:157-196
+//   add_plain_kernel        ct +- pt                                 F/bfv/ops/mod.rs:71-108, 166-203
 // Compile-time knobs live in knobs.hpp (pinned in the release build); rejected kernel variants in tools/lab/ (lab builds only).
 #pragma once
 #include "kernels_common.hpp"
@@ -31,6 +34,7 @@
 #include "kernels_ks.hpp"
 #include "kernels_scaler.hpp"
 #include "kernels_misc.hpp"
+#include "kernels_encode.hpp"
 
 namespace fhe {
 namespace k {

@@ -56,7 +56,9 @@ enum {
     FHE_E_NO_DEVICE = -18,                    /* compute call on a host-only (device = -1) handle */
     FHE_E_EMPTY_DOT_PRODUCT = -19,            /* Error::EmptyDotProduct / DotProductError::EmptyInput */
     FHE_E_INVALID_EXPANSION_SIZE = -20,       /* EvaluationKeyError::InvalidExpansionSize          */
-    FHE_E_EXPANSION_UNSUPPORTED = -21         /* EvaluationKeyError::Unsupported{Expansion} / Missing{GaloisKey} */
+    FHE_E_EXPANSION_UNSUPPORTED = -21,        /* EvaluationKeyError::Unsupported{Expansion} / Missing{GaloisKey} */
+    FHE_E_SIMD_UNAVAILABLE = -22,             /* EncodingError::SimdUnavailable (F/bfv/plaintext.rs:157-170)     */
+    FHE_E_TOO_MANY_VALUES = -23               /* PlaintextError::TooManyValues (F/bfv/plaintext.rs:313-325)      */
 };
 
 typedef struct fhe_ctx fhe_ctx;       /* == rq::Context on one device   (M/rq/context.rs:9-19)        */
@@ -64,6 +66,7 @@ typedef struct fhe_scaler fhe_scaler; /* == rq::scaler::Scaler          (M/rq/sc
 typedef struct fhe_ksk fhe_ksk;       /* == bfv::KeySwitchingKey        (F/bfv/keys/key_switching_key.rs:22-46) */
 typedef struct fhe_mul fhe_mul;       /* == bfv::Multiplicator          (F/bfv/ops/mul.rs:21-32)      */
 typedef struct fhe_params fhe_params; /* == bfv::BfvParameters' level tables (F/bfv/parameters.rs:83-117) */
+typedef struct fhe_encoder fhe_encoder; /* == BfvParameters' encoding tables (F/bfv/parameters.rs:598, 607-633, 711-725) */
 
 const char *fhe_last_error(void);
 const char *fhe_version(void);
@@ -447,6 +450,40 @@ fhe_status fhe_params_down_scaler(const fhe_params *p, size_t level, const fhe_s
  * relinearisation (F/bfv/ops/mod.rs:259-358), which uses the level's mul_params as the reference does. */
 fhe_status fhe_mul_create_default(const fhe_params *p, size_t level, const fhe_ksk *rk_or_null, int mod_switch,
                                   fhe_mul **out);
+
+/* ------------------------------------------------------- plaintext encoding ---- */
+/* Encoding and decoding of BFV plaintexts and ct +- pt.  Device-pointer forms only, with no host-pointer twin (like
+ * fhe_synth_uniform_dev): a host without PyTorch stages through fhe_buf_*.
+ * Every value and coefficient is reduced mod t on load.  For inputs in [0, t) -- what the reference accepts -- the
+ * results are the reference's, bit for bit.  The reference itself does not reduce: for inputs >= t its SIMD transform
+ * gets out-of-range words and Poly encoding keeps v mod q_i, so there the two differ. */
+enum { FHE_ENCODING_POLY = 0, FHE_ENCODING_SIMD = 1 };
+/* The encoding tables of a parameter set (BfvParametersBuilder::build, F/bfv/parameters.rs:598, 607-633, 711-725):
+ * t's NttOperator::new(t, N) when t admits a degree-N NTT (parameters.rs:71-75; otherwise SIMD calls return
+ * FHE_E_SIMD_UNAVAILABLE and Poly encoding still works), SEAL's index map (generator 3, m = 2N), and per level
+ * q_mod_t and delta_i = (-t)^-1 mod q_i.  `tables` (same typedef as fhe_params_create_with_tables) is called once, for
+ * t, when t admits the NTT, and only while this call runs; a non-zero return -> FHE_E_NTT_UNAVAILABLE.  NULL -> the
+ * engine's own psi (as fhe_params_create).  A host-only parameter set -> FHE_E_NO_DEVICE.  `par` must outlive the
+ * encoder. */
+fhe_status fhe_encoder_create(const fhe_params *par, fhe_ntt_tables_fn tables, void *user, fhe_encoder **out);
+void fhe_encoder_destroy(fhe_encoder *enc);
+/* PlaintextVec::try_encode (F/bfv/plaintext_vec.rs:70-102) with Encoding::{poly,simd}_at_level: values
+ * [batch][nvalues] (nvalues <= N, zero-padded; more -> FHE_E_TOO_MANY_VALUES) -> out [batch][L_level][N] Ntt, the
+ * plaintexts' `poly_ntt` (scaled = 0) or their Delta-scaled Plaintext::to_poly (F/bfv/plaintext.rs:172-196;
+ * scaled = 1), the operand of fhe_bfv_add_plain_dev.  Poly: coefficients = values; SIMD: coefficients[map[i]] =
+ * values[i], then NttOperator::backward mod t.  level > max -> FHE_E_INVALID_LEVEL.  The engine's scratch rows of
+ * coefficients mod t are cleared before they are reused (the reference zeroizes them, plaintext.rs:104, 178). */
+fhe_status fhe_bfv_encode_dev(const fhe_encoder *enc, int encoding, int scaled, size_t level, const uint64_t *values,
+                              size_t nvalues, uint64_t *out, size_t batch, void *stream);
+/* Vec<u64>::try_decode (F/bfv/plaintext.rs:157-170, 408-431): coefficients mod t [batch][N] (what fhe_bfv_decrypt_dev
+ * writes) -> values [batch][N].  Poly: the coefficients; SIMD: NttOperator::forward mod t, then out[i] = v[map[i]]. */
+fhe_status fhe_bfv_decode_dev(const fhe_encoder *enc, int encoding, const uint64_t *coeffs, uint64_t *out, size_t batch,
+                              void *stream);
+/* `&Ciphertext + &Plaintext` / `-` (F/bfv/ops/mod.rs:71-108, 166-203): out = ct with c0 +- pt, pt the Delta-scaled
+ * form (fhe_bfv_encode_dev with scaled = 1) at the ciphertext's level.  ct, out [batch][nparts][L][N] Ntt; pt
+ * [batch][L][N] (or [L][N] shared by the batch when pt_shared != 0); out == ct allowed. */
+fhe_status fhe_bfv_add_plain_dev(const fhe_ctx *ctx, int subtract, size_t nparts, const uint64_t *ct, const uint64_t *pt,
+                                 int pt_shared, uint64_t *out, size_t batch, void *stream);
 
 /* ------------------------------------------------- zq::primes (host, no GPU) ---- */
 /* generate_prime (M/zq/primes.rs:30-59): returns 0 when none exists. */

@@ -9,6 +9,7 @@
 //! | [`HipKsk`]         | `fhe_ksk`                | `fhe::bfv::KeySwitchingKey`        (keys/key_switching_key.rs:22-46) |
 //! | [`HipMul`]         | `fhe_mul`                | `fhe::bfv::Multiplicator`          (ops/mul.rs:21-32)      |
 //! | [`HipParams`]      | `fhe_params`             | level tables of `BfvParameters`    (parameters.rs:83-117)  |
+//! | [`HipEncoder`]     | `fhe_encoder`            | encoding tables of `BfvParameters` (parameters.rs:598, 711-725) |
 //! | [`Stream`]         | `hipStream_t` (ABI-made) | --                                                         |
 //! | [`DeviceBuffer`]   | `fhe_buf_alloc` memory   | the device shadow of `Poly.coefficients: Array2<u64>`      |
 //! | [`DeviceCiphertexts`] | a `DeviceBuffer` + shape | a batch of `bfv::Ciphertext` kept on the GPU between calls |
@@ -74,6 +75,8 @@ pub mod status {
     pub const EMPTY_DOT_PRODUCT: i32 = -19;
     pub const INVALID_EXPANSION_SIZE: i32 = -20;
     pub const EXPANSION_UNSUPPORTED: i32 = -21;
+    pub const SIMD_UNAVAILABLE: i32 = -22;
+    pub const TOO_MANY_VALUES: i32 = -23;
 }
 
 pub fn check(status: ffi::FheStatus) -> Result<()> {
@@ -96,6 +99,19 @@ fn whole_batch(what: &str, len: usize, per: usize) -> Result<usize> {
         return Err(shape_error(&format!("{what}: {len} u64 words is not a whole number of {per}-word items")));
     }
     Ok(len / per)
+}
+/// Checks a plaintext operand against a device-resident batch over `ctx`: true when one `[rows][N]` plaintext is
+/// shared by the batch, false for one per ciphertext.
+fn plain_operand(what: &str, ctx: &CtxView<'_>, ct: &DeviceCiphertexts, pt: &DeviceBuffer) -> Result<bool> {
+    if ct.rows != ctx.nmoduli() || ct.degree != ctx.degree() {
+        return Err(shape_error(&format!("{what}: the ciphertexts are not over this context")));
+    }
+    let pw = ct.rows * ct.degree;
+    if pt.len() == pw {
+        return Ok(true);
+    }
+    expect_len(what, pt.len(), ct.batch * pw)?;
+    Ok(false)
 }
 /// The device the patched crates put their handles on: `FHE_HIP_DEVICE` (one process per GPU when a batch is
 /// sharded across the GPUs of a node), default 0.
@@ -290,6 +306,17 @@ impl CtxView<'_> {
         })?;
         Ok(out)
     }
+    /// `&Ciphertext * &Plaintext` (ops/mod.rs:229-257) on a device-resident batch: every part times `pt`, the
+    /// plaintext's `poly_ntt` (`[rows][N]` shared by the batch, or `[batch][rows][N]`) -- `fhe_bfv_mul_plain_dev`.
+    pub fn mul_plain_dev(&self, ct: &DeviceCiphertexts, pt: &DeviceBuffer, stream: &Stream) -> Result<DeviceCiphertexts> {
+        let shared = plain_operand("mul_plain_dev", self, ct, pt)?;
+        let out = DeviceCiphertexts::alloc_on(self.device(), ct.batch, ct.parts, ct.rows, ct.degree, ct.level, stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_mul_plain_dev(self.ptr, ct.parts, ct.buf.as_ptr(), pt.as_ptr(), shared as c_int, out.buf.as_mut_ptr(),
+                                       ct.batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
 }
 
 pub struct HipCtx {
@@ -414,6 +441,21 @@ impl HipScaler {
     pub fn as_ptr(&self) -> *const ffi::FheScaler { self.ptr }
     pub fn from_ctx(&self) -> &Arc<HipCtx> { &self.from }
     pub fn to_ctx(&self) -> &Arc<HipCtx> { &self.to }
+    /// `SecretKey::try_decrypt` (keys/secret_key.rs:198-247) on a device-resident batch with this cipher-to-plaintext
+    /// scaler (`CipherPlainContext::scaler`): `s_ntt` `[from.L][N]` -> the plaintexts' coefficients mod t, `[batch][N]`
+    /// (`fhe_bfv_decrypt_dev`; clearing `s_ntt` and the result is the caller's job).
+    pub fn decrypt_dev(&self, plaintext_modulus: u64, s_ntt: &DeviceBuffer, ct: &DeviceCiphertexts, stream: &Stream) -> Result<DeviceBuffer> {
+        expect_len("decrypt_dev secret key", s_ntt.len(), self.from.poly_words())?;
+        if ct.rows != self.from.nmoduli() || ct.degree != self.from.degree() {
+            return Err(shape_error("decrypt_dev: the ciphertexts are not over the scaler's source context"));
+        }
+        let out = DeviceBuffer::alloc_on(self.from.device(), ct.batch * ct.degree, stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_decrypt_dev(self.ptr, plaintext_modulus, s_ntt.as_ptr(), ct.buf.as_ptr(), ct.parts, out.as_mut_ptr(),
+                                     ct.batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
     /// `Scaler::scale` (rq/scaler.rs:55-127): `[batch][from.L][N]` -> `[batch][to.L][N]`.
     pub fn scale(&self, input: &[u64], out: &mut [u64], repr_is_ntt: bool) -> Result<()> {
         let b = whole_batch("scale", input.len(), self.from.poly_words())?;
@@ -687,6 +729,24 @@ impl HipParams {
         let base = self.context_at_level(level)?;
         HipMul::finish(out, &base, MulKeep::Params { _params: self.clone(), _rk: rk.cloned() })
     }
+    /// The parameter set's plaintext encoding tables (`fhe_encoder_create`): t's NTT operator -- from `tables` (called
+    /// once, for t, with the same contract as `with_tables`) or the engine's own psi -- SEAL's index map, and per level
+    /// q mod t and delta.  The encoder keeps the parameter set alive.
+    pub fn encoder(self: &Arc<Self>, tables: Option<&mut TablesFn<'_>>) -> Result<HipEncoder> {
+        let mut out: *mut ffi::FheEncoder = ptr::null_mut();
+        match tables {
+            Some(f) => {
+                let mut fat: &mut TablesFn<'_> = f;
+                check(unsafe {
+                    ffi::fhe_encoder_create(self.ptr, Some(tables_trampoline), &mut fat as *mut &mut TablesFn<'_> as *mut c_void,
+                                            &mut out)
+                })?
+            }
+            None => check(unsafe { ffi::fhe_encoder_create(self.ptr, None, ptr::null_mut(), &mut out) })?,
+        }
+        let degree = self.context_at_level(0)?.degree();
+        Ok(HipEncoder { ptr: out, params: self.clone(), degree })
+    }
     /// `BfvParameters::context_at_level`: borrowed from `self`.
     pub fn context_at_level(&self, level: usize) -> Result<CtxView<'_>> {
         let mut out: *const ffi::FheCtx = ptr::null();
@@ -696,6 +756,56 @@ impl HipParams {
 }
 impl Drop for HipParams {
     fn drop(&mut self) { unsafe { ffi::fhe_params_destroy(self.ptr) } }
+}
+
+/// `Encoding::poly()` / `Encoding::simd()` (F/bfv/encoding.rs).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum Encoding {
+    Poly = 0,
+    Simd = 1,
+}
+
+/// The encoding tables of a `BfvParameters` on the device (`fhe_encoder`): `PlaintextVec::try_encode`,
+/// `Plaintext::to_poly` and the decoders without leaving the GPU.  Values are reduced mod t on load.
+pub struct HipEncoder {
+    ptr: *mut ffi::FheEncoder,
+    params: Arc<HipParams>, // the C object borrows the parameter set's contexts
+    degree: usize,
+}
+unsafe impl Send for HipEncoder {}
+unsafe impl Sync for HipEncoder {}
+impl HipEncoder {
+    /// `PlaintextVec::try_encode` (plaintext_vec.rs:70-102) at `level`: `values` `[batch][nvalues]` (nvalues <= N,
+    /// zero-padded) -> `[batch][L_level][N]` Ntt, each plaintext's `poly_ntt`, or with `scaled` its `to_poly()`
+    /// (plaintext.rs:172-196), the operand of `DeviceCiphertexts::{add,sub}_plain_dev`.
+    pub fn encode_dev(&self, encoding: Encoding, scaled: bool, level: usize, values: &DeviceBuffer, nvalues: usize,
+                      stream: &Stream) -> Result<DeviceBuffer> {
+        if nvalues > self.degree {
+            return Err(HipError { status: status::TOO_MANY_VALUES, message: "TooManyValues".into() });
+        }
+        let batch = whole_batch("encode_dev values", values.len(), nvalues)?;
+        let ctx = self.params.context_at_level(level)?;
+        let out = DeviceBuffer::alloc_on(ctx.device(), batch * ctx.poly_words(), stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_encode_dev(self.ptr, encoding as c_int, scaled as c_int, level, values.as_ptr(), nvalues,
+                                    out.as_mut_ptr(), batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+    /// `Vec::<u64>::try_decode` (plaintext.rs:157-170, 408-431): coefficients mod t `[batch][N]` (what
+    /// `HipScaler::decrypt_dev` returns) -> values `[batch][N]`.
+    pub fn decode_dev(&self, encoding: Encoding, coeffs: &DeviceBuffer, stream: &Stream) -> Result<DeviceBuffer> {
+        let batch = whole_batch("decode_dev coefficients", coeffs.len(), self.degree)?;
+        let device = self.params.context_at_level(0)?.device();
+        let out = DeviceBuffer::alloc_on(device, coeffs.len(), stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_decode_dev(self.ptr, encoding as c_int, coeffs.as_ptr(), out.as_mut_ptr(), batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+}
+impl Drop for HipEncoder {
+    fn drop(&mut self) { unsafe { ffi::fhe_encoder_destroy(self.ptr) } }
 }
 
 // ------------------------------------------------------------------------------------ engine-wide state
@@ -834,5 +944,23 @@ impl DeviceCiphertexts {
         let mut v = vec![0u64; self.buf.len()];
         self.buf.download(&mut v, stream)?;
         Ok(v)
+    }
+    /// `&Ciphertext + &Plaintext` (ops/mod.rs:71-108) over `ctx` (the ciphertexts' level): c0 + `pt`, `pt` the
+    /// Delta-scaled form (`HipEncoder::encode_dev` with `scaled`), `[rows][N]` shared or `[batch][rows][N]`.
+    pub fn add_plain_dev(&self, ctx: &CtxView<'_>, pt: &DeviceBuffer, stream: &Stream) -> Result<DeviceCiphertexts> {
+        self.plain_dev("add_plain_dev", ctx, pt, false, stream)
+    }
+    /// `&Ciphertext - &Plaintext` (ops/mod.rs:166-203): c0 - `pt`.
+    pub fn sub_plain_dev(&self, ctx: &CtxView<'_>, pt: &DeviceBuffer, stream: &Stream) -> Result<DeviceCiphertexts> {
+        self.plain_dev("sub_plain_dev", ctx, pt, true, stream)
+    }
+    fn plain_dev(&self, what: &str, ctx: &CtxView<'_>, pt: &DeviceBuffer, subtract: bool, stream: &Stream) -> Result<DeviceCiphertexts> {
+        let shared = plain_operand(what, ctx, self, pt)?;
+        let out = Self::alloc_on(ctx.device(), self.batch, self.parts, self.rows, self.degree, self.level, stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_add_plain_dev(ctx.as_ptr(), subtract as c_int, self.parts, self.buf.as_ptr(), pt.as_ptr(), shared as c_int,
+                                       out.buf.as_mut_ptr(), self.batch, stream.as_ptr())
+        })?;
+        Ok(out)
     }
 }

@@ -1,0 +1,19 @@
+// TEST INFRASTRUCTURE (tests/test_encode_isa.py): explicit instantiations of the plaintext encoding kernels at the whole-row
+// tile sizes of the stock parameter sets (4096 ... 16384 points), integer (narrow / general passes) and F64, so that their
+// device assembly can be produced in seconds and checked for scratch (spills).
+#include "kernels.hpp"
+namespace fhe {
+namespace k {
+#define FHE_PROBE_E(LOGM, NRW, HR)                                                                                     \
+    template __global__ void encode_simd_t_kernel<LOGM, NRW, HR>(const u64 *, u64, const uint32_t *, u64 *, const DevMod *, \
+                                                                 const u64x2 *, u64x2, u64x2);                         \
+    template __global__ void encode_lift_kernel<LOGM, NRW, HR>(LiftSrc, u64 *, uint32_t, const DevMod *, const u64x2 *); \
+    template __global__ void decode_simd_kernel<LOGM, NRW, HR>(const u64 *, const uint32_t *, u64 *, const DevMod *,   \
+                                                               const u64x2 *);
+#define FHE_PROBE_LM(LOGM) FHE_PROBE_E(LOGM, true, 0) FHE_PROBE_E(LOGM, false, 0) FHE_PROBE_E(LOGM, false, 3) \
+    FHE_PROBE_E(LOGM, false, 4) FHE_PROBE_E(LOGM, false, 5)
+FHE_PROBE_LM(12)
+FHE_PROBE_LM(13)
+FHE_PROBE_LM(14)
+}  // namespace k
+}  // namespace fhe
