@@ -148,6 +148,9 @@ SIGNATURES = {
     "fhe_bfv_encode_dev": (i32, [vp, i32, i32, sz, vp, sz, vp, sz, vp]),
     "fhe_bfv_decode_dev": (i32, [vp, i32, vp, vp, sz, vp]),
     "fhe_bfv_add_plain_dev": (i32, [vp, i32, sz, vp, vp, i32, vp, sz, vp]),
+    "fhe_bfv_sample_small_dev": (i32, [vp, sz, vp, i32, vp, sz, vp]),
+    "fhe_bfv_encrypt_sk_dev": (i32, [vp, sz, vp, vp, vp, vp, i32, vp, sz, vp]),
+    "fhe_bfv_encrypt_pk_dev": (i32, [vp, sz, vp, vp, vp, i32, vp, sz, vp]),
     "fhe_generate_prime": (u64, [sz, u64, u64]),
     "fhe_supports_opt": (i32, [u64]),
     "fhe_is_prime": (i32, [u64]),

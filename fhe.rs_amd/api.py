@@ -17,6 +17,7 @@ Polynomials are `[..., L, N]` row-major exactly like `rq::Poly`; leading dims ar
 Nothing in this module computes on the CPU: without the HIP library it cannot be imported.
 """
 import ctypes as C
+import secrets
 
 import numpy as np
 
@@ -560,6 +561,27 @@ class Context:
         check(L.fhe_poly_from_seed(self._h, sd.ctypes.data_as(_lib.u8p), _ptr(out), sd.shape[0]))
         return out
 
+    def sample_small(self, seeds, variance, ntt=True):
+        """Poly::small (rq/mod.rs:298-330) of ChaCha8Rng::from_seed(seed) per 32-byte seed (fhe_bfv_sample_small_dev):
+        seeds [batch, 32] uint8 -> [batch, L, N], Ntt (ntt=True) or PowerBasis.  numpy seeds -> numpy out; device seeds
+        -> a device array.  The device buffers this wrapper stages host seeds and samples through are cleared before
+        they are freed; what it returns, and device seeds the caller passes, are the caller's to clear."""
+        staged = []
+        try:
+            sd, b, own = _seeds(seeds, 1, self.device)
+            if own:
+                staged.append(sd)
+            host = not _is_dev(seeds)
+            out = DeviceArray((b, self.nmoduli, self.degree), max(self.device, 0)) if host else _empty_dev(
+                seeds, (b, self.nmoduli, self.degree))
+            if host:
+                staged.append(out)
+            check(_lib.lib().fhe_bfv_sample_small_dev(self._h, variance, _dptr8(sd), 1 if ntt else 0, _dptr(out), b,
+                                                      _stream()))
+            return out.download() if host else out
+        finally:
+            _wipe(staged)
+
     def synth_uniform(self, seed, ct0, part0, nparts, batch):
         """Device-side synthetic residues [batch, nparts, L, N] (bench / parity inputs)."""
         shape = (batch, nparts, self.nmoduli, self.degree)
@@ -947,14 +969,203 @@ class Encoder:
         return out.download()
 
 
+def _alloc(shape, device, itemsize=8):
+    """A new device array: a torch CUDA tensor when torch drives the device and no `Stream` is current, else a
+    DeviceArray on the ABI's own allocator."""
+    if getattr(_tls, "stream", None) is not None or torch is None or not torch.cuda.is_available():
+        return DeviceArray(shape, max(device, 0), itemsize)
+    return torch.empty(tuple(shape), dtype=torch.int64 if itemsize == 8 else torch.uint8, device=f"cuda:{max(device, 0)}")
+
+
+def _seeds(seeds, count, device):
+    """(device uint8 buffer [n, 32], n, owned): None -> `count` fresh seeds from `secrets`; bytes -> one seed; a list
+    of bytes, a numpy uint8 [n, 32] array or a device uint8 [n, 32] array as given.  `owned`: the buffer was staged
+    here (the caller of _seeds clears it with _wipe once the engine call is enqueued)."""
+    if seeds is not None and _is_dev(seeds):
+        if seeds.element_size() != 1 or seeds.numel() % 32:
+            raise ValueError("device seeds must be a contiguous uint8 [count, 32] array")
+        return seeds, int(seeds.numel() // 32), False
+    if seeds is None:
+        a = np.frombuffer(b"".join(secrets.token_bytes(32) for _ in range(count)), dtype=np.uint8)
+    elif isinstance(seeds, (bytes, bytearray)):
+        a = np.frombuffer(bytes(seeds), dtype=np.uint8)
+    elif isinstance(seeds, (list, tuple)):
+        a = np.frombuffer(b"".join(bytes(x) for x in seeds), dtype=np.uint8)
+    else:
+        a = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint8)).reshape(-1)
+    if a.size == 0 or a.size % 32:
+        raise ValueError("seeds are 32 bytes each")
+    return DeviceArray.from_numpy(a.reshape(-1, 32), max(device, 0)), a.size // 32, True
+
+
+def _wipe(staged):
+    """Clears the device buffers staged from host secrets (seeds, samples, plaintexts) on the current stream, ahead of
+    their release (the engine clears its own scratch the same way)."""
+    for d in staged:
+        check(_lib.lib().fhe_buf_zero_async(C.c_void_p(d.data_ptr()), d.nbytes, _stream()))
+
+
+def _seed_count(seeds):
+    if _is_dev(seeds):
+        return int(seeds.numel() // 32)
+    if isinstance(seeds, (bytes, bytearray)):
+        return len(seeds) // 32
+    if isinstance(seeds, (list, tuple)):
+        return len(seeds)
+    return int(np.asarray(seeds).size // 32)
+
+
+def _batch_of(pt, count):
+    """(leading dims, batch, pt_shared) of a plaintext [..., L, N] (or None) encrypted with `count` seeds."""
+    if pt is None or len(pt.shape) == 2:
+        return ((count,) if count != 1 or pt is None else ()), count, 1
+    lead = tuple(int(d) for d in pt.shape[:-2])
+    return lead, int(np.prod(lead)), 0
+
+
+class SecretKey:
+    """bfv::SecretKey (F/bfv/keys/secret_key.rs) kept on the device: `s_ntt` is the level-0 key in Ntt form [L, N]
+    (level l uses its first L - l rows).  Made by `SecretKey.random`; nothing here copies it to the host.  Device buffers
+    the encryption wrappers stage host seeds and plaintexts through are cleared before they are freed; `s_ntt` itself
+    and device arrays the caller passes are the caller's to clear."""
+
+    def __init__(self, params, s_ntt):
+        self.params, self.s_ntt = params, s_ntt
+
+    @classmethod
+    def random(cls, params, seed=None):
+        """SecretKey::random (secret_key.rs:41-46): Poly::small(variance) of ChaCha8Rng::from_seed(seed) (32 bytes;
+        None: from `secrets`), in Ntt form over the level-0 context (fhe_bfv_sample_small_dev)."""
+        ctx = params.context_at_level(0)
+        sd, _, own = _seeds(seed, 1, params.device)
+        try:
+            out = _alloc((ctx.nmoduli, params.degree), params.device)
+            check(_lib.lib().fhe_bfv_sample_small_dev(ctx._h, params.variance, _dptr8(sd), 1, _dptr(out), 1,
+                                                      _stream()))
+        finally:
+            _wipe([sd] if own else [])
+        return cls(params, out)
+
+    def encrypt(self, pt, level=0, a_seeds=None, e_seeds=None):
+        """SecretKey::try_encrypt (secret_key.rs:100-134) of Delta-scaled plaintexts pt [..., L - level, N]
+        (`Encoder.encode(..., scaled=True)`; [L - level, N] with several seeds: shared; None: the zero plaintext) ->
+        [..., 2, L - level, N] Ntt.  c1 = Poly::random_from_seed(a_seeds[b]) (the wire format's seeded c1), the error
+        is Poly::small of ChaCha8Rng::from_seed(e_seeds[b]); one a seed and one e seed per plaintext, seeds not given
+        come from `secrets`.  numpy in -> numpy out; a device array in -> a device array out."""
+        L = _lib.lib()
+        return _encrypt(self.params, level, pt, a_seeds, e_seeds, True, lambda ctx, a, e, ptp, shared, out, b: (
+            L.fhe_bfv_encrypt_sk_dev(ctx._h, self.params.variance, _dptr(self.s_ntt), _dptr8(a), _dptr8(e), ptp, shared,
+                                     _dptr(out), b, _stream())))
+
+    def decrypt(self, ct, level=0):
+        """SecretKey::try_decrypt (secret_key.rs:198-247): ct [..., nparts, L - level, N] -> coefficients mod t
+        [..., N] (Encoder.decode turns them into values).  The key stays on the device: numpy ciphertexts are
+        uploaded."""
+        if _is_dev(ct):
+            return self.params.decrypt(self.s_ntt, ct, level)
+        x = DeviceArray.from_numpy(_np(ct), max(self.params.device, 0))
+        d = self.params.decrypt(self.s_ntt, x, level)
+        try:
+            return _download(d)
+        finally:
+            _wipe([d])   # (the plaintext coefficients)
+
+
+class PublicKey:
+    """bfv::PublicKey (F/bfv/keys/public_key.rs) on the device: the encryption of zero under `sk` (PublicKey::new,
+    :26-30), [2, L, N] Ntt, plus its copies switched down to each level used (made once, then cached)."""
+
+    def __init__(self, sk, a_seed=None, e_seed=None):
+        self.params = sk.params
+        dev = self.params.device
+        a, _, own_a = _seeds(a_seed, 1, dev)
+        e, _, own_e = _seeds(e_seed, 1, dev)
+        try:   # (device seeds in: the key stays on the device)
+            c = sk.encrypt(None, 0, a_seeds=a, e_seeds=e)
+        finally:
+            _wipe([x for x, own in ((a, own_a), (e, own_e)) if own])
+        self.c = c.reshape(2, c.shape[-2], c.shape[-1])
+        self._levels = {0: self.c}
+
+    def at_level(self, level):
+        """The key over the context of `level` (Ciphertext::switch_down until the level matches, public_key.rs:66-74)."""
+        if level not in self._levels:
+            if not 0 <= level <= self.params.max_level:
+                raise FheError(-12, "InvalidLevel")
+            ctx = self.params.context_at_level(0)
+            self._levels[level] = ctx.ciphertext_switch_to_level(self.c, level)
+        return self._levels[level]
+
+    def encrypt(self, pt, level=0, seeds=None):
+        """PublicKey::try_encrypt (public_key.rs:47-97) of Delta-scaled plaintexts pt [..., L - level, N] (as
+        SecretKey.encrypt) -> [..., 2, L - level, N] Ntt; u, e1, e2 are three consecutive Poly::small draws of
+        ChaCha8Rng::from_seed(seeds[b]), one seed per plaintext; seeds not given come from `secrets`."""
+        pk = self.at_level(level)
+        L = _lib.lib()
+        return _encrypt(self.params, level, pt, seeds, None, False, lambda ctx, sd, _e, ptp, shared, out, b: (
+            L.fhe_bfv_encrypt_pk_dev(ctx._h, self.params.variance, _dptr(pk), _dptr8(sd), ptp, shared, _dptr(out), b,
+                                     _stream())))
+
+
+def _download(x):
+    return x.download() if isinstance(x, DeviceArray) else x.cpu().numpy().view(np.uint64)
+
+
+def _encrypt(params, level, pt, seeds, seeds2, two, call):
+    """The shared body of SecretKey.encrypt (two seed sets: a, e) and PublicKey.encrypt (one): checks that there is one
+    seed of each set per plaintext, stages numpy plaintexts and host seeds (cleared again after the call), sizes the
+    output and runs call(ctx, seeds, seeds2, pt_ptr, pt_shared, out, batch)."""
+    if not 0 <= level <= params.max_level:
+        raise FheError(-12, "InvalidLevel")
+    ctx = params.context_at_level(level)
+    if pt is not None and len(pt.shape) > 2:
+        count = int(np.prod(pt.shape[:-2]))
+    elif seeds is not None:
+        count = _seed_count(seeds)
+    elif two and seeds2 is not None:
+        count = _seed_count(seeds2)
+    else:
+        count = 1
+    if pt is not None and (int(pt.shape[-2]), int(pt.shape[-1])) != (ctx.nmoduli, params.degree):
+        raise FheError(-1, "the plaintext must be [..., L - level, N] at the encryption level")
+    staged = []
+    try:
+        sd, n, own = _seeds(seeds, count, params.device)
+        if own:
+            staged.append(sd)
+        sd2 = None
+        if two:
+            sd2, n2, own2 = _seeds(seeds2, n, params.device)
+            if own2:
+                staged.append(sd2)
+            if n2 != n:
+                raise FheError(-1, "one e seed per a seed: %d a seeds, %d e seeds" % (n, n2))
+        lead, batch, shared = _batch_of(pt, n)
+        if batch != n:
+            raise FheError(-1, "one seed per plaintext: %d plaintexts, %d seeds" % (batch, n))
+        host = not _is_dev(pt if pt is not None else seeds)   # numpy (or host seeds, for pt None) in -> numpy out
+        if host and pt is not None:
+            pt = DeviceArray.from_numpy(_np(pt), max(params.device, 0))
+            staged.append(pt)
+        oshape = lead + (2, ctx.nmoduli, params.degree)
+        out = DeviceArray(oshape, max(params.device, 0)) if host else _empty_dev(pt if pt is not None else seeds,
+                                                                                 oshape)
+        check(call(ctx, sd, sd2, _dptr(pt) if pt is not None else None, shared, out, batch))
+        return out.download() if host else out
+    finally:
+        _wipe(staged)
+
+
 class BfvParameters:
     """The device-table part of bfv::BfvParameters (crates/fhe/src/bfv/parameters.rs:560-738):
     per-level contexts, the extended multiplication basis and per-level mul parameters."""
 
-    def __init__(self, degree, plaintext_modulus, moduli=None, moduli_sizes=None, device=0, tables_fn=None):
+    def __init__(self, degree, plaintext_modulus, moduli=None, moduli_sizes=None, device=0, tables_fn=None, variance=10):
         """tables_fn(modulus, degree) -> dict(omegas, omegas_shoup, zetas_inv, zetas_inv_shoup, size_inv,
         size_inv_shoup): the host's NttOperator tables for every modulus the parameter set builds a context over
-        (fhe_params_create_with_tables); None: the engine's own psi (fhe_params_create)."""
+        (fhe_params_create_with_tables); None: the engine's own psi (fhe_params_create).  variance: the centered
+        binomial variance of the secret key and the errors (BfvParametersBuilder::set_variance, default 10); the
+        encryption calls return FheError -24 (InvalidVariance) outside [1, 32]."""
         L = _lib.lib()
         if moduli_sizes:
             sizes = (C.c_size_t * len(moduli_sizes))(*moduli_sizes)
@@ -973,6 +1184,7 @@ class BfvParameters:
             # nothing has to keep the callback alive afterwards)
         self._h = h
         self.degree, self.plaintext, self.moduli, self.device = degree, plaintext_modulus, [int(x) for x in m], device
+        self.variance = variance
         self.max_level = L.fhe_params_max_level(h)
 
     def __del__(self):

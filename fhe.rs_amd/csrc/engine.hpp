@@ -26,7 +26,7 @@ enum : int {
     E_INVALID_SUBST = -10, E_PARAMETER_MISMATCH = -11, E_INVALID_LEVEL = -12, E_MUL_POLY_COUNT = -13,
     E_EMPTY_MODULI = -14, E_NON_COPRIME = -15, E_NOT_ENOUGH_PRIMES = -16, E_KEYSWITCH_UNSUPPORTED = -17,
     E_NO_DEVICE = -18, E_EMPTY_DOT = -19, E_EXPANSION_SIZE = -20, E_EXPANSION_UNSUPPORTED = -21,
-    E_SIMD_UNAVAILABLE = -22, E_TOO_MANY_VALUES = -23
+    E_SIMD_UNAVAILABLE = -22, E_TOO_MANY_VALUES = -23, E_INVALID_VARIANCE = -24
 };
 
 #define FHE_HIP_CHECK(expr)                                                                        \
@@ -2924,6 +2924,140 @@ inline void decode(const Encoder &e, bool simd, const u64 *coeffs, u64 *out, siz
     launch_ntt(tc, false, tmp.u(), tmp.u(), full_map(tc, 1), batch, s);
     FHE_LAUNCH("decode_gather", k::perm_reduce_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
                (const u64 *)tmp.u(), (u64)e.n, (u64)e.n, (const uint32_t *)e.d_map.p, out, e.tm, (uint32_t)e.logn, total);
+}
+
+// ------------------------------------------------------------------------ encryption ----
+// Poly::small (M/rq/mod.rs:298-330) and sample_vec_cbd (fhe-util/src/lib.rs:22-66).
+inline void check_variance(size_t variance) {
+    require(variance >= 1 && variance <= 32, E_INVALID_VARIANCE, "InvalidVariance: the variance must be in [1, 32]");
+}
+
+// sample_vec_cbd draws of ChaCha8Rng::from_seed(seeds[b]): `kdraws` consecutive draws of N = 2^logn samples ->
+// smp [batch][kdraws N]
+inline void cbd_sample(const uint8_t *seeds, size_t variance, size_t logn, size_t kdraws, int8_t *smp, size_t batch,
+                       hipStream_t s) {
+    const u64 n = 1ull << logn, ns = (u64)kdraws * n;
+    const u64 wpd = variance <= 16 ? ((u64)n * 4 * variance + 63) / 64 : 2 * (u64)n;   // next_u64 words per draw
+    FHE_LAUNCH("cbd_sample", k::cbd_sample_kernel, dim3(blocks_for(ns, k::CBD_THREADS), (unsigned)batch),
+               dim3(k::CBD_THREADS), k::CBD_SMEM_BYTES, s, seeds, smp, (uint32_t)variance, ns, (uint32_t)logn, wpd);
+}
+
+// (int8 scratch rounded up to whole 16-byte words)
+inline size_t small_bytes(size_t count) { return (count + 15) & ~(size_t)15; }
+
+// Poly::small(ctx, variance, ChaCha8Rng::from_seed(seeds[b])): out [batch][L][N], PowerBasis or (to_ntt) Ntt.
+inline void sample_small(const Ctx &c, size_t variance, const uint8_t *seeds, bool to_ntt, u64 *out, size_t batch,
+                         hipStream_t s) {
+    c.need_device();
+    check_variance(variance);
+    if (!batch) return;
+    require(batch <= 65535 && batch * c.L <= 0x7fffffffu, E_ARG, "sample_small: batch exceeds the grid limit");
+    // the samples are secrets (SecretKey::random, the errors): cleared before the block returns to the pool
+    WsGuard smp(small_bytes(batch * c.n), s, true);
+    int8_t *sp = (int8_t *)smp.p;
+    cbd_sample(seeds, variance, c.logn, 1, sp, batch, s);
+    if (to_ntt && c.logn <= 14) {
+        const int hr = f64_rows(c, 0, c.L, !f64_disabled());
+        FHE_ENC_SWITCH(small_ntt_kernel, c.logn, all_below_2p60(c), hr, "small_ntt", batch * c.L, s, (const int8_t *)sp,
+                       out, (uint32_t)c.L, c.dmods(), hr > 0 ? c.dtw_f() : c.dtw());
+        return;
+    }
+    const u64 total = (u64)batch * c.L * c.n;
+    FHE_LAUNCH("small_lift", k::small_lift_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
+               (const int8_t *)sp, out, (uint32_t)c.L, c.dmods(), (uint32_t)c.logn, total);
+    if (to_ntt) launch_ntt(c, false, out, out, full_map(c, c.L), batch, s);
+}
+
+// Items per launch group of an encryption: the u64 scratch rows of one group (`rows_per_item` polynomials per item:
+// the seeded `a`, and for rows larger than one LDS tile the transformed samples) stay within `budget` bytes, and the
+// batch is split into groups of equal size (a small tail group would underfill the device).
+inline size_t encrypt_group(const Ctx &c, size_t rows_per_item, size_t batch, size_t budget) {
+    const size_t per = std::max<size_t>(1, rows_per_item) * c.L * c.n * sizeof(u64);
+    const size_t most = std::max<size_t>(1, std::min<size_t>(65535, budget / per));
+    const size_t groups = (batch + most - 1) / most;
+    return (batch + groups - 1) / groups;
+}
+
+// SecretKey::encrypt_poly (F/bfv/keys/secret_key.rs:100-134) with a = Poly::random_from_seed(a_seeds[b]) and
+// e = Poly::small(ChaCha8Rng::from_seed(e_seeds[b])): out [batch][2][L][N] Ntt, c0 = e - a s + pt, c1 = a.
+// s_ntt [L][N]; pt [batch][L][N] Delta-scaled (pt_shared: [L][N]; null: zero).
+inline void encrypt_sk(const Ctx &c, size_t variance, const u64 *s_ntt, const uint8_t *a_seeds, const uint8_t *e_seeds,
+                       const u64 *pt, bool pt_shared, u64 *out, size_t batch, hipStream_t s) {
+    c.need_device();
+    check_variance(variance);
+    if (!batch) return;
+    require(batch * c.L <= 0x7fffffffu, E_ARG, "encrypt: batch exceeds the grid limit");
+    const bool f64_on = !f64_disabled();   // (read once per call: every transform of the call takes the same kind)
+    const int hr = c.logn <= 14 ? f64_rows(c, 0, c.L, f64_on) : 0;
+    const u64 PL = (u64)c.L * c.n;
+    // `a` is expanded into scratch: the unchanged seed_expand_kernel writes whole polynomials back to back
+    // ([npolys][L][N]), so it cannot place them at out[b][1] (item stride 2 L N); the epilogue copies a into c1 while
+    // it reads it for a (.) s.  Whole rows: groups of up to 1 GiB of `a` (seed_expand_kernel walks one polynomial per
+    // workgroup and needs wide launches); larger rows: 256 MiB of `a` and transformed samples.
+    const size_t group = c.logn <= 14 ? encrypt_group(c, 1, batch, (size_t)1 << 30)
+                                      : encrypt_group(c, 2, batch, (size_t)256 << 20);
+    for (size_t b0 = 0; b0 < batch; b0 += group) {
+        const size_t nb = std::min(group, batch - b0);
+        const u64 *ptb = pt ? pt + (pt_shared ? 0 : b0 * PL) : nullptr;
+        u64 *outb = out + b0 * 2 * PL;
+        WsGuard smp(small_bytes(nb * c.n), s, true), a(nb * PL * sizeof(u64), s);
+        int8_t *sp = (int8_t *)smp.p;
+        cbd_sample(e_seeds + b0 * 32, variance, c.logn, 1, sp, nb, s);
+        polys_from_seeds(c, a_seeds + b0 * 32, a.u(), nb, s);
+        if (c.logn <= 14) {
+            FHE_ENC_SWITCH(encrypt_sk_kernel, c.logn, all_below_2p60(c), hr, "encrypt_sk", nb * c.L, s, (const int8_t *)sp,
+                           (const u64 *)a.u(), s_ntt, ptb, pt_shared ? (u64)0 : PL, outb, (uint32_t)c.L, c.dmods(),
+                           hr > 0 ? c.dtw_f() : c.dtw());
+            continue;
+        }
+        // rows larger than one LDS tile: lift, launch_ntt, then the epilogue as a pass of its own
+        WsGuard x(nb * PL * sizeof(u64), s, true);
+        const u64 total = (u64)nb * PL;
+        FHE_LAUNCH("small_lift", k::small_lift_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
+                   (const int8_t *)sp, x.u(), (uint32_t)c.L, c.dmods(), (uint32_t)c.logn, total);
+        launch_ntt(c, false, x.u(), x.u(), full_map(c, c.L), nb, s);
+        FHE_LAUNCH("encrypt_combine", k::encrypt_combine_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS),
+                   0, s, (const u64 *)x.u(), (const u64 *)a.u(), s_ntt, ptb, pt_shared ? (u64)0 : PL, outb, (uint32_t)c.L,
+                   c.dmods(), (uint32_t)c.logn, 0u, total);
+    }
+}
+
+// PublicKey::try_encrypt (F/bfv/keys/public_key.rs:47-97) with u, e1, e2 three consecutive Poly::small draws of
+// ChaCha8Rng::from_seed(seeds[b]): out [batch][2][L][N] Ntt, c0 = u pk0 + e1 + pt, c1 = u pk1 + e2.  pk [2][L][N] over
+// this context.
+inline void encrypt_pk(const Ctx &c, size_t variance, const u64 *pk, const uint8_t *seeds, const u64 *pt, bool pt_shared,
+                       u64 *out, size_t batch, hipStream_t s) {
+    c.need_device();
+    check_variance(variance);
+    if (!batch) return;
+    require(batch * c.L <= 0x7fffffffu, E_ARG, "encrypt: batch exceeds the grid limit");
+    const bool f64_on = !f64_disabled();
+    const int hr = c.logn <= 14 ? f64_rows(c, 0, c.L, f64_on) : 0;
+    const u64 PL = (u64)c.L * c.n;
+    const size_t group = c.logn <= 14 ? 65535 : encrypt_group(c, 3, batch, (size_t)256 << 20);
+    for (size_t b0 = 0; b0 < batch; b0 += group) {
+        const size_t nb = std::min(group, batch - b0);
+        const u64 *ptb = pt ? pt + (pt_shared ? 0 : b0 * PL) : nullptr;
+        u64 *outb = out + b0 * 2 * PL;
+        WsGuard smp(small_bytes(nb * 3 * c.n), s, true);
+        int8_t *sp = (int8_t *)smp.p;
+        cbd_sample(seeds + b0 * 32, variance, c.logn, 3, sp, nb, s);
+        if (c.logn <= 14) {
+            for (uint32_t stage = 0; stage < 3; stage++)
+                FHE_ENC_SWITCH(encrypt_pk_kernel, c.logn, all_below_2p60(c), hr, "encrypt_pk", nb * c.L, s,
+                               (const int8_t *)sp, pk, ptb, pt_shared ? (u64)0 : PL, outb, (uint32_t)c.L, c.dmods(),
+                               hr > 0 ? c.dtw_f() : c.dtw(), stage);
+            continue;
+        }
+        WsGuard x(nb * 3 * PL * sizeof(u64), s, true);
+        const u64 lifted = (u64)nb * 3 * PL, total = (u64)nb * PL;
+        FHE_LAUNCH("small_lift", k::small_lift_ew_kernel, dim3(blocks_for(lifted, EW_THREADS)), dim3(EW_THREADS), 0, s,
+                   (const int8_t *)sp, x.u(), (uint32_t)c.L, c.dmods(), (uint32_t)c.logn, lifted);
+        launch_ntt(c, false, x.u(), x.u(), full_map(c, c.L), nb * 3, s);
+        FHE_LAUNCH("encrypt_combine", k::encrypt_combine_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS),
+                   0, s, (const u64 *)x.u(), (const u64 *)nullptr, pk, ptb, pt_shared ? (u64)0 : PL, outb, (uint32_t)c.L,
+                   c.dmods(), (uint32_t)c.logn, 1u, total);
+    }
 }
 #undef FHE_ENC_SWITCH
 #undef FHE_ENC_CASE_F64

@@ -1665,6 +1665,59 @@ fhe_status fhe_bfv_add_plain_dev(const fhe_ctx *ctx, int subtract, size_t nparts
     });
 }
 
+// ------------------------------------------------------------------------- encryption ----
+// Device-pointer forms only, like the encoding entry points: secrets and errors are never staged through host memory
+// by the engine.
+fhe_status fhe_bfv_sample_small_dev(const fhe_ctx *ctx, size_t variance, const uint8_t *seeds, int to_ntt, uint64_t *out,
+                                    size_t batch, void *stream) {
+    return guard([&] {
+        need(ctx, "ctx");
+        const Ctx &c = *ctx->c;
+        c.need_device();
+        check_variance(variance);
+        if (batch) {
+            need(seeds, "seeds");
+            need(out, "out");
+        }
+        set_device(c);
+        sample_small(c, variance, seeds, to_ntt != 0, out, batch, as_stream(stream));
+    });
+}
+fhe_status fhe_bfv_encrypt_sk_dev(const fhe_ctx *ctx, size_t variance, const uint64_t *s_ntt, const uint8_t *a_seeds,
+                                  const uint8_t *e_seeds, const uint64_t *pt, int pt_shared, uint64_t *out, size_t batch,
+                                  void *stream) {
+    return guard([&] {
+        need(ctx, "ctx");
+        const Ctx &c = *ctx->c;
+        c.need_device();
+        check_variance(variance);
+        if (batch) {
+            need(s_ntt, "s_ntt");
+            need(a_seeds, "a_seeds");
+            need(e_seeds, "e_seeds");
+            need(out, "out");
+        }
+        set_device(c);
+        encrypt_sk(c, variance, s_ntt, a_seeds, e_seeds, pt, pt_shared != 0, out, batch, as_stream(stream));
+    });
+}
+fhe_status fhe_bfv_encrypt_pk_dev(const fhe_ctx *ctx, size_t variance, const uint64_t *pk, const uint8_t *seeds,
+                                  const uint64_t *pt, int pt_shared, uint64_t *out, size_t batch, void *stream) {
+    return guard([&] {
+        need(ctx, "ctx");
+        const Ctx &c = *ctx->c;
+        c.need_device();
+        check_variance(variance);
+        if (batch) {
+            need(pk, "pk");
+            need(seeds, "seeds");
+            need(out, "out");
+        }
+        set_device(c);
+        encrypt_pk(c, variance, pk, seeds, pt, pt_shared != 0, out, batch, as_stream(stream));
+    });
+}
+
 // --------------------------------------------------------------------------- primes ----
 uint64_t fhe_generate_prime(size_t num_bits, uint64_t modulo, uint64_t upper_bound) {
     return generate_prime(num_bits, modulo, upper_bound);

@@ -26,6 +26,8 @@
 //   encode_simd_t_kernel, encode_lift_kernel, decode_simd_kernel   PlaintextVec::try_encode, Plaintext::to_poly, decoders
 //                                                                   F/bfv/plaintext_vec.rs:70-102, plaintext.rs:157-196
 //   add_plain_kernel        ct +- pt                                 F/bfv/ops/mod.rs:71-108, 166-203
+//   cbd_sample_kernel, small_ntt_kernel, encrypt_sk_kernel, encrypt_pk_kernel   Poly::small, SecretKey::encrypt_poly,
+//                           PublicKey::try_encrypt   M/rq/mod.rs:298-330, F/bfv/keys/secret_key.rs:100-134, public_key.rs:47-97
 // Compile-time knobs live in knobs.hpp (pinned in the release build); rejected kernel variants in tools/lab/ (lab builds only).
 #pragma once
 #include "kernels_common.hpp"
@@ -35,6 +37,7 @@
 #include "kernels_scaler.hpp"
 #include "kernels_misc.hpp"
 #include "kernels_encode.hpp"
+#include "kernels_encrypt.hpp"
 
 namespace fhe {
 namespace k {

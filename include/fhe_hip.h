@@ -58,7 +58,8 @@ enum {
     FHE_E_INVALID_EXPANSION_SIZE = -20,       /* EvaluationKeyError::InvalidExpansionSize          */
     FHE_E_EXPANSION_UNSUPPORTED = -21,        /* EvaluationKeyError::Unsupported{Expansion} / Missing{GaloisKey} */
     FHE_E_SIMD_UNAVAILABLE = -22,             /* EncodingError::SimdUnavailable (F/bfv/plaintext.rs:157-170)     */
-    FHE_E_TOO_MANY_VALUES = -23               /* PlaintextError::TooManyValues (F/bfv/plaintext.rs:313-325)      */
+    FHE_E_TOO_MANY_VALUES = -23,              /* PlaintextError::TooManyValues (F/bfv/plaintext.rs:313-325)      */
+    FHE_E_INVALID_VARIANCE = -24              /* Error::InvalidVariance (M/rq/mod.rs:303-309)                    */
 };
 
 typedef struct fhe_ctx fhe_ctx;       /* == rq::Context on one device   (M/rq/context.rs:9-19)        */
@@ -484,6 +485,45 @@ fhe_status fhe_bfv_decode_dev(const fhe_encoder *enc, int encoding, const uint64
  * [batch][L][N] (or [L][N] shared by the batch when pt_shared != 0); out == ct allowed. */
 fhe_status fhe_bfv_add_plain_dev(const fhe_ctx *ctx, int subtract, size_t nparts, const uint64_t *ct, const uint64_t *pt,
                                  int pt_shared, uint64_t *out, size_t batch, void *stream);
+
+/* ------------------------------------------------------------- encryption ---- */
+/* Sampling and encryption of BFV ciphertexts.  Device-pointer forms only, with no host-pointer twin: secrets and
+ * errors are never staged through host memory by the engine (a host without PyTorch stages through fhe_buf_*).
+ *
+ * ChaCha8Rng::from_seed(seed) below is the generator whose key is the 32 seed bytes read as little-endian words, with
+ * no hashing (Poly::random_from_seed hashes its seed with SHA-256 first).  Its word layout -- 64-bit block counter from
+ * 0, stream id 0, next_u64 = two consecutive little-endian words, low word first -- restates rand_chacha, which the
+ * reference does not vendor: PARITY UNPINNED against a real fhe.rs run, exactly like fhe_poly_from_seed.
+ * sample_vec_cbd (fhe-util/src/lib.rs:22-66) is taken as counter-addressable: within one draw, for v <= 16 sample i is
+ * popcount(bits [4v i, 4v i + 2v)) - popcount(bits [4v i + 2v, 4v (i + 1))) of the draw's next_u64 words, least
+ * significant bit first; for 17 <= v <= 32 sample i takes the draw's words 2i and 2i + 1.  Each draw starts a fresh
+ * pool and drops the bits left in its last word: a draw of N samples consumes ceil(N 4v / 64) words (2N for v > 16),
+ * and consecutive draws of one generator start at the next word.  variance outside [1, 32] -> FHE_E_INVALID_VARIANCE.
+ *
+ * Secret hygiene: the engine's scratch that holds samples (secret key, u, errors) or their transforms is cleared on
+ * the stream before it returns to the pool.  The caller's buffers -- s_ntt, and `out` of fhe_bfv_sample_small_dev --
+ * are the caller's to clear.  No branch or address of the kernels depends on a sample, a key or a plaintext word.
+ * Outputs are canonical words in the usual [batch][parts][L][N] layout; batch == 0 is a no-op (NULL buffers allowed). */
+/* Poly::small(ctx, variance, &mut ChaCha8Rng::from_seed(seeds[b])) (M/rq/mod.rs:298-330): seeds [batch][32] ->
+ * out [batch][L][N], PowerBasis (to_ntt = 0) or Ntt (to_ntt = 1); negative samples lift to q_i - |x|
+ * (try_convert_from(&[i64], ctx, false)).  With to_ntt = 1 over the top-level context this is SecretKey::random
+ * (F/bfv/keys/secret_key.rs:41-46) in the s_ntt form fhe_bfv_decrypt_dev takes. */
+fhe_status fhe_bfv_sample_small_dev(const fhe_ctx *ctx, size_t variance, const uint8_t *seeds, int to_ntt, uint64_t *out,
+                                    size_t batch, void *stream);
+/* SecretKey::encrypt_poly (F/bfv/keys/secret_key.rs:100-134): out[b][1] = Poly::random_from_seed(ctx, a_seeds[b])
+ * (bit-identical to fhe_poly_from_seed_dev: the wire format's seeded c1), out[b][0] = small(ctx, variance,
+ * ChaCha8Rng::from_seed(e_seeds[b]))_ntt - out[b][1] (.) s_ntt + pt[b].  s_ntt [L][N] over ctx; pt [batch][L][N] the
+ * Delta-scaled Ntt form fhe_bfv_encode_dev(scaled = 1) writes at ctx's level ([L][N] shared when pt_shared != 0; NULL:
+ * the zero plaintext, which is PublicKey::new, F/bfv/keys/public_key.rs:26-30); out [batch][2][L][N] Ntt. */
+fhe_status fhe_bfv_encrypt_sk_dev(const fhe_ctx *ctx, size_t variance, const uint64_t *s_ntt, const uint8_t *a_seeds,
+                                  const uint8_t *e_seeds, const uint64_t *pt, int pt_shared, uint64_t *out, size_t batch,
+                                  void *stream);
+/* PublicKey::try_encrypt (F/bfv/keys/public_key.rs:47-97): u, e1, e2 are three consecutive Poly::small draws of one
+ * ChaCha8Rng::from_seed(seeds[b]); out[b][0] = u (.) pk[0] + e1 + pt[b], out[b][1] = u (.) pk[1] + e2, all Ntt.  pk
+ * [2][L][N] must already be over ctx (the reference switches a copy of the key down to the plaintext's level:
+ * fhe_bfv_switch_to_level_dev does that once per level).  pt as fhe_bfv_encrypt_sk_dev. */
+fhe_status fhe_bfv_encrypt_pk_dev(const fhe_ctx *ctx, size_t variance, const uint64_t *pk, const uint8_t *seeds,
+                                  const uint64_t *pt, int pt_shared, uint64_t *out, size_t batch, void *stream);
 
 /* ------------------------------------------------- zq::primes (host, no GPU) ---- */
 /* generate_prime (M/zq/primes.rs:30-59): returns 0 when none exists. */

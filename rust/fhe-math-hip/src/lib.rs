@@ -10,6 +10,7 @@
 //! | [`HipMul`]         | `fhe_mul`                | `fhe::bfv::Multiplicator`          (ops/mul.rs:21-32)      |
 //! | [`HipParams`]      | `fhe_params`             | level tables of `BfvParameters`    (parameters.rs:83-117)  |
 //! | [`HipEncoder`]     | `fhe_encoder`            | encoding tables of `BfvParameters` (parameters.rs:598, 711-725) |
+//! | [`DeviceSeeds`]    | `[batch][32]` bytes      | the seeds of `Poly::small` / `random_from_seed` (encryption)   |
 //! | [`Stream`]         | `hipStream_t` (ABI-made) | --                                                         |
 //! | [`DeviceBuffer`]   | `fhe_buf_alloc` memory   | the device shadow of `Poly.coefficients: Array2<u64>`      |
 //! | [`DeviceCiphertexts`] | a `DeviceBuffer` + shape | a batch of `bfv::Ciphertext` kept on the GPU between calls |
@@ -77,6 +78,7 @@ pub mod status {
     pub const EXPANSION_UNSUPPORTED: i32 = -21;
     pub const SIMD_UNAVAILABLE: i32 = -22;
     pub const TOO_MANY_VALUES: i32 = -23;
+    pub const INVALID_VARIANCE: i32 = -24;
 }
 
 pub fn check(status: ffi::FheStatus) -> Result<()> {
@@ -906,6 +908,93 @@ impl DeviceBuffer {
 }
 impl Drop for DeviceBuffer {
     fn drop(&mut self) { unsafe { ffi::fhe_buf_free(self.ptr as *mut c_void); } }
+}
+
+/// 32-byte seeds on the device, `[batch][32]` bytes (four little-endian `u64` words each): the generators of
+/// `CtxView::{sample_small_dev, encrypt_sk_dev, encrypt_pk_dev}`.  `ChaCha8Rng::from_seed(seed)` takes the bytes as its
+/// key; the word layout is PARITY UNPINNED against a real fhe.rs run, like `fhe_poly_from_seed` (`fhe_hip.h`).
+pub struct DeviceSeeds {
+    buf: DeviceBuffer,
+    pub batch: usize,
+}
+impl DeviceSeeds {
+    pub fn upload(device: i32, seeds: &[[u8; 32]], stream: &Stream) -> Result<Self> {
+        let words: Vec<u64> = seeds
+            .iter()
+            .flat_map(|s| s.chunks_exact(8).map(|c| u64::from_le_bytes(c.try_into().unwrap())).collect::<Vec<_>>())
+            .collect();
+        let buf = DeviceBuffer::alloc_on(device, words.len().max(1), stream)?;
+        if !words.is_empty() {
+            buf.upload(&words, stream)?;
+        }
+        Ok(Self { buf, batch: seeds.len() })
+    }
+    fn as_ptr(&self) -> *const u8 { self.buf.as_ptr() as *const u8 }
+    pub fn release_on(self, stream: &Stream) -> Result<()> { self.buf.release_on(stream) }
+}
+
+/// Encryption over one level's context (F/bfv/keys/secret_key.rs, public_key.rs).  The engine clears its own scratch of
+/// samples; `s_ntt` and the output of `sample_small_dev` are the caller's to clear.
+impl CtxView<'_> {
+    /// `Poly::small(ctx, variance, ChaCha8Rng::from_seed(seed))` (rq/mod.rs:298-330) per seed -> `[batch][L][N]`,
+    /// Ntt when `to_ntt` (over the level-0 context: `SecretKey::random`'s `s_ntt`, secret_key.rs:41-46).
+    pub fn sample_small_dev(&self, variance: usize, seeds: &DeviceSeeds, to_ntt: bool, stream: &Stream) -> Result<DeviceBuffer> {
+        let out = DeviceBuffer::alloc_on(self.device(), (seeds.batch * self.poly_words()).max(1), stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_sample_small_dev(self.ptr, variance, seeds.as_ptr(), to_ntt as c_int, out.as_mut_ptr(), seeds.batch,
+                                          stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+    /// `SecretKey::encrypt_poly` (secret_key.rs:100-134) at this context's `level`: c1 = `random_from_seed(a_seeds[b])`,
+    /// c0 = `small(e_seeds[b])` - c1 s + pt.  `s_ntt`: the level-0 key (its first L rows are used); `pt`: the
+    /// Delta-scaled plaintexts (`HipEncoder::encode_dev` with `scaled`), `[rows][N]` shared or `[batch][rows][N]`, or
+    /// `None` for the zero plaintext (`PublicKey::new`).
+    pub fn encrypt_sk_dev(&self, level: usize, variance: usize, s_ntt: &DeviceBuffer, a_seeds: &DeviceSeeds,
+                          e_seeds: &DeviceSeeds, pt: Option<&DeviceBuffer>, stream: &Stream) -> Result<DeviceCiphertexts> {
+        if a_seeds.batch != e_seeds.batch {
+            return Err(shape_error("encrypt_sk_dev: as many a seeds as e seeds"));
+        }
+        if s_ntt.len() < self.poly_words() {
+            return Err(shape_error("encrypt_sk_dev: s_ntt is shorter than one polynomial over this context"));
+        }
+        let (pp, shared) = self.plain_for("encrypt_sk_dev", a_seeds.batch, pt)?;
+        let out = DeviceCiphertexts::alloc_on(self.device(), a_seeds.batch.max(1), 2, self.nmoduli(), self.degree(), level,
+                                              stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_encrypt_sk_dev(self.ptr, variance, s_ntt.as_ptr(), a_seeds.as_ptr(), e_seeds.as_ptr(), pp,
+                                        shared as c_int, out.buf.as_mut_ptr(), a_seeds.batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+    /// `PublicKey::try_encrypt` (public_key.rs:47-97): u, e1, e2 three `Poly::small` draws of
+    /// `ChaCha8Rng::from_seed(seeds[b])`; c0 = u pk0 + e1 + pt, c1 = u pk1 + e2.  `pk`: one two-part ciphertext over
+    /// this context (switched down to it with `ciphertexts_switch_to_level_dev` when the level is not 0).
+    pub fn encrypt_pk_dev(&self, variance: usize, pk: &DeviceCiphertexts, seeds: &DeviceSeeds, pt: Option<&DeviceBuffer>,
+                          stream: &Stream) -> Result<DeviceCiphertexts> {
+        if pk.batch != 1 || pk.parts != 2 || pk.rows != self.nmoduli() || pk.degree != self.degree() {
+            return Err(shape_error("encrypt_pk_dev: the public key must be one two-part ciphertext over this context"));
+        }
+        let (pp, shared) = self.plain_for("encrypt_pk_dev", seeds.batch, pt)?;
+        let out = DeviceCiphertexts::alloc_on(self.device(), seeds.batch.max(1), 2, self.nmoduli(), self.degree(), pk.level,
+                                              stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_encrypt_pk_dev(self.ptr, variance, pk.buf.as_ptr(), seeds.as_ptr(), pp, shared as c_int,
+                                        out.buf.as_mut_ptr(), seeds.batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+    /// (plaintext pointer, shared) of an encryption's optional plaintext operand for `batch` items.
+    fn plain_for(&self, what: &str, batch: usize, pt: Option<&DeviceBuffer>) -> Result<(*const u64, bool)> {
+        match pt {
+            None => Ok((ptr::null(), false)),
+            Some(p) if p.len() == self.poly_words() => Ok((p.as_ptr(), true)),
+            Some(p) => {
+                expect_len(what, p.len(), batch * self.poly_words())?;
+                Ok((p.as_ptr(), false))
+            }
+        }
+    }
 }
 
 /// A batch of `bfv::Ciphertext`s that stays on the GPU between operations: `[batch][parts][rows][N]` u64, Ntt form,
