@@ -20,19 +20,27 @@ devices are visible (a 1-GPU box) the ranks share devices and rendezvous over gl
 `--gpus N` with N > 1 measures BASELINE.json configs[3] (C4: batch 65536 over 8 GPUs = 8192 pairs per GPU) unless
 `--batch` says otherwise; N = 1 measures C2 (1024 pairs).  Each rank pins its host thread to its GPU's NUMA node.
 
+A plain run does only what the headline figure needs: setup, the W warmup steps, the timed steps, the
+`--dump-outputs` sample if asked for, and the line.  Every other leg runs only with `--full` (marked below);
+`--no-cpu`, `--no-extras`, `--cpu-seconds` and `--sustain` trim or size those legs and do nothing without it.
+
 Prints ONE JSON line on rank 0:
   value / ms_per_step   the K timed steps, single-stream mode with the library's per-launch HIP events on
                         (per-kernel durations are exact there; `roofline` comes from this region)
+  roofline              dominant kernel, HIP-event timed on the launching stream (read from the timed region: no run
+                        of its own); --full: `roofline.int_issue`, the second ceiling SURVEY 8(d) asks for --
+                        register-resident butterfly / multiply rates measured in this process (fhe_ubench_int) and
+                        every NTT-type kernel as a fraction of them
+  multi_gpu             (N > 1) who ran where; --full: efficiency against rank 0's solo rate on the same batch
+  --full only:
   event_free            the same K steps without the events (their overhead, stated rather than assumed)
   default_mode          the same K steps in the handle's default two-stream mode (kernels of the two streams
                         overlap, so per-kernel durations are not attributable there: informational)
   ntt                   forward NTT of [batch*2][4][8192] (fhe-math/benches/ntt.rs:12-38): Poly-NTT/s, row-NTT/s
   other_configs         C3 relinearise / rotations (batch 512) and C5 level-0 multiply+relin+mod-switch (batch 16)
-  roofline              dominant kernel, HIP-event timed on the launching stream; `roofline.int_issue`: the second
-                        ceiling SURVEY 8(d) asks for -- register-resident butterfly / multiply rates measured in this
-                        process (fhe_ubench_int) and every NTT-type kernel as a fraction of them
   host_api              the drop-in host-pointer entry point (fhe_bfv_mul: H2D + compute + D2H per call) at batch 1
                         and at the bench batch, and the `_dev` path on buffers / a stream owned through the C ABI
+  sustained             the same step back to back for `--sustain` seconds after the timed region
   per_rank              (N > 1) every rank's own ops/s and the max/min skew
   cpu_baseline          (N = 1) the plain-C port of the reference algorithm on this box's host cores
 
@@ -1084,14 +1092,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=0,
                     help="ciphertext pairs per GPU per step (default: 1024 = C2 with one GPU, 8192 = C4's shard with more)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip event_free / default_mode / ntt / other_configs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline figure: CPU baseline, event-free / default-mode / NTT / "
+                         "host-API legs, integer-issue roofline, other configs, sustained leg, N > 1 solo and per-rank legs")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (--full)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full without event_free / default_mode / ntt / host_api / int_issue / other_configs")
     ap.add_argument("--chunk", type=int, default=0)
     ap.add_argument("--streams", type=int, default=1,
                     help="streams of the TIMED region (1: exact per-kernel durations; 2: the handle's default mode)")
     ap.add_argument("--sustain", type=float, default=3.0,
-                    help="seconds of a sustained event-free leg after the timed region (0: none)")
+                    help="seconds of a sustained event-free leg after the timed region (--full; 0: none)")
     ap.add_argument("--spawn-check", action="store_true",
                     help="rendezvous only: start the ranks, all-reduce their ranks, print a JSON line (no GPU work)")
     ap.add_argument("--dump-outputs", metavar="DIR",
@@ -1100,6 +1112,7 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    extras_on = args.full and not args.no_extras
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -1185,13 +1198,13 @@ def main():
     # and loads the kernels' code objects -- one-time state, like the tables and the key above
     step()
     torch.cuda.synchronize()
-    # The CPU-baseline leg runs FIRST (it used to be 9 of the run's 14.6 s at the END, so a sampler that
-    # looks at the GPU every few seconds saw an idle device); its parity spot check happens after the timed region.
+    # --full: the CPU-baseline leg runs FIRST (it used to be 9 of the run's 14.6 s at the END, so a sampler
+    # that looks at the GPU every few seconds saw an idle device); its parity spot check happens after the timed region.
     cpu_leg, cpu_default128 = None, None
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         os.sched_setaffinity(0, all_cpus)   # the CPU baseline gets every host core, not just the GPU's NUMA node
         cpu_leg = cpu_baseline(n, MODULI_SIZES, t, SEED, args.cpu_seconds)
-        if not args.no_extras:
+        if extras_on:
             # the reference's own Criterion IDs on its stock parameter sets, one host thread (part of the CPU leg: the
             # only other place this file touches oracle/)
             import ref_params
@@ -1201,12 +1214,12 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    # N > 1: rank 0's rate on the SAME per-GPU batch while every other rank idles at a barrier -- the one-GPU
-    # reference the scaling efficiency of this very run is computed against, and who is who
+    # N > 1: who is who, and with --full rank 0's rate on the SAME per-GPU batch while every other rank idles at a
+    # barrier -- the one-GPU reference the scaling efficiency of this very run is computed against
     solo_rate, identities, n1_reference = None, None, None
     if dist is not None:
         dist.barrier()
-        if rank == 0:
+        if rank == 0 and args.full:
             t0 = time.perf_counter()
             for _ in range(args.steps):
                 step()
@@ -1260,7 +1273,7 @@ def main():
     prof_steps = args.steps * REPEATS    # the per-kernel event sums cover every repeat
     # every rank's own elapsed time for the same K steps (its barrier-to-barrier time is the slowest rank's)
     per_rank = None
-    if dist is not None:
+    if dist is not None and args.full:
         t0 = time.perf_counter()
         for _ in range(args.steps):
             step()
@@ -1278,7 +1291,7 @@ def main():
     # for a utilisation sampler that looks every few seconds -- this keeps the device busy with the same step for
     # `--sustain` seconds and reports the rate it held (`gpu_busy` saw 0 of 3 samples).
     sustained = None
-    if args.sustain > 0:
+    if args.full and args.sustain > 0:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         n_sus = 0
@@ -1294,7 +1307,7 @@ def main():
                          note="same step, library profiler off, back to back; this rank only")
 
     extras = {}
-    if not args.no_extras:
+    if extras_on:
         # (1) the same K steps without the per-launch events
         e1 = timed(step, args.steps)
         extras["event_free"] = dict(value=round(world * batch * args.steps / e1, 1), unit="ops/s",
@@ -1409,7 +1422,7 @@ def main():
                                   frac=round(stage_model_rows(L, K, L) * R * value / world / 1e9 / HBM_PEAK_GBS, 4)),
                     kernels=per_kernel, kernel_is="dominant FAMILY (instances of one kernel template summed)",
                     dominant_by_symbol=dominant_by_symbol, by_symbol=by_symbol)
-    if not args.no_extras:
+    if extras_on:
         roofline["int_issue"] = int_issue_roofline(fhe, dev, prof, n, L, K, batch, prof_steps, pipeline_step=step,
                                                    sync=torch.cuda.synchronize, par=par, value_per_gpu=value / world,
                                                    stage_bytes=stage_model_rows(L, K, L) * R)
@@ -1444,10 +1457,11 @@ def main():
         distinct = len({(i["pci"], i["uuid"]) for i in identities})
         result["multi_gpu"] = dict(
             rccl_world_size=world if backend == "nccl" else None, dist_backend=backend, ranks=identities,
-            distinct_devices=distinct, one_device_per_rank=bool(distinct == world),
-            solo_rank0_ops_per_s=round(solo_rate, 1), solo_note="rank 0, same per-GPU batch, all other ranks idle at a barrier",
-            efficiency_vs_1gpu_same_batch=round(value / (world * solo_rate), 4),
-            n1_reference=n1_reference, data_path_collectives=0)
+            distinct_devices=distinct, one_device_per_rank=bool(distinct == world), data_path_collectives=0)
+        if solo_rate is not None:
+            result["multi_gpu"].update(
+                solo_rank0_ops_per_s=round(solo_rate, 1), solo_note="rank 0, same per-GPU batch, all other ranks idle at a barrier",
+                efficiency_vs_1gpu_same_batch=round(value / (world * solo_rate), 4), n1_reference=n1_reference)
 
     if cpu_leg is not None:
         cb, cm, (clhs, crhs, last, count, npairs) = cpu_leg
@@ -1463,7 +1477,7 @@ def main():
         assert np.array_equal(out[i].cpu().numpy().view(np.uint64), last), "GPU result differs from the oracle"
         result["parity_spot_check"] = f"ciphertext {i} bit-identical to the oracle"
 
-    if world == 1 and not args.no_extras:
+    if world == 1 and extras_on:
         del lhs, rhs, out, mul
         other = result["other_configs"] = {}
 

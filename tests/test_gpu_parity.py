@@ -328,16 +328,16 @@ def _bench_lines(stdout):
 
 
 def test_bench_record_is_compact():
-    """the default-flags shape of the command the driver runs (extras ON, CPU leg ON), at a small step
-    count: the last stdout line parses, is below 2,000 characters and carries `roofline`, `cpu_baseline`, `ntt` and the
-    other configs' binding ceilings; the full result is in the DETAIL line and in bench_detail.json."""
+    """the `--full` shape of the command (extras ON, CPU leg ON), at a small step count: the last
+    stdout line parses, is below 2,000 characters and carries `roofline`, `cpu_baseline`, `ntt` and the other configs'
+    binding ceilings; the full result is in the DETAIL line and in bench_detail.json."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-seconds", "2"],
-                       capture_output=True, text=True, timeout=1500)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--full",
+                        "--cpu-seconds", "2"], capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     rec, det = _bench_lines(r.stdout)
     assert rec["n_gpus"] == 1 and rec["config"]["workload"].startswith("C2:") and rec["config"]["batch_per_gpu"] == 1024
@@ -364,16 +364,42 @@ def test_bench_record_is_compact():
     assert on_disk["value"] == rec["value"] and "other_configs" in on_disk
 
 
+def test_bench_plain_run_is_lean(tmp_path):
+    """Without `--full` the run does only what the headline figure needs: the record carries the contract's keys and the
+    roofline read from the timed region's events, `--dump-outputs` still writes its sample, and none of the other legs
+    (CPU baseline, extras, integer-issue ceilings, other configs, sustained leg) has run."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    rec, det = _bench_lines(r.stdout)
+    assert rec["n_gpus"] == 1 and rec["steps"] == 2 and rec["warmup"] == 1 and rec["unit"] == "ops/s" and rec["value"] > 0
+    assert rec["config"]["workload"].startswith("C2:") and rec["config"]["batch_per_gpu"] == 1024
+    assert abs(rec["value"] * rec["ms_per_step"] / 1e3 / 1024 - 1) < 2e-3
+    rf = det["roofline"]
+    assert rf["kernel_sum_le_step"] is True and rf["by_symbol"] and "int_issue" not in rf
+    for k in ("cpu_baseline", "parity_spot_check", "event_free", "default_mode", "ntt", "host_api", "other_configs",
+              "binding_ceilings", "sustained", "per_rank", "multi_gpu", "errors"):
+        assert k not in det, k
+    assert det["dump_outputs"]["files"] == ["product_hi32.npy", "product_index.npy", "product_lo32.npy"]
+    for f in det["dump_outputs"]["files"]:
+        assert (tmp_path / "out" / f).stat().st_size > 0
+
+
 def test_bench_two_ranks_on_one_gpu():
     """`python bench.py --gpus 2` starts its own two ranks; on a one-GPU box they share the device and
-    rendezvous over gloo (RCCL needs one device per rank).  The line must say n_gpus = 2."""
+    rendezvous over gloo (RCCL needs one device per rank).  The line must say n_gpus = 2; `--full` adds the solo leg
+    the efficiency block is computed from."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch", "128", "--no-cpu", "--no-extras"], capture_output=True, text=True, timeout=600)
+                        "--batch", "128", "--full", "--no-cpu", "--no-extras"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     rec, line = _bench_lines(r.stdout)
     assert rec["n_gpus"] == 2 and rec["multi_gpu"]["data_path_collectives"] == 0 and "efficiency_vs_1gpu_same_batch" in rec["multi_gpu"]
@@ -408,7 +434,8 @@ def test_bench_eight_ranks_on_one_gpu():
                     f"{SHARED_GPU_PROCESS_LIMIT}")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-                        "--batch", "32", "--no-cpu", "--no-extras", "--sustain", "0.2"], capture_output=True, text=True, timeout=900)
+                        "--batch", "32", "--full", "--no-cpu", "--no-extras", "--sustain", "0.2"], capture_output=True, text=True,
+                       timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     rec, line = _bench_lines(r.stdout)
     # the compact record of an N > 1 run (what SCALE_rNN.json keeps): world size, who ran where in summary, the one-GPU reference

@@ -20,7 +20,7 @@ res["_ratio_mac_f64_over_int"] = res["f64_mac"] / res["shoup_mac"]
 res["_ratio_mulmod_f64_over_shoup"] = res["f64_mulmod"] / res["shoup_lazy"]
 print(json.dumps(res, indent=1))
 PY
-python bench.py > $OUT/bench_default.out 2> $OUT/bench_default.err
+python bench.py --full > $OUT/bench_default.out 2> $OUT/bench_default.err
 cp bench_detail.json $OUT/bench_detail_default.json 2>/dev/null
 tail -c 2000 $OUT/bench_default.out > $OUT/bench_default_tail2000.txt
 timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1

@@ -6,7 +6,7 @@ mkdir -p $OUT
 cd $ROOT
 timeout 1800 python -m pytest tests -m gpu -q > $OUT/pytest_gpu.log 2>&1; tail -3 $OUT/pytest_gpu.log
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log
-python bench.py > $OUT/bench_default.out 2> $OUT/bench_default.err; tail -1 $OUT/bench_default.out | cut -c1-1900
+python bench.py --full > $OUT/bench_default.out 2> $OUT/bench_default.err; tail -1 $OUT/bench_default.out | cut -c1-1900
 bash tools/collect_profiles.sh r06_final4/prof 20 > $OUT/collect.log 2>&1
 tail -1 $OUT/prof/bench.json | cut -c1-300
 AB_REPS=3 timeout 900 python tools/f64_ab.py > $OUT/f64_ab_v3.jsonl 2> $OUT/f64_ab_v3.err

@@ -27,5 +27,5 @@ for k in rows[0]["t"]:
 print({k: len({r["t"][k] for r in rows}) for k in rows[0]["t"] if k.endswith("digest")})
 PY
 timeout 600 python -m pytest tests -m gpu -q -k "stream or workspace or trim" > $OUT/pytest_streams.log 2>&1; tail -2 $OUT/pytest_streams.log
-python bench.py > $OUT/bench_default.out 2>$OUT/bench_default.err; tail -1 $OUT/bench_default.out | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['configs'])"
+python bench.py --full > $OUT/bench_default.out 2>$OUT/bench_default.err; tail -1 $OUT/bench_default.out | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['configs'])"
 grep '^DETAIL ' $OUT/bench_default.out | sed 's/^DETAIL //' | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('default_mode', d.get('default_mode',{}).get('value'), 'event_free', d.get('event_free',{}).get('value'))"

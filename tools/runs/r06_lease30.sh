@@ -5,8 +5,8 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/r06_zz
 mkdir -p $OUT
 cd $ROOT
-timeout 600 python bench.py --gpus 2 --steps 5 --warmup 2 --batch 1024 > $OUT/bench_gpus2_spawn.out 2> $OUT/bench_gpus2_spawn.err; tail -1 $OUT/bench_gpus2_spawn.out | cut -c1-1900
-timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 --batch 1024 > $OUT/bench_gpus2_torchrun.out 2> $OUT/bench_gpus2_torchrun.err; tail -1 $OUT/bench_gpus2_torchrun.out | cut -c1-1900
+timeout 600 python bench.py --gpus 2 --steps 5 --warmup 2 --batch 1024 --full > $OUT/bench_gpus2_spawn.out 2> $OUT/bench_gpus2_spawn.err; tail -1 $OUT/bench_gpus2_spawn.out | cut -c1-1900
+timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 --batch 1024 --full > $OUT/bench_gpus2_torchrun.out 2> $OUT/bench_gpus2_torchrun.err; tail -1 $OUT/bench_gpus2_torchrun.out | cut -c1-1900
 run() { python tests/random_sweep_gpu.py "$@" 2>/dev/null | tee -a $OUT/random_sweeps.jsonl | cut -c1-220; }
 run ${SWEEP_S:-240} 40000000 41000000 0 -
 run ${SWEEP_S:-240} 41000000 42000000 0 f64
