@@ -151,6 +151,11 @@ SIGNATURES = {
     "fhe_bfv_sample_small_dev": (i32, [vp, sz, vp, i32, vp, sz, vp]),
     "fhe_bfv_encrypt_sk_dev": (i32, [vp, sz, vp, vp, vp, vp, i32, vp, sz, vp]),
     "fhe_bfv_encrypt_pk_dev": (i32, [vp, sz, vp, vp, vp, i32, vp, sz, vp]),
+    "fhe_ksk_generate_dev": (i32, [vp, vp, sz, vp, vp, vp, sz, vp, vp, vp]),
+    "fhe_bfv_relin_key_generate_dev": (i32, [vp, vp, sz, vp, vp, vp, vp, vp]),
+    "fhe_bfv_galois_keys_generate_dev": (i32, [vp, vp, sz, vp, vp, vp, sz, vp, vp, vp]),
+    "fhe_ksk_export_dev": (i32, [vp, vp, vp, vp, vp, vp]),
+    "fhe_ksk_ndigits": (sz, [vp]),
     "fhe_generate_prime": (u64, [sz, u64, u64]),
     "fhe_supports_opt": (i32, [u64]),
     "fhe_is_prime": (i32, [u64]),

@@ -704,6 +704,61 @@ class KeySwitchingKey:
                 _tls.ks_forced_mode = old
         return cm()
 
+    @classmethod
+    def _adopt(cls, ctx_ciphertext, ctx_ksk, handle, seeds, index):
+        """A handle made by one of the generation entry points; `seeds[index]` is its public seed K (device)."""
+        self = cls.__new__(cls)
+        self.ctx_ciphertext, self.ctx_ksk = ctx_ciphertext, ctx_ksk
+        self._h = C.c_void_p(handle)
+        _, self.log_base = _ksk_digits(ctx_ciphertext, ctx_ksk)
+        self.ndigits = _lib.lib().fhe_ksk_ndigits(self._h)   # (export sizes its arrays from the engine's count)
+        self._seeds, self._seed_index = seeds, index
+        forced = getattr(_tls, "ks_forced_mode", (0, 0))
+        if forced != (0, 0):
+            self.set_mode(*forced)
+        return self
+
+    @property
+    def seed(self):
+        """The key's public seed K (32 bytes) when it was generated on the device (KeySwitchingKey::new's `seed`),
+        else None."""
+        sd = getattr(self, "_seeds", None)
+        if sd is None:
+            return None
+        row = sd[self._seed_index]
+        return bytes(row.download() if isinstance(row, DeviceArray) else row.cpu().numpy())
+
+    @classmethod
+    def generate(cls, sk, from_ntt, ciphertext_level=0, ksk_level=0, seed=None):
+        """KeySwitchingKey::new (key_switching_key.rs:71-236) on the device with rng = ChaCha8Rng::from_seed(seed):
+        from_ntt [Lk, N] (one key) or [nkeys, Lk, N] is the reference's `from` in Ntt form over the key context (a
+        device array; numpy is staged and cleared again), canonical residues (row j below q_j: not checked on the
+        device, a larger word gives a key that is not canonical); seed: 32 bytes, or one per key (None: from `secrets`).
+        Returns one key, or a list for a batch (fhe_ksk_generate_dev)."""
+        L = _lib.lib()
+        one = len(from_ntt.shape) == 2
+        count = 1 if one else int(from_ntt.shape[0])
+        staged = []
+        try:
+            f = from_ntt
+            if not _is_dev(f):
+                f = DeviceArray.from_numpy(_np(f), max(sk.params.device, 0))
+                staged.append(f)
+            keys = _keygen(sk, ciphertext_level, ksk_level, count, seed, lambda ct, kc, sd, ko, hs: (
+                L.fhe_ksk_generate_dev(ct._h, kc._h, sk.params.variance, _dptr(sk.s_ntt), _dptr(f), _dptr8(sd), count,
+                                       _dptr8(ko), _stream(), hs)))
+        finally:
+            _wipe(staged)
+        return keys[0] if one else keys
+
+    def export(self):
+        """(c0, c1, c0_shoup, c1_shoup), each [ndigits, Lk, N] on the device (fhe_ksk_export_dev): what a client sends
+        to the server; `KeySwitchingKey(ctx_ct, ctx_ksk, c0, c1, ...)` of them is an equal key."""
+        shape = (self.ndigits, self.ctx_ksk.nmoduli, self.ctx_ksk.degree)
+        out = [_alloc(shape, self.ctx_ksk.device) for _ in range(4)]
+        check(_lib.lib().fhe_ksk_export_dev(self._h, *[_dptr(x) for x in out], _stream()))
+        return tuple(out)
+
     def __del__(self):
         if getattr(self, "_h", None) is not None and _lib._lib is not None:
             _lib._lib.fhe_ksk_destroy(self._h)
@@ -745,6 +800,15 @@ class RelinearizationKey:
             raise FheError(-17, "KeySwitchingNotSupported")
         self.ksk = ksk
 
+    @classmethod
+    def generate(cls, sk, seed=None, ciphertext_level=0, key_level=0):
+        """RelinearizationKey::new_leveled (relinearization_key.rs:43-64) on the device with
+        rng = ChaCha8Rng::from_seed(seed) (32 bytes; None: from `secrets`): fhe_bfv_relin_key_generate_dev."""
+        L = _lib.lib()
+        return cls(_keygen(sk, ciphertext_level, key_level, 1, seed, lambda ct, kc, sd, ko, hs: (
+            L.fhe_bfv_relin_key_generate_dev(ct._h, kc._h, sk.params.variance, _dptr(sk.s_ntt), _dptr8(sd), _dptr8(ko),
+                                             _stream(), hs)))[0])
+
     def relinearizes(self, ct3):
         """[..., 3, L, N] Ntt -> [..., 2, L, N] Ntt."""
         L = _lib.lib()
@@ -772,6 +836,21 @@ class GaloisKey:
             raise FheError(-10, "InvalidSubstitutionExponent")
         self.ksk, self.exponent = ksk, exponent % (2 * n)
 
+    @classmethod
+    def generate(cls, sk, exponents, seeds=None, ciphertext_level=0, key_level=0):
+        """GaloisKey::new (galois_key.rs:26-58) for every exponent in one batched device call
+        (fhe_bfv_galois_keys_generate_dev), key b with rng = ChaCha8Rng::from_seed(seeds[b]) (None: from `secrets`).
+        Returns a list of keys in the order of `exponents`."""
+        exps = [int(e) for e in exponents]
+        if not exps:
+            return []
+        L = _lib.lib()
+        arr = (C.c_size_t * len(exps))(*exps)
+        keys = _keygen(sk, ciphertext_level, key_level, len(exps), seeds, lambda ct, kc, sd, ko, hs: (
+            L.fhe_bfv_galois_keys_generate_dev(ct._h, kc._h, sk.params.variance, _dptr(sk.s_ntt), arr, _dptr8(sd),
+                                               len(exps), _dptr8(ko), _stream(), hs)))
+        return [cls(k, e) for k, e in zip(keys, exps)]
+
     def relinearize(self, ct):
         """[..., 2, L, N] Ntt -> same shape."""
         L = _lib.lib()
@@ -796,6 +875,37 @@ class EvaluationKey:
     def __init__(self, degree, galois_keys):
         self.degree = degree
         self.gk = {g.exponent: g for g in galois_keys}
+
+    @staticmethod
+    def exponents(degree, column_rotations=(), row_rotation=False, inner_sum=False, expansion_level=0):
+        """The Galois exponents EvaluationKeyBuilder::build generates keys for (evaluation_key.rs:429-489), sorted."""
+        n = degree
+        idx = set()
+        for i in column_rotations:
+            if not 1 <= i < n // 2:
+                raise FheError(-1, "InvalidRotationStep: %d not in [1, %d]" % (i, n // 2 - 1))
+            idx.add(pow(3, i, 2 * n))
+        if row_rotation or inner_sum:
+            idx.add(2 * n - 1)
+        if inner_sum:
+            i = 1
+            while i < n // 2:
+                idx.add(pow(3, i, 2 * n))
+                i *= 2
+        if not 0 <= expansion_level <= n.bit_length() - 1:
+            raise FheError(-12, "InvalidLevel: the expansion level is at most log2(N)")
+        for l in range(expansion_level):
+            idx.add((n >> l) + 1)
+        return sorted(idx)
+
+    @classmethod
+    def generate(cls, sk, column_rotations=(), row_rotation=False, inner_sum=False, expansion_level=0, seeds=None,
+                 ciphertext_level=0, key_level=0):
+        """EvaluationKeyBuilder (evaluation_key.rs:345-489) on the device: the builder's Galois exponents, sorted, one
+        seed per exponent (None: from `secrets`), in one batched call.  (The reference draws its keys from one rng in
+        HashSet order; here each key has its own seed.)"""
+        exps = cls.exponents(sk.params.degree, column_rotations, row_rotation, inner_sum, expansion_level)
+        return cls(sk.params.degree, GaloisKey.generate(sk, exps, seeds, ciphertext_level, key_level))
 
     def rotates_rows(self, ct):
         e = 2 * self.degree - 1
@@ -1021,6 +1131,37 @@ def _batch_of(pt, count):
         return ((count,) if count != 1 or pt is None else ()), count, 1
     lead = tuple(int(d) for d in pt.shape[:-2])
     return lead, int(np.prod(lead)), 0
+
+
+def _ksk_digits(ct, kc):
+    """(ndigits, log_base) of a key from `ct`'s level to `kc`'s (key_switching_key.rs:97-136)."""
+    if kc.nmoduli == 1:
+        lm = (kc.moduli[0] - 1).bit_length()
+        return -(-lm // (lm // 2)), lm // 2
+    return ct.nmoduli, 0
+
+
+def _keygen(sk, ciphertext_level, key_level, count, seeds, call):
+    """The shared body of the key-generation wrappers: the two contexts, one seed per key (host seeds are staged and
+    cleared again), a device array for the public seeds and call(ct, kc, seeds, seeds_out, handles) -> status."""
+    par = sk.params
+    for lvl in (ciphertext_level, key_level):
+        if not 0 <= lvl <= par.max_level:
+            raise FheError(-12, "InvalidLevel")
+    ct, kc = par.context_at_level(ciphertext_level), par.context_at_level(key_level)
+    staged = []
+    try:
+        sd, n, own = _seeds(seeds, count, par.device)
+        if own:
+            staged.append(sd)
+        if n != count:
+            raise FheError(-1, "one seed per key: %d keys, %d seeds" % (count, n))
+        kout = _alloc((count, 32), par.device, itemsize=1)
+        hs = (C.c_void_p * count)()
+        check(call(ct, kc, sd, kout, hs))
+    finally:
+        _wipe(staged)
+    return [KeySwitchingKey._adopt(ct, kc, hs[i], kout, i) for i in range(count)]
 
 
 class SecretKey:

@@ -1448,12 +1448,20 @@ struct Ksk {
 };
 enum : int { KS_AUTO = 0, KS_FUSED = 1, KS_UNFUSED = 2, KS_UNFUSED_SUB = 3, KS_FUSED_SUB = 4 };
 
+// Does a key over `kc` with these digits carry the F64 words (c0f, c1f)?  RNS digits, the device's F64 tables, and every
+// key modulus below 2^50 (so that a canonical key word is an exact double).  Used by the host path (ksk_fill_f64) and
+// by device generation (ksk_generate) alike.
+inline bool ksk_f64_eligible(const Ctx &kc, size_t log_base) {
+    if (log_base != 0 || kc.device < 0 || !kc.root->d_tw_f.p) return false;
+    for (u64 q : kc.moduli)
+        if (q >> 50) return false;
+    return true;
+}
+
 // host key words [ndigits][Lk][N] (canonical, checked by the caller) -> the F64 twins on the device
 inline void ksk_fill_f64(Ksk &k_, const u64 *h0, const u64 *h1) {
     const Ctx &kc = *k_.ksk_ctx;
-    if (k_.log_base != 0 || kc.device < 0 || !kc.root->d_tw_f.p) return;
-    for (u64 q : kc.moduli)
-        if (q >> 50) return;
+    if (!ksk_f64_eligible(kc, k_.log_base)) return;
     const size_t count = k_.ndigits * kc.L * kc.n;
     std::vector<u64> f(count);
     auto fill = [&](const u64 *h, DevBuf<u64> &df) {
@@ -1484,6 +1492,19 @@ inline void ksk_validate(const Ctx &ct_ctx, const Ctx &ksk_ctx, size_t ndigits, 
         require(ndigits == ct_ctx.L, E_PARAMETER_MISMATCH, "ndigits must equal the ciphertext context's moduli count");
         require(ksk_ctx.L >= 2, E_KEYSWITCH_UNSUPPORTED, "KeySwitchingNotSupported: single-modulus key without log_base");
     }
+}
+
+// A key handle with its geometry checked and no arrays yet (fhe_ksk_create fills them from the host, ksk_generate on
+// the device).
+inline std::unique_ptr<Ksk> make_ksk(const Ctx &ct, const Ctx &kc, size_t ndigits, size_t log_base) {
+    ksk_validate(ct, kc, ndigits, log_base);
+    kc.need_device();
+    auto k_ = std::make_unique<Ksk>();
+    k_->ct_ctx = &ct;
+    k_->ksk_ctx = &kc;
+    k_->ndigits = ndigits;
+    k_->log_base = log_base;
+    return k_;
 }
 
 template <int LOGN>
@@ -2932,12 +2953,17 @@ inline void check_variance(size_t variance) {
     require(variance >= 1 && variance <= 32, E_INVALID_VARIANCE, "InvalidVariance: the variance must be in [1, 32]");
 }
 
+// next_u64 words one sample_vec_cbd draw of n samples consumes (each draw starts at a word boundary)
+inline u64 cbd_words_per_draw(size_t variance, u64 n) {
+    return variance <= 16 ? (n * 4 * variance + 63) / 64 : 2 * n;
+}
+
 // sample_vec_cbd draws of ChaCha8Rng::from_seed(seeds[b]): `kdraws` consecutive draws of N = 2^logn samples ->
 // smp [batch][kdraws N]
 inline void cbd_sample(const uint8_t *seeds, size_t variance, size_t logn, size_t kdraws, int8_t *smp, size_t batch,
                        hipStream_t s) {
     const u64 n = 1ull << logn, ns = (u64)kdraws * n;
-    const u64 wpd = variance <= 16 ? ((u64)n * 4 * variance + 63) / 64 : 2 * (u64)n;   // next_u64 words per draw
+    const u64 wpd = cbd_words_per_draw(variance, n);
     FHE_LAUNCH("cbd_sample", k::cbd_sample_kernel, dim3(blocks_for(ns, k::CBD_THREADS), (unsigned)batch),
                dim3(k::CBD_THREADS), k::CBD_SMEM_BYTES, s, seeds, smp, (uint32_t)variance, ns, (uint32_t)logn, wpd);
 }
@@ -3058,6 +3084,152 @@ inline void encrypt_pk(const Ctx &c, size_t variance, const u64 *pk, const uint8
                    0, s, (const u64 *)x.u(), (const u64 *)nullptr, pk, ptb, pt_shared ? (u64)0 : PL, outb, (uint32_t)c.L,
                    c.dmods(), (uint32_t)c.logn, 1u, total);
     }
+}
+
+// ------------------------------------------------------------------ key generation ----
+// KeySwitchingKey::new's digits over the key context (F/bfv/keys/key_switching_key.rs:97-136): RNS digits, one per
+// ciphertext modulus, or for a single-modulus key context the decomposition in base 2^log_base with
+// log_base = log_modulus / 2, log_modulus = q.next_power_of_two().ilog2().  -> (ndigits, log_base)
+inline std::pair<size_t, size_t> ksk_digits(const Ctx &ct, const Ctx &kc) {
+    if (kc.L == 1) {
+        const size_t log_modulus = 64 - __builtin_clzll(kc.moduli[0] - 1);
+        const size_t lb = log_modulus / 2;
+        return {(log_modulus + lb - 1) / lb, lb};
+    }
+    return {ct.L, 0};
+}
+
+// KeySwitchingKey::new (F/bfv/keys/key_switching_key.rs:71-236) for `nkeys` keys, key b with
+// rng = ChaCha8Rng::from_seed(seeds[b]): K = the rng's first 32 bytes (written to seeds_out[b] when given),
+// c1[i] = Poly::random_from_seed(ctx_ksk, bytes [32 i, 32 i + 32) of ChaCha8Rng::from_seed(K)), e_i = the rng's i-th
+// Poly::small draw (from u64 word 4 on), c0[i] = NTT(e_i) - c1[i] (.) s + g_i (.) from[b].  s_ntt: the level-0 secret
+// in Ntt form (its first Lk rows are read); from_ntt [nkeys][Lk][N] Ntt over the key context.  The handles are ready to
+// use on `s`: no host synchronisation, and no key word passes through host memory.  The sampler, the seed expansion
+// and the combine stage are one launch each per group of up to KG_KEYS keys.
+inline std::vector<std::unique_ptr<Ksk>> ksk_generate(const Ctx &ct, const Ctx &kc, size_t variance, const u64 *s_ntt,
+                                                      const u64 *from_ntt, const uint8_t *seeds, size_t nkeys,
+                                                      uint8_t *seeds_out, hipStream_t s) {
+    kc.need_device();
+    check_variance(variance);
+    const auto dg = ksk_digits(ct, kc);
+    const size_t nd = dg.first, lb = dg.second, Lk = kc.L, N = kc.n;
+    ksk_validate(ct, kc, nd, lb);
+    std::vector<std::unique_ptr<Ksk>> keys;
+    if (!nkeys) return keys;
+    const u64 PK = (u64)nd * Lk * N;   // words of one key array
+    const bool wf = ksk_f64_eligible(kc, lb);
+    for (size_t b = 0; b < nkeys; b++) {
+        auto k_ = make_ksk(ct, kc, nd, lb);
+        for (DevBuf<u64> *d : {&k_->c0, &k_->c0s, &k_->c1, &k_->c1s}) d->alloc(PK);
+        if (wf) {
+            k_->c0f.alloc(PK);
+            k_->c1f.alloc(PK);
+        }
+        keys.push_back(std::move(k_));
+    }
+    // the public constants: rq [Lk] {2^64 mod q_j, q_j^-1}, then g [nd][Lk]
+    WsGuard cst((2 * Lk + nd * Lk) * sizeof(u64), s);
+    k::u64x2 *rq = (k::u64x2 *)cst.p;
+    u64 *g = cst.u() + 2 * Lk;
+    FHE_LAUNCH("ksk_consts", k::ksk_consts_kernel, dim3(blocks_for(nd * Lk, 64)), dim3(64), 0, s, kc.dmods(),
+               (uint32_t)nd, (uint32_t)Lk, (uint32_t)lb, g, rq);
+    const bool whole = kc.logn <= 14;
+    const bool f64_on = !f64_disabled();   // (read once per call: every transform of the call takes the same kind)
+    const int hr = whole ? f64_rows(kc, 0, Lk, f64_on) : 0;
+    const u64 wpd = cbd_words_per_draw(variance, N);
+    // groups: at most KG_KEYS keys (the output table travels in the kernel arguments) and 1 GiB of c1 scratch (256 MiB
+    // of c1 and transformed errors for larger rows), split into groups of equal size
+    const size_t per = PK * sizeof(u64) * (whole ? 1 : 2), budget = whole ? (size_t)1 << 30 : (size_t)256 << 20;
+    const size_t most = std::max<size_t>(1, std::min<size_t>(k::KG_KEYS, budget / per));
+    const size_t groups = (nkeys + most - 1) / most, group = (nkeys + groups - 1) / groups;
+    require(group * nd * Lk <= 0x7fffffffu, E_ARG, "ksk_generate: a launch group exceeds the grid limit");
+    for (size_t b0 = 0; b0 < nkeys; b0 += group) {
+        const size_t nb = std::min(group, nkeys - b0);
+        k::KskOutTable tab{};
+        for (size_t b = 0; b < nb; b++) {
+            const Ksk &kk = *keys[b0 + b];
+            tab.k[b] = k::KskOut{kk.c0.p, kk.c0s.p, kk.c1.p, kk.c1s.p, kk.c0f.p, kk.c1f.p};
+        }
+        WsGuard ds(nb * nd * 32, s), c1(nb * PK * sizeof(u64), s);
+        WsGuard smp(small_bytes(nb * nd * N), s, true);   // the errors: secrets, cleared before they return to the pool
+        int8_t *sp = (int8_t *)smp.p;
+        const uint8_t *sd = seeds + b0 * 32;
+        FHE_LAUNCH("ksk_seeds", k::ksk_seeds_kernel, dim3(blocks_for(nb * nd, 64)), dim3(64), 0, s, sd,
+                   seeds_out ? seeds_out + b0 * 32 : nullptr, (uint8_t *)ds.p, (uint32_t)nd, (uint32_t)(nb * nd));
+        const u64 ns = (u64)nd * N;
+        FHE_LAUNCH("cbd_sample_at", k::cbd_sample_at_kernel, dim3(blocks_for(ns, k::CBD_THREADS), (unsigned)nb),
+                   dim3(k::CBD_THREADS), k::CBD_AT_SMEM_BYTES, s, sd, sp, (uint32_t)variance, ns, (uint32_t)kc.logn, wpd,
+                   (u64)4);
+        polys_from_seeds(kc, (const uint8_t *)ds.p, c1.u(), nb * nd, s);
+        const u64 *fb = from_ntt + b0 * Lk * N;
+        if (whole) {
+            FHE_ENC_SWITCH(ksk_gen_kernel, kc.logn, all_below_2p60(kc), hr, "ksk_gen", nb * nd * Lk, s, (const int8_t *)sp,
+                           (const u64 *)c1.u(), s_ntt, fb, (const u64 *)g, (const k::u64x2 *)rq, tab, (uint32_t)nd,
+                           (uint32_t)Lk, (uint32_t)wf, kc.dmods(), hr > 0 ? kc.dtw_f() : kc.dtw());
+            continue;
+        }
+        // rows larger than one LDS tile: lift, launch_ntt, then the epilogue as a pass of its own
+        WsGuard x(nb * PK * sizeof(u64), s, true);
+        const u64 total = (u64)nb * PK;
+        FHE_LAUNCH("small_lift", k::small_lift_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
+                   (const int8_t *)sp, x.u(), (uint32_t)Lk, kc.dmods(), (uint32_t)kc.logn, total);
+        launch_ntt(kc, false, x.u(), x.u(), full_map(kc, Lk), nb * nd, s);
+        FHE_LAUNCH("ksk_combine", k::ksk_combine_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
+                   (const u64 *)x.u(), (const u64 *)c1.u(), s_ntt, fb, (const u64 *)g, (const k::u64x2 *)rq, tab,
+                   (uint32_t)nd, (uint32_t)Lk, (uint32_t)wf, kc.dmods(), (uint32_t)kc.logn, total);
+    }
+    return keys;
+}
+
+// Switcher(ctx_ct -> ctx_key) on Ntt rows (the switch-up of RelinearizationKey / GaloisKey::new when the key level is
+// below the ciphertext level): in [np][ct.L][N] Ntt -> out [np][kc.L][N] Ntt, through a wiped PowerBasis scratch.  The
+// switcher's tables are built on the host (public constants, as fhe_switcher_create); the call waits for the stream
+// before they are freed.
+inline void switch_up_ntt(const Ctx &ct, const Ctx &kc, const u64 *in, u64 *out, size_t np, hipStream_t s) {
+    RnsContext rf(ct.moduli), rt(kc.moduli);
+    auto sc = scaler_create(ct, kc, rt.product, rf.product);
+    {
+        WsGuard pb(np * ct.L * ct.n * sizeof(u64), s, true);
+        launch_ntt(ct, true, in, pb.u(), full_map(ct, ct.L), np, s);
+        launch_scale(*sc, pb.u(), (u64)ct.L * ct.n, out, (u64)kc.L * kc.n, np, s);
+        launch_ntt(kc, false, out, out, full_map(kc, kc.L), np, s);
+    }
+    FHE_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// RelinearizationKey::new_leveled's `from` (F/bfv/keys/relinearization_key.rs:43-64): Switcher(ctx_ct -> ctx_key)
+// applied to s_ct (.) s_ct, in Ntt form over the key context: out [kc.L][N].  s_ntt: the level-0 secret.
+inline void relin_from(const Ctx &ct, const Ctx &kc, const u64 *s_ntt, u64 *out, hipStream_t s) {
+    const size_t bytes = ct.L * ct.n * sizeof(u64);
+    if (kc.L == ct.L) {
+        FHE_HIP_CHECK(hipMemcpyAsync(out, s_ntt, bytes, hipMemcpyDeviceToDevice, s));
+        ew_op(ct, out, s_ntt, 1, k::EW_MUL, s);
+        return;
+    }
+    WsGuard t(bytes, s, true);
+    FHE_HIP_CHECK(hipMemcpyAsync(t.p, s_ntt, bytes, hipMemcpyDeviceToDevice, s));
+    ew_op(ct, t.u(), s_ntt, 1, k::EW_MUL, s);
+    switch_up_ntt(ct, kc, t.u(), out, 1, s);
+}
+
+// GaloisKey::new's `from` (F/bfv/keys/galois_key.rs:26-58) for a batch of exponents: Switcher(ctx_ct -> ctx_key) of
+// substitute(s_ct, exponents[b]), Ntt over the key context: out [nkeys][kc.L][N].  Exponents must be odd mod 2N
+// (checked by the caller).
+inline void galois_from(const Ctx &ct, const Ctx &kc, const u64 *s_ntt, const size_t *exponents, size_t nkeys, u64 *out,
+                        hipStream_t s) {
+    const u64 pc = (u64)ct.L * ct.n;
+    std::unique_ptr<WsGuard> t;   // (the substituted rows over the ciphertext context, when they still switch up)
+    if (kc.L != ct.L) t = std::make_unique<WsGuard>(nkeys * pc * sizeof(u64), s, true);
+    u64 *dst = t ? t->u() : out;
+    for (size_t b0 = 0; b0 < nkeys; b0 += k::KG_KEYS) {
+        const size_t nb = std::min<size_t>(k::KG_KEYS, nkeys - b0);
+        k::KgExps e{};
+        for (size_t b = 0; b < nb; b++) e.e[b] = (uint32_t)(exponents[b0 + b] % (2 * ct.n));
+        const u64 total = (u64)nb * pc;
+        FHE_LAUNCH("galois_from", k::galois_from_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
+                   s_ntt, dst + b0 * pc, e, (uint32_t)ct.L, (uint32_t)ct.logn, total);
+    }
+    if (t) switch_up_ntt(ct, kc, t->u(), out, nkeys, s);
 }
 #undef FHE_ENC_SWITCH
 #undef FHE_ENC_CASE_F64

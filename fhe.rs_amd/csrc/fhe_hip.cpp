@@ -284,16 +284,6 @@ fhe_status host_call(A... a) {
     return guard([&] { run_host(Op(a...)); });
 }
 
-std::unique_ptr<Ksk> make_ksk(const Ctx &ct, const Ctx &kc, size_t ndigits, size_t log_base) {
-    ksk_validate(ct, kc, ndigits, log_base);
-    kc.need_device();
-    auto k_ = std::make_unique<Ksk>();
-    k_->ct_ctx = &ct;
-    k_->ksk_ctx = &kc;
-    k_->ndigits = ndigits;
-    k_->log_base = log_base;
-    return k_;
-}
 // Context over `moduli` whose NTT tables come from the host's callback (NULL: the engine's own psi).  Every table
 // is cached per modulus, so handles made later from the parameter set (a level-specific multiplication basis) never
 // call back into the host: `fn` is only invoked while fhe_params_create_with_tables runs.
@@ -1715,6 +1705,111 @@ fhe_status fhe_bfv_encrypt_pk_dev(const fhe_ctx *ctx, size_t variance, const uin
         }
         set_device(c);
         encrypt_pk(c, variance, pk, seeds, pt, pt_shared != 0, out, batch, as_stream(stream));
+    });
+}
+
+// --------------------------------------------------------------------- key generation ----
+// Device-pointer forms only, like encryption.  Each checks its handles, the device, the variance and the key's
+// geometry before it looks at a buffer; nkeys == 0 is a no-op.  The handles are made all or none: on an error none is
+// returned and none leaks.
+static void keygen_checks(const fhe_ctx *ct_ctx, const fhe_ctx *key_ctx, size_t variance) {
+    need(ct_ctx, "ct_ctx");
+    need(key_ctx, "key_ctx");
+    key_ctx->c->need_device();
+    check_variance(variance);
+}
+static void keygen_out(std::vector<std::unique_ptr<Ksk>> keys, fhe_ksk **out) {
+    std::vector<std::unique_ptr<fhe_ksk>> hs;
+    for (auto &k_ : keys) {
+        hs.push_back(std::make_unique<fhe_ksk>());
+        hs.back()->k = std::move(k_);
+    }
+    for (size_t i = 0; i < hs.size(); i++) out[i] = hs[i].release();
+}
+fhe_status fhe_ksk_generate_dev(const fhe_ctx *ct_ctx, const fhe_ctx *ksk_ctx, size_t variance, const uint64_t *s_ntt,
+                                const uint64_t *from_ntt, const uint8_t *seeds, size_t nkeys, uint8_t *seeds_out,
+                                void *stream, fhe_ksk **out) {
+    return guard([&] {
+        keygen_checks(ct_ctx, ksk_ctx, variance);
+        const Ctx &ct = *ct_ctx->c, &kc = *ksk_ctx->c;
+        const auto dg = ksk_digits(ct, kc);
+        ksk_validate(ct, kc, dg.first, dg.second);
+        if (!nkeys) return;
+        need(out, "out");
+        for (size_t i = 0; i < nkeys; i++) out[i] = nullptr;
+        need(s_ntt, "s_ntt");
+        need(from_ntt, "from_ntt");
+        need(seeds, "seeds");
+        set_device(kc);
+        keygen_out(ksk_generate(ct, kc, variance, s_ntt, from_ntt, seeds, nkeys, seeds_out, as_stream(stream)), out);
+    });
+}
+fhe_status fhe_bfv_relin_key_generate_dev(const fhe_ctx *ct_ctx, const fhe_ctx *key_ctx, size_t variance,
+                                          const uint64_t *s_ntt, const uint8_t *seed, uint8_t *seed_out, void *stream,
+                                          fhe_ksk **out) {
+    return guard([&] {
+        keygen_checks(ct_ctx, key_ctx, variance);
+        const Ctx &ct = *ct_ctx->c, &kc = *key_ctx->c;
+        require(kc.L >= 2, E_KEYSWITCH_UNSUPPORTED, "KeySwitchingNotSupported: a relinearization key needs two key moduli");
+        ksk_validate(ct, kc, ct.L, 0);
+        need(out, "out");
+        *out = nullptr;
+        need(s_ntt, "s_ntt");
+        need(seed, "seed");
+        set_device(kc);
+        hipStream_t s = as_stream(stream);
+        WsGuard from(kc.L * kc.n * sizeof(u64), s, true);   // s^2: a secret
+        relin_from(ct, kc, s_ntt, from.u(), s);
+        keygen_out(ksk_generate(ct, kc, variance, s_ntt, from.u(), seed, 1, seed_out, s), out);
+    });
+}
+fhe_status fhe_bfv_galois_keys_generate_dev(const fhe_ctx *ct_ctx, const fhe_ctx *key_ctx, size_t variance,
+                                            const uint64_t *s_ntt, const size_t *exponents, const uint8_t *seeds,
+                                            size_t nkeys, uint8_t *seeds_out, void *stream, fhe_ksk **out) {
+    return guard([&] {
+        keygen_checks(ct_ctx, key_ctx, variance);
+        const Ctx &ct = *ct_ctx->c, &kc = *key_ctx->c;
+        if (nkeys) need(exponents, "exponents");
+        for (size_t i = 0; i < nkeys; i++)
+            require((exponents[i] % (2 * ct.n)) & 1, E_INVALID_SUBST, "InvalidSubstitutionExponent");
+        const auto dg = ksk_digits(ct, kc);
+        ksk_validate(ct, kc, dg.first, dg.second);
+        if (!nkeys) return;
+        need(out, "out");
+        for (size_t i = 0; i < nkeys; i++) out[i] = nullptr;
+        need(s_ntt, "s_ntt");
+        need(seeds, "seeds");
+        set_device(kc);
+        hipStream_t s = as_stream(stream);
+        std::vector<std::unique_ptr<Ksk>> keys;
+        // chunks of 256 keys bound the `from` scratch (the substituted secrets, cleared after use)
+        for (size_t b0 = 0; b0 < nkeys; b0 += 256) {
+            const size_t nb = std::min<size_t>(256, nkeys - b0);
+            WsGuard from(nb * kc.L * kc.n * sizeof(u64), s, true);
+            galois_from(ct, kc, s_ntt, exponents + b0, nb, from.u(), s);
+            for (auto &k_ : ksk_generate(ct, kc, variance, s_ntt, from.u(), seeds + b0 * 32, nb,
+                                         seeds_out ? seeds_out + b0 * 32 : nullptr, s))
+                keys.push_back(std::move(k_));
+        }
+        keygen_out(std::move(keys), out);
+    });
+}
+size_t fhe_ksk_ndigits(const fhe_ksk *ksk) { return ksk ? ksk->k->ndigits : 0; }
+fhe_status fhe_ksk_export_dev(const fhe_ksk *ksk, uint64_t *c0, uint64_t *c1, uint64_t *c0_shoup, uint64_t *c1_shoup,
+                              void *stream) {
+    return guard([&] {
+        need(ksk, "ksk");
+        need(c0, "c0");
+        need(c1, "c1");
+        const Ksk &k_ = *ksk->k;
+        const Ctx &kc = *k_.ksk_ctx;
+        set_device(kc);
+        const size_t bytes = k_.ndigits * kc.L * kc.n * sizeof(u64);
+        hipStream_t s = as_stream(stream);
+        const std::pair<u64 *, const DevBuf<u64> *> parts[] = {{c0, &k_.c0}, {c1, &k_.c1}, {c0_shoup, &k_.c0s},
+                                                               {c1_shoup, &k_.c1s}};
+        for (const auto &pr : parts)
+            if (pr.first) FHE_HIP_CHECK(hipMemcpyAsync(pr.first, pr.second->p, bytes, hipMemcpyDeviceToDevice, s));
     });
 }
 

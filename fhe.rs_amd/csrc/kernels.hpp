@@ -28,6 +28,8 @@
 //   add_plain_kernel        ct +- pt                                 F/bfv/ops/mod.rs:71-108, 166-203
 //   cbd_sample_kernel, small_ntt_kernel, encrypt_sk_kernel, encrypt_pk_kernel   Poly::small, SecretKey::encrypt_poly,
 //                           PublicKey::try_encrypt   M/rq/mod.rs:298-330, F/bfv/keys/secret_key.rs:100-134, public_key.rs:47-97
+//   ksk_seeds_kernel, cbd_sample_at_kernel, ksk_consts_kernel, ksk_gen_kernel, galois_from_kernel   KeySwitchingKey::new,
+//                           RelinearizationKey / GaloisKey::new   F/bfv/keys/key_switching_key.rs:71-236, galois_key.rs:26-58
 // Compile-time knobs live in knobs.hpp (pinned in the release build); rejected kernel variants in tools/lab/ (lab builds only).
 #pragma once
 #include "kernels_common.hpp"
@@ -38,6 +40,7 @@
 #include "kernels_misc.hpp"
 #include "kernels_encode.hpp"
 #include "kernels_encrypt.hpp"
+#include "kernels_keygen.hpp"
 
 namespace fhe {
 namespace k {

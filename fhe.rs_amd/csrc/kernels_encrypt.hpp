@@ -36,42 +36,47 @@ __device__ __forceinline__ u64 cbd_bit_offset(u64 g, uint32_t v, uint32_t logn, 
     const u64 i = g & ((1ull << logn) - 1);
     return (g >> logn) * wpd * 64 + (v <= 16 ? 4ull * v * i : 128ull * i);
 }
+// The body of both samplers, written once: BIT(g) is the first stream bit of sample g (cbd_sample_kernel: draws from
+// word 0; cbd_sample_at_kernel, kernels_keygen.hpp: from a word offset).  A macro and not an inline function: inlining a
+// shared function reorders cbd_sample_kernel's instructions, and its ISA stays as it was.
+#define FHE_CBD_SAMPLE_BODY(BIT)                                                                                   \
+    const uint32_t tid = threadIdx.x;                                                                              \
+    const uint32_t b = blockIdx.y;                                                                                 \
+    const u64 g0 = (u64)blockIdx.x * CBD_THREADS;                                                                  \
+    const u64 glast = (g0 + CBD_THREADS <= nsamples ? g0 + CBD_THREADS : nsamples) - 1;                            \
+    const u64 blk0 = (BIT(g0) >> 6) >> 3;                                                                          \
+    const u64 wlast = (BIT(glast) >> 6) + 1;   /* (the word after a sample's first is always read) */              \
+    const uint32_t nblk = (uint32_t)((wlast >> 3) - blk0 + 1);                                                     \
+    if (tid < nblk) {                                                                                              \
+        const uint8_t *sd = seeds + (u64)b * 32;                                                                   \
+        uint32_t key[8];                                                                                           \
+        _Pragma("unroll") for (int i = 0; i < 8; i++)                                                              \
+            key[i] = (uint32_t)sd[4 * i] | ((uint32_t)sd[4 * i + 1] << 8) | ((uint32_t)sd[4 * i + 2] << 16) |     \
+                     ((uint32_t)sd[4 * i + 3] << 24);                                                              \
+        uint32_t w[16];                                                                                            \
+        chacha8_block(key, blk0 + tid, w);                                                                         \
+        _Pragma("unroll") for (int i = 0; i < 16; i++) words[16 * tid + i] = w[i];                                 \
+    }                                                                                                              \
+    __syncthreads();                                                                                               \
+    const u64 g = g0 + tid;                                                                                        \
+    if (g >= nsamples) return;                                                                                     \
+    const u64 bo = BIT(g);                                                                                         \
+    const uint32_t wi = (uint32_t)((bo >> 6) - 8 * blk0), sh = (uint32_t)(bo & 63);                                \
+    const u64 lo = (u64)words[2 * wi] | ((u64)words[2 * wi + 1] << 32);                                            \
+    const u64 hi = (u64)words[2 * wi + 2] | ((u64)words[2 * wi + 3] << 32);                                        \
+    const u128_t pool = (((u128_t)hi << 64) | lo) >> sh;                                                           \
+    const uint32_t v2 = 2 * variance; /* 2 ... 64 */                                                               \
+    const u64 mask = v2 == 64 ? ~0ull : (1ull << v2) - 1;                                                          \
+    const int add = __builtin_popcountll((u64)pool & mask), sub = __builtin_popcountll((u64)(pool >> v2) & mask);  \
+    out[(u64)b * nsamples + g] = (int8_t)(add - sub)
+#define FHE_CBD_BIT(g) cbd_bit_offset(g, variance, logn, wpd)
 __global__ void __launch_bounds__(CBD_THREADS)
     cbd_sample_kernel(const uint8_t *__restrict__ seeds, int8_t *__restrict__ out, uint32_t variance, u64 nsamples,
                       uint32_t logn, u64 wpd) {
     FHE_DYN_SMEM(uint32_t, words);   // CBD_SMEM_BYTES: [nblk][16] keystream words
-    const uint32_t tid = threadIdx.x;
-    const uint32_t b = blockIdx.y;
-    const u64 g0 = (u64)blockIdx.x * CBD_THREADS;
-    const u64 glast = (g0 + CBD_THREADS <= nsamples ? g0 + CBD_THREADS : nsamples) - 1;
-    const u64 blk0 = (cbd_bit_offset(g0, variance, logn, wpd) >> 6) >> 3;
-    const u64 wlast = (cbd_bit_offset(glast, variance, logn, wpd) >> 6) + 1;   // (the word after a sample's first is always read)
-    const uint32_t nblk = (uint32_t)((wlast >> 3) - blk0 + 1);
-    if (tid < nblk) {
-        const uint8_t *sd = seeds + (u64)b * 32;
-        uint32_t key[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++)
-            key[i] = (uint32_t)sd[4 * i] | ((uint32_t)sd[4 * i + 1] << 8) | ((uint32_t)sd[4 * i + 2] << 16) |
-                     ((uint32_t)sd[4 * i + 3] << 24);
-        uint32_t w[16];
-        chacha8_block(key, blk0 + tid, w);
-#pragma unroll
-        for (int i = 0; i < 16; i++) words[16 * tid + i] = w[i];
-    }
-    __syncthreads();
-    const u64 g = g0 + tid;
-    if (g >= nsamples) return;
-    const u64 bo = cbd_bit_offset(g, variance, logn, wpd);
-    const uint32_t wi = (uint32_t)((bo >> 6) - 8 * blk0), sh = (uint32_t)(bo & 63);
-    const u64 lo = (u64)words[2 * wi] | ((u64)words[2 * wi + 1] << 32);
-    const u64 hi = (u64)words[2 * wi + 2] | ((u64)words[2 * wi + 3] << 32);
-    const u128_t pool = (((u128_t)hi << 64) | lo) >> sh;
-    const uint32_t v2 = 2 * variance;                        // 2 ... 64
-    const u64 mask = v2 == 64 ? ~0ull : (1ull << v2) - 1;
-    const int add = __builtin_popcountll((u64)pool & mask), sub = __builtin_popcountll((u64)(pool >> v2) & mask);
-    out[(u64)b * nsamples + g] = (int8_t)(add - sub);
+    FHE_CBD_SAMPLE_BODY(FHE_CBD_BIT);
 }
+#undef FHE_CBD_BIT
 
 // x in [-64, 64] -> x mod p (try_convert_from(&[i64], ctx, false)): p + x selected for negative x, no branch
 __device__ __forceinline__ u64 lift_small(int8_t x, u64 p) {

@@ -525,6 +525,53 @@ fhe_status fhe_bfv_encrypt_sk_dev(const fhe_ctx *ctx, size_t variance, const uin
 fhe_status fhe_bfv_encrypt_pk_dev(const fhe_ctx *ctx, size_t variance, const uint64_t *pk, const uint8_t *seeds,
                                   const uint64_t *pt, int pt_shared, uint64_t *out, size_t batch, void *stream);
 
+/* --------------------------------------------------------- key generation ---- */
+/* Key-switching, relinearization and Galois keys made on the device from a device-resident secret.  Device-pointer
+ * forms only, with no host-pointer twin: the secret, the errors and s^2 / s_sub never pass through host memory.
+ *
+ * KeySwitchingKey::new(sk, from, ciphertext_level, ksk_level, rng) (F/bfv/keys/key_switching_key.rs:71-236) with
+ * rng = ChaCha8Rng::from_seed(seeds[b]) (the layout of fhe_bfv_sample_small_dev, PARITY UNPINNED like it):
+ *   K      = the rng's first 32 bytes (u64 words 0 ... 3): the key's public seed, written to seeds_out[b] when given;
+ *   c1[i]  = Poly::random_from_seed(ksk_ctx, bytes [32 i, 32 i + 32) of ChaCha8Rng::from_seed(K)), as Ntt values;
+ *   e_i    = the rng's i-th Poly::small(variance) draw, starting at u64 word 4 + i wpd (draws start on word boundaries);
+ *   c0[i]  = NTT(e_i) - c1[i] (.) s + g_i (.) from, bit-identical to the reference's NTT(e_i - INTT(c1[i] s) + g_i from).
+ * Digits: ndigits = the ciphertext context's moduli count and g_i = RnsContext(moduli[..ndigits]).get_garner(i) mod q_j;
+ * for a single-modulus key context the decomposition (:197-236): log_base = log_modulus / 2 with
+ * log_modulus = q.next_power_of_two().ilog2(), ndigits = ceil(log_modulus / log_base), g_i = 2^(i log_base) mod q.
+ * s_ntt is the level-0 secret in Ntt form (fhe_bfv_sample_small_dev's SecretKey::random); the first Lk rows are read.
+ * The handles hold the Shoup twins and, when eligible, the F64 words, as fhe_ksk_create would make them from the
+ * exported arrays.  They are ready to use on `stream`; on another stream, synchronise first.  Statuses:
+ * FHE_E_INVALID_VARIANCE (variance outside [1, 32]), FHE_E_CONTEXT_NOT_REACHABLE (key level above the ciphertext
+ * level), FHE_E_ARG (NULL handle or buffer).  nkeys == 0 is a no-op.  On an error no handle is returned (out[] NULL).
+ * Engine scratch holding samples, s^2 or s_sub is cleared before it returns to the pool. */
+/* KeySwitchingKey::new for nkeys keys: from_ntt [nkeys][Lk][N] Ntt over ksk_ctx (the reference's `from` after the
+ * forward transform), seeds [nkeys][32] -> out[nkeys] handles, seeds_out [nkeys][32] (may be NULL).  from_ntt must
+ * hold canonical residues (row j below q_j), as every Ntt-form output of this library does: the words are not checked
+ * on the device (fhe_ksk_create's host check would need a copy of them), and a word >= q_j gives a key whose c0 words
+ * and Shoup twins are not canonical. */
+fhe_status fhe_ksk_generate_dev(const fhe_ctx *ct_ctx, const fhe_ctx *ksk_ctx, size_t variance, const uint64_t *s_ntt,
+                                const uint64_t *from_ntt, const uint8_t *seeds, size_t nkeys, uint8_t *seeds_out,
+                                void *stream, fhe_ksk **out);
+/* RelinearizationKey::new_leveled (F/bfv/keys/relinearization_key.rs:43-64): from = Switcher(ct_ctx -> key_ctx) of
+ * s_ct (.) s_ct (the identity when the two contexts are one).  One key from seed [32]; seed_out [32] may be NULL.  A
+ * single-modulus key_ctx -> FHE_E_KEYSWITCH_UNSUPPORTED.  (A switch-up builds the switcher's public tables on the host
+ * and waits for the stream before freeing them.) */
+fhe_status fhe_bfv_relin_key_generate_dev(const fhe_ctx *ct_ctx, const fhe_ctx *key_ctx, size_t variance,
+                                          const uint64_t *s_ntt, const uint8_t *seed, uint8_t *seed_out, void *stream,
+                                          fhe_ksk **out);
+/* GaloisKey::new (F/bfv/keys/galois_key.rs:26-58) for nkeys exponents (host array) in one batched call: from =
+ * Switcher(ct_ctx -> key_ctx) of substitute(s_ct, exponents[b]); key b from seeds[b].  An even exponent (mod 2N) ->
+ * FHE_E_INVALID_SUBSTITUTION_EXPONENT.  Use the handles with fhe_bfv_galois_dev(exponent mod 2N). */
+fhe_status fhe_bfv_galois_keys_generate_dev(const fhe_ctx *ct_ctx, const fhe_ctx *key_ctx, size_t variance,
+                                            const uint64_t *s_ntt, const size_t *exponents, const uint8_t *seeds,
+                                            size_t nkeys, uint8_t *seeds_out, void *stream, fhe_ksk **out);
+/* A key's arrays as a client sends them: c0, c1 [ndigits][Lk][N] (NttShoup values) and, when not NULL, their Shoup
+ * twins floor(c 2^64 / q); device-to-device copies on `stream`.  fhe_ksk_create of the copies makes an equal handle. */
+fhe_status fhe_ksk_export_dev(const fhe_ksk *ksk, uint64_t *c0, uint64_t *c1, uint64_t *c0_shoup, uint64_t *c1_shoup,
+                              void *stream);
+/* A key's digit count: each of fhe_ksk_export_dev's arrays holds ndigits * Lk * N words (0 for NULL). */
+size_t fhe_ksk_ndigits(const fhe_ksk *ksk);
+
 /* ------------------------------------------------- zq::primes (host, no GPU) ---- */
 /* generate_prime (M/zq/primes.rs:30-59): returns 0 when none exists. */
 uint64_t fhe_generate_prime(size_t num_bits, uint64_t modulo, uint64_t upper_bound);

@@ -933,6 +933,84 @@ impl DeviceSeeds {
     pub fn release_on(self, stream: &Stream) -> Result<()> { self.buf.release_on(stream) }
 }
 
+/// Key generation on the device (F/bfv/keys/key_switching_key.rs:71-236, relinearization_key.rs:43-64,
+/// galois_key.rs:26-58): key b with rng = `ChaCha8Rng::from_seed(seeds[b])`; the keys' public seeds K come back as
+/// `DeviceSeeds`.  `s_ntt` is the level-0 secret in Ntt form (`CtxView::sample_small_dev`), the caller's to clear; the
+/// engine clears its own scratch of errors, s^2 and s_sub.  The handles are ready to use on `stream`.
+impl HipKsk {
+    fn adopt(ptrs: Vec<*mut ffi::FheKsk>, ct_ctx: &Arc<HipCtx>, ksk_ctx: &Arc<HipCtx>) -> Vec<Self> {
+        ptrs.into_iter().map(|p| Self { ptr: p, ct_ctx: ct_ctx.clone(), ksk_ctx: ksk_ctx.clone() }).collect()
+    }
+    fn seeds_out(ksk_ctx: &Arc<HipCtx>, batch: usize, stream: &Stream) -> Result<DeviceSeeds> {
+        DeviceSeeds::upload(ksk_ctx.device(), &vec![[0u8; 32]; batch], stream)
+    }
+    /// `KeySwitchingKey::new` for `seeds.batch` keys: `from_ntt` `[batch][Lk][N]` is the reference's `from` in Ntt form
+    /// over the key context, canonical residues (row j below q_j; not checked on the device).
+    pub fn generate(ct_ctx: &Arc<HipCtx>, ksk_ctx: &Arc<HipCtx>, variance: usize, s_ntt: &DeviceBuffer,
+                    from_ntt: &DeviceBuffer, seeds: &DeviceSeeds, stream: &Stream) -> Result<(Vec<Self>, DeviceSeeds)> {
+        expect_len("generate from_ntt", from_ntt.len(), seeds.batch * ksk_ctx.poly_words())?;
+        if s_ntt.len() < ksk_ctx.poly_words() {
+            return Err(shape_error("generate: s_ntt is shorter than one polynomial over the key context"));
+        }
+        let k = Self::seeds_out(ksk_ctx, seeds.batch, stream)?;
+        let mut out = vec![ptr::null_mut(); seeds.batch];
+        check(unsafe {
+            ffi::fhe_ksk_generate_dev(ct_ctx.as_ptr(), ksk_ctx.as_ptr(), variance, s_ntt.as_ptr(), from_ntt.as_ptr(),
+                                      seeds.as_ptr(), seeds.batch, k.buf.as_mut_ptr() as *mut u8, stream.as_ptr(),
+                                      out.as_mut_ptr())
+        })?;
+        Ok((Self::adopt(out, ct_ctx, ksk_ctx), k))
+    }
+    /// `RelinearizationKey::new_leveled` from one seed.
+    pub fn generate_relin(ct_ctx: &Arc<HipCtx>, key_ctx: &Arc<HipCtx>, variance: usize, s_ntt: &DeviceBuffer,
+                          seed: &DeviceSeeds, stream: &Stream) -> Result<(Self, DeviceSeeds)> {
+        expect_len("generate_relin seeds", seed.batch, 1)?;
+        if s_ntt.len() < key_ctx.poly_words() {
+            return Err(shape_error("generate_relin: s_ntt is shorter than one polynomial over the key context"));
+        }
+        let k = Self::seeds_out(key_ctx, 1, stream)?;
+        let mut out: *mut ffi::FheKsk = ptr::null_mut();
+        check(unsafe {
+            ffi::fhe_bfv_relin_key_generate_dev(ct_ctx.as_ptr(), key_ctx.as_ptr(), variance, s_ntt.as_ptr(), seed.as_ptr(),
+                                                k.buf.as_mut_ptr() as *mut u8, stream.as_ptr(), &mut out)
+        })?;
+        Ok((Self { ptr: out, ct_ctx: ct_ctx.clone(), ksk_ctx: key_ctx.clone() }, k))
+    }
+    /// `GaloisKey::new` for every exponent in one call, key b from `seeds[b]`; use key b with exponent b mod 2N.
+    pub fn generate_galois(ct_ctx: &Arc<HipCtx>, key_ctx: &Arc<HipCtx>, variance: usize, s_ntt: &DeviceBuffer,
+                           exponents: &[usize], seeds: &DeviceSeeds, stream: &Stream) -> Result<(Vec<Self>, DeviceSeeds)> {
+        expect_len("generate_galois seeds", seeds.batch, exponents.len())?;
+        if s_ntt.len() < key_ctx.poly_words() {
+            return Err(shape_error("generate_galois: s_ntt is shorter than one polynomial over the key context"));
+        }
+        let k = Self::seeds_out(key_ctx, seeds.batch, stream)?;
+        let mut out = vec![ptr::null_mut(); seeds.batch];
+        check(unsafe {
+            ffi::fhe_bfv_galois_keys_generate_dev(ct_ctx.as_ptr(), key_ctx.as_ptr(), variance, s_ntt.as_ptr(),
+                                                  exponents.as_ptr(), seeds.as_ptr(), seeds.batch,
+                                                  k.buf.as_mut_ptr() as *mut u8, stream.as_ptr(), out.as_mut_ptr())
+        })?;
+        Ok((Self::adopt(out, ct_ctx, key_ctx), k))
+    }
+    /// The key's digit count as the engine holds it (`fhe_ksk_ndigits`): `c0`, `c1` and their twins are
+    /// `[ndigits][Lk][N]`.
+    pub fn ndigits(&self) -> usize { unsafe { ffi::fhe_ksk_ndigits(self.ptr) } }
+    /// The key's `c0`, `c1` and their Shoup twins, `[ndigits][Lk][N]` each on the device, sized from the engine's own
+    /// digit count of this key: what a client sends to the server (`HipKsk::new` of the downloaded arrays is an equal
+    /// key).
+    pub fn export_dev(&self, stream: &Stream) -> Result<[DeviceBuffer; 4]> {
+        let len = self.ndigits() * self.ksk_ctx.poly_words();
+        let dev = self.ksk_ctx.device();
+        let out = [DeviceBuffer::alloc_on(dev, len, stream)?, DeviceBuffer::alloc_on(dev, len, stream)?,
+                   DeviceBuffer::alloc_on(dev, len, stream)?, DeviceBuffer::alloc_on(dev, len, stream)?];
+        check(unsafe {
+            ffi::fhe_ksk_export_dev(self.ptr, out[0].as_mut_ptr(), out[1].as_mut_ptr(), out[2].as_mut_ptr(),
+                                    out[3].as_mut_ptr(), stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+}
+
 /// Encryption over one level's context (F/bfv/keys/secret_key.rs, public_key.rs).  The engine clears its own scratch of
 /// samples; `s_ntt` and the output of `sample_small_dev` are the caller's to clear.
 impl CtxView<'_> {
