@@ -580,6 +580,17 @@ struct Ctx {
         if (mx >> 50) return 0;
         return (mx >> 49) ? 3 : (mx >> 48) ? 4 : 5;
     }
+    // The F64 class of those rows for a launch on whole-row tiles (4096 ... 16384 points: the sizes the F64 instances
+    // exist for), 0 otherwise.  `f64_on`: a caller's own reading of the switch, taken once for all launches of a call.
+    int f64_rows(size_t first, size_t rows, bool f64_on = true) const {
+        return f64_on && logn >= 12 && logn <= 14 ? f64_class(first, rows) : 0;
+    }
+    // every modulus [first, first + rows) of the ROOT's list below 2^60: the narrow passes apply
+    bool below_2p60(size_t first, size_t rows) const {
+        for (size_t i = first; i < first + rows; i++)
+            if (root->moduli[i] >> 60) return false;
+        return true;
+    }
     const DevMod *dmods() const { return root->d_mods.p; }
     const k::u64x2 *dtw() const { return root->d_tw.p; }
     const k::u64x2 *ditw() const { return root->d_itw.p; }
@@ -762,6 +773,67 @@ inline void allow_big_lds(K kernel, size_t bytes) {
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
 }
 
+// One launch of KERNEL (a compile-time constant, so that the call in FHE_LAUNCH stays a direct one)
+template <auto KERNEL, class... A>
+inline void launch_k(const char *name, dim3 grid, dim3 block, size_t lds, hipStream_t s, A... args) {
+    allow_big_lds(KERNEL, lds);
+    FHE_LAUNCH(name, KERNEL, grid, block, lds, s, args...);
+}
+// (a kernel as a value, for the local launch lambdas of a site: decltype(kernel)::value is the kernel)
+template <auto KERNEL>
+struct kernel_c {
+    static constexpr auto value = KERNEL;
+};
+
+// ---- instance selection: a run-time property of a launch becomes a template argument of its kernel ----
+// Each helper hands its callback a std::integral_constant; the callback names the kernel's template-id with
+// decltype(x)::value.  A callback is instantiated for EVERY value its helper offers, so a site that must not create an
+// instance (F64 below 4096 points, a gathering loader below 4096, ...) narrows the bounds or tests with `if constexpr`.
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+// f(int_c<LM>) for LM == logn in [LO, HI]; E_ARG with `what` outside
+template <int LO, int... I, class F>
+inline bool with_logn_from(size_t logn, std::integer_sequence<int, I...>, F &f) {
+    return ((logn == (size_t)(LO + I) && (f(int_c<LO + I>{}), true)) || ...);
+}
+template <int LO, int HI, class F>
+inline void with_logn(size_t logn, const char *what, F &&f) {
+    if (!with_logn_from<LO>(logn, std::make_integer_sequence<int, HI - LO + 1>{}, f)) throw StatusError(E_ARG, what);
+}
+
+// f(bool_constant<NARROW>, int_c<HR>) for rows of 2^LM points: the F64 class hr = 3, 4, 5 (Ctx::f64_class) exists for
+// whole rows of 4096 ... 16384 points only; otherwise the integer instances, narrow (every modulus below 2^60) or general
+template <int LM, class F>
+inline void with_row_kind(bool narrow, int hr, F &&f) {
+    if constexpr (LM >= 12 && LM <= 14) {
+        if (hr == 3) return f(std::false_type{}, int_c<3>{});
+        if (hr == 4) return f(std::false_type{}, int_c<4>{});
+        if (hr == 5) return f(std::false_type{}, int_c<5>{});
+    }
+    if (narrow) f(std::true_type{}, int_c<0>{});
+    else f(std::false_type{}, int_c<0>{});
+}
+
+template <class F>
+inline void with_bool(bool b, F &&f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// The kernels that hold one tile of 2^logm points in LDS (logm in [LO, 14]): f(int_c<LM>, bool_constant<NARROW>, int_c<HR>)
+template <int LO = 3, class F>
+inline void with_tile(size_t logm, const char *what, bool narrow, int hr, F &&f) {
+    with_logn<LO, 14>(logm, what, [&](auto lm) {
+        with_row_kind<decltype(lm)::value>(narrow, hr, [&](auto nrw, auto h) { f(lm, nrw, h); });
+    });
+}
+// ... and their launch: `grid` workgroups of one 2^lm-point tile each
+template <auto KERNEL, class... A>
+inline void launch_tile(const char *name, int lm, size_t grid, hipStream_t s, A... args) {
+    launch_k<KERNEL>(name, dim3((unsigned)grid), dim3(k::ntt_threads_c(lm)), k::lds_words(1u << lm) * sizeof(u64), s, args...);
+}
+
 #if defined(FHE_LAB)
 // rejected kernel variants, selected by FHE_LAB_* environment switches in lab builds only (lab/lab_engine.hpp)
 struct Ksk;
@@ -772,56 +844,20 @@ inline bool lab_try_ks_pair(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0, 
                             const u64 *a1, u64 a_stride, size_t npolys, hipStream_t s);
 #endif
 
-template <bool INV, bool NARROW = false, bool GATHER = false>
-inline void launch_ntt_lds(const char *name, uint32_t logm, unsigned grid, hipStream_t s, const u64 *in, u64 *out,
-                           const k::RowMap &map, const DevMod *mods, const k::u64x2 *tw, const k::u64x2 *ninv,
-                           uint32_t logn) {
-    const size_t lds = k::lds_words(1u << logm) * sizeof(u64);
-#define FHE_NTT_CASE(LM)                                                                                        \
-    case LM:                                                                                                    \
-        allow_big_lds((k::ntt_kernel<INV, LM, NARROW, 1, GATHER>), lds);                                        \
-        FHE_LAUNCH(name, (k::ntt_kernel<INV, LM, NARROW, 1, GATHER>), dim3(grid), dim3(k::ntt_threads_c(LM)), lds, s, in, \
-                   out, map, mods, tw, ninv, logn);                                                             \
-        break;
-    if constexpr (GATHER) {   // (galois_apply folds the substitution from N = 4096 on: three tile sizes)
-        switch (logm) {
-            FHE_NTT_CASE(12) FHE_NTT_CASE(13) FHE_NTT_CASE(14)
-            default: throw StatusError(E_ARG, "unsupported NTT tile size for the gathering loader");
-        }
-    } else {
-        switch (logm) {
-            FHE_NTT_CASE(3) FHE_NTT_CASE(4) FHE_NTT_CASE(5) FHE_NTT_CASE(6) FHE_NTT_CASE(7) FHE_NTT_CASE(8)
-            FHE_NTT_CASE(9) FHE_NTT_CASE(10) FHE_NTT_CASE(11) FHE_NTT_CASE(12) FHE_NTT_CASE(13) FHE_NTT_CASE(14)
-            default: throw StatusError(E_ARG, "unsupported NTT tile size");
-        }
-    }
-#undef FHE_NTT_CASE
-}
-
-// The F64 instances of ntt_kernel (whole rows of 4096 / 8192 / 16384 points, every modulus of the launch below 2^50:
-// Ctx::f64_class): false when the launch does not qualify and takes the integer kernels.
-template <bool INV, bool GATHER>
-inline bool launch_ntt_f64(const Ctx &c, const char *name, int hr, uint32_t logn, unsigned grid, hipStream_t s, const u64 *in,
-                           u64 *out, const k::RowMap &map) {
-    if (!hr || logn < 12 || logn > 14) return false;
-    const size_t lds = k::lds_words(1u << logn) * sizeof(u64);
-    const k::u64x2 *tw = INV ? c.ditw_f() : c.dtw_f();
-#define FHE_NTT_F64(LM, HR)                                                                                            \
-    do {                                                                                                               \
-        allow_big_lds((k::ntt_kernel<INV, LM, false, 1, GATHER, HR>), lds);                                            \
-        FHE_LAUNCH(name, (k::ntt_kernel<INV, LM, false, 1, GATHER, HR>), dim3(grid), dim3(k::ntt_threads_c(LM)), lds, s, in, \
-                   out, map, c.dmods(), tw, c.dninv_f(), logn);                                                        \
-    } while (0)
-#define FHE_NTT_F64_HR(LM)                      \
-    case LM:                                    \
-        if (hr == 3) FHE_NTT_F64(LM, 3);        \
-        else if (hr == 4) FHE_NTT_F64(LM, 4);   \
-        else FHE_NTT_F64(LM, 5);                \
-        break;
-    switch (logn) { FHE_NTT_F64_HR(12) FHE_NTT_F64_HR(13) FHE_NTT_F64_HR(14) }
-#undef FHE_NTT_F64_HR
-#undef FHE_NTT_F64
-    return true;
+// One launch of ntt_kernel on `grid` tiles of 2^logm points.  hr != 0 (Ctx::f64_rows: whole rows of 4096 / 8192 / 16384
+// points, every modulus of the launch below 2^50): the F64 instances, under the label name_f64.
+// (GATHER: galois_apply folds the substitution from N = 4096 on: three tile sizes)
+template <bool INV, bool GATHER = false>
+inline void launch_ntt_lds(const Ctx &c, const char *name, const char *name_f64, uint32_t logm, bool narrow, int hr,
+                           unsigned grid, hipStream_t s, const u64 *in, u64 *out, const k::RowMap &map, uint32_t logn) {
+    with_tile<GATHER ? 12 : 3>(
+        logm, GATHER ? "unsupported NTT tile size for the gathering loader" : "unsupported NTT tile size", narrow, hr,
+        [&](auto lm, auto nrw, auto h) {
+            constexpr int LM = decltype(lm)::value, HR = decltype(h)::value;
+            launch_tile<k::ntt_kernel<INV, LM, decltype(nrw)::value, 1, GATHER, HR>>(
+                HR ? name_f64 : name, LM, grid, s, in, out, map, c.dmods(),
+                HR ? (INV ? c.ditw_f() : c.dtw_f()) : (INV ? c.ditw() : c.dtw()), HR ? c.dninv_f() : c.dninv(), logn);
+        });
 }
 
 // Forward / inverse NTT of `npolys * map.rows` residue rows.  N <= 16384: one LDS-resident
@@ -831,50 +867,31 @@ inline void launch_ntt(const Ctx &c, bool inverse, const u64 *in, u64 *out, k::R
     if (npolys == 0 || map.rows == 0) return;
     const uint32_t logn = (uint32_t)c.logn;
     const unsigned rows_total = (unsigned)(npolys * map.rows);
+    const size_t first = (size_t)((int32_t)map.row_begin + map.mod_offset);
+    // every modulus of the launch below 2^60: the transform without per-stage conditional subtractions
+    bool narrow = !FHE_LAB_FLAG("NO_NARROW") && c.below_2p60(first, map.rows);
+    // (inverse: with subst_exp the source rows are read through the substitution x -> x^subst_exp, galois_apply)
+    auto inverse_lds = [&](uint32_t logm, int hr, unsigned grid) {
+        with_bool(map.subst_exp != 0, [&](auto gather) {
+            launch_ntt_lds<true, decltype(gather)::value>(c, "ntt_inv", "ntt_inv_f64", logm, narrow, hr, grid, s, in, out, map,
+                                                          logn);
+        });
+    };
     if (logn <= 14) {
         // every modulus of the launch below 2^50: the FP64-FMA instances (round 6)
-        const int hr = c.f64_class((size_t)((int32_t)map.row_begin + map.mod_offset), map.rows);
-        if (!inverse) {
-            if (launch_ntt_f64<false, false>(c, "ntt_fwd_f64", hr, logn, rows_total, s, in, out, map)) return;
-            // every modulus of the launch below 2^60: the transform without per-stage conditional subtractions
-            bool narrow = !FHE_LAB_FLAG("NO_NARROW");
-            for (uint32_t r = 0; r < map.rows; r++)
-                narrow = narrow && (c.root->moduli[(size_t)((int32_t)(map.row_begin + r) + map.mod_offset)] >> 60) == 0;
+        const int hr = c.f64_rows(first, map.rows);
+        if (inverse) return inverse_lds(logn, hr, rows_total);
 #if defined(FHE_LAB)
-            if (lab_try_ntt_fwd(c, rows_total, narrow, in, out, map, s)) return;   // lab/lab_engine.hpp
+        if (!hr && lab_try_ntt_fwd(c, rows_total, narrow, in, out, map, s)) return;   // lab/lab_engine.hpp
 #endif
-            if (narrow)
-                launch_ntt_lds<false, true>("ntt_fwd", logn, rows_total, s, in, out, map, c.dmods(), c.dtw(), c.dninv(),
-                                            logn);
-            else
-                launch_ntt_lds<false>("ntt_fwd", logn, rows_total, s, in, out, map, c.dmods(), c.dtw(), c.dninv(), logn);
-        } else {
-            bool narrow = !FHE_LAB_FLAG("NO_NARROW");
-            for (uint32_t r = 0; r < map.rows; r++)
-                narrow = narrow && (c.root->moduli[(size_t)((int32_t)(map.row_begin + r) + map.mod_offset)] >> 60) == 0;
-            if (map.subst_exp ? launch_ntt_f64<true, true>(c, "ntt_inv_f64", hr, logn, rows_total, s, in, out, map)
-                               : launch_ntt_f64<true, false>(c, "ntt_inv_f64", hr, logn, rows_total, s, in, out, map))
-                return;
-            if (map.subst_exp) {   // the source rows are read through the substitution x -> x^subst_exp (galois_apply)
-                if (narrow)
-                    launch_ntt_lds<true, true, true>("ntt_inv", logn, rows_total, s, in, out, map, c.dmods(), c.ditw(), c.dninv(), logn);
-                else
-                    launch_ntt_lds<true, false, true>("ntt_inv", logn, rows_total, s, in, out, map, c.dmods(), c.ditw(), c.dninv(), logn);
-            } else if (narrow)
-                launch_ntt_lds<true, true>("ntt_inv", logn, rows_total, s, in, out, map, c.dmods(), c.ditw(), c.dninv(),
-                                           logn);
-            else
-                launch_ntt_lds<true>("ntt_inv", logn, rows_total, s, in, out, map, c.dmods(), c.ditw(), c.dninv(), logn);
-        }
+        launch_ntt_lds<false>(c, "ntt_fwd", "ntt_fwd_f64", logn, narrow, hr, rows_total, s, in, out, map, logn);
         return;
     }
     const uint32_t logm = 13, g0 = logn - logm, m = 1u << logm;
     const unsigned gth = 256, gblocks = rows_total * (m / gth);
-    // every modulus of the launch below 2^60: the LDS halves take the bound-tracked narrow passes here too (round 4;
-    // rounds 1-3 ran rows larger than LDS on the general passes whatever the moduli)
-    bool narrow = !FHE_LAB_FLAG("NO_NARROW") && !FHE_LAB_FLAG("NO_NARROW_SUB");
-    for (uint32_t r = 0; r < map.rows; r++)
-        narrow = narrow && (c.root->moduli[(size_t)((int32_t)(map.row_begin + r) + map.mod_offset)] >> 60) == 0;
+    // the LDS halves take the bound-tracked narrow passes here too (round 4; rounds 1-3 ran rows larger than LDS on the
+    // general passes whatever the moduli)
+    narrow = narrow && !FHE_LAB_FLAG("NO_NARROW_SUB");
     k::RowMap inplace = map;
     inplace.src_poly_stride = map.dst_poly_stride;
     inplace.src_row_fixed = -1;
@@ -887,25 +904,13 @@ inline void launch_ntt(const Ctx &c, bool inverse, const u64 *in, u64 *out, k::R
         else
             FHE_LAUNCH("ntt_fwd_global", (k::ntt_global_kernel<false, 3>), dim3(gblocks), dim3(gth), 0, s, in, out,
                        map, c.dmods(), c.dtw(), c.dninv(), logn);
-        if (narrow) {   // (the global stages above leave values below 4p: FWD_B0 = 4)
-            const size_t lds = k::lds_words(1u << 13) * sizeof(u64);
-            allow_big_lds((k::ntt_kernel<false, 13, true, 4>), lds);
-            FHE_LAUNCH("ntt_fwd", (k::ntt_kernel<false, 13, true, 4>), dim3(rows_total << g0), dim3(k::ntt_threads_c(13)), lds,
-                       s, out, out, inplace, c.dmods(), c.dtw(), c.dninv(), logn);
-        } else {
-            launch_ntt_lds<false>("ntt_fwd", logm, rows_total << g0, s, out, out, inplace, c.dmods(), c.dtw(), c.dninv(),
-                                  logn);
-        }
-    } else {
-        if (map.subst_exp) {
-            if (narrow)
-                launch_ntt_lds<true, true, true>("ntt_inv", logm, rows_total << g0, s, in, out, map, c.dmods(), c.ditw(), c.dninv(), logn);
-            else
-                launch_ntt_lds<true, false, true>("ntt_inv", logm, rows_total << g0, s, in, out, map, c.dmods(), c.ditw(), c.dninv(), logn);
-        } else if (narrow)
-            launch_ntt_lds<true, true>("ntt_inv", logm, rows_total << g0, s, in, out, map, c.dmods(), c.ditw(), c.dninv(), logn);
+        if (narrow)   // (the global stages above leave values below 4p: FWD_B0 = 4)
+            launch_tile<k::ntt_kernel<false, 13, true, 4>>("ntt_fwd", 13, rows_total << g0, s, out, out, inplace, c.dmods(),
+                                                           c.dtw(), c.dninv(), logn);
         else
-            launch_ntt_lds<true>("ntt_inv", logm, rows_total << g0, s, in, out, map, c.dmods(), c.ditw(), c.dninv(), logn);
+            launch_ntt_lds<false>(c, "ntt_fwd", nullptr, logm, false, 0, rows_total << g0, s, out, out, inplace, logn);
+    } else {
+        inverse_lds(logm, 0, rows_total << g0);
         if (g0 == 2)
             FHE_LAUNCH("ntt_inv_global", (k::ntt_global_kernel<true, 2>), dim3(gblocks), dim3(gth), 0, s, out, out,
                        inplace, c.dmods(), c.ditw(), c.dninv(), logn);
@@ -938,48 +943,24 @@ inline k::RowMap full_map(const Ctx &c, size_t rows_in_poly) {
 inline void launch_tensor_intt_rows(const Ctx &e, const k::TensorSrc &ts, u64 *out, size_t nb, uint32_t row_begin,
                                     uint32_t lrows, bool narrow, hipStream_t s, bool reverse, int f64_hr = 0) {
     const uint32_t logn = (uint32_t)e.logn, logm = logn <= 14 ? logn : 13;
-    const size_t lds = k::lds_words(1u << logm) * sizeof(u64);
     // 8 (row, pair, sub-block) combinations x 3 slots per group
     const unsigned groups = (unsigned)(((((size_t)lrows * nb) << (logn - logm)) + 7) / 8);
-    if (f64_hr && logn >= 12 && logn <= 14) {   // round 6: rows below 2^50 on the F64 instances
-#define FHE_TI_F64(LM, HR)                                                                                          \
-    allow_big_lds((k::tensor_intt_kernel<LM, false, false, HR>), lds);                                              \
-    FHE_LAUNCH("tensor_intt_f64", (k::tensor_intt_kernel<LM, false, false, HR>), dim3(groups * 24),                 \
-               dim3(k::ntt_threads_c(LM)), lds, s, ts, out, e.dmods(), e.ditw_f(), e.dninv_f(), (uint32_t)e.L,      \
-               (uint32_t)nb, logn, row_begin, lrows, reverse ? 1u : 0u);
-#define FHE_TI_F64_HR(LM)                               \
-    case LM:                                            \
-        if (f64_hr == 3) { FHE_TI_F64(LM, 3) }          \
-        else if (f64_hr == 4) { FHE_TI_F64(LM, 4) }     \
-        else { FHE_TI_F64(LM, 5) }                      \
-        break;
-        switch (logn) { FHE_TI_F64_HR(12) FHE_TI_F64_HR(13) FHE_TI_F64_HR(14) }
-#undef FHE_TI_F64_HR
-#undef FHE_TI_F64
+    auto launch = [&](auto kernel, bool nrw, bool f64) {
+        launch_tile<decltype(kernel)::value>(f64 ? "tensor_intt_f64" : nrw ? "tensor_intt_narrow" : "tensor_intt", (int)logm,
+                                             groups * 24, s, ts, out, e.dmods(), f64 ? e.ditw_f() : e.ditw(),
+                                             f64 ? e.dninv_f() : e.dninv(), (uint32_t)e.L, (uint32_t)nb, logn, row_begin, lrows,
+                                             reverse ? 1u : 0u);
+    };
+    if (logn > 14) {   // 8192-point sub-blocks
+        with_bool(narrow,
+                  [&](auto nrw) { launch(kernel_c<k::tensor_intt_kernel<13, true, decltype(nrw)::value>>{}, nrw, false); });
         return;
     }
-#define FHE_TI_LAUNCH(LM, SUB, NRW)                                                                              \
-    allow_big_lds((k::tensor_intt_kernel<LM, SUB, NRW>), lds);                                                   \
-    FHE_LAUNCH((NRW ? "tensor_intt_narrow" : "tensor_intt"), (k::tensor_intt_kernel<LM, SUB, NRW>), dim3(groups * 24), \
-               dim3(k::ntt_threads_c(LM)), lds, s, ts, out, e.dmods(), e.ditw(), e.dninv(), (uint32_t)e.L,       \
-               (uint32_t)nb, logn, row_begin, lrows, reverse ? 1u : 0u);
-#define FHE_TI_CASE(LM)                               \
-    case LM:                                          \
-        if (narrow) { FHE_TI_LAUNCH(LM, false, true) } \
-        else { FHE_TI_LAUNCH(LM, false, false) }       \
-        break;
-    if (logn > 14) {
-        if (narrow) { FHE_TI_LAUNCH(13, true, true) }
-        else { FHE_TI_LAUNCH(13, true, false) }
-        return;
-    }
-    switch (logn) {
-        FHE_TI_CASE(3) FHE_TI_CASE(4) FHE_TI_CASE(5) FHE_TI_CASE(6) FHE_TI_CASE(7) FHE_TI_CASE(8)
-        FHE_TI_CASE(9) FHE_TI_CASE(10) FHE_TI_CASE(11) FHE_TI_CASE(12) FHE_TI_CASE(13) FHE_TI_CASE(14)
-        default: throw StatusError(E_ARG, "unsupported tensor tile size");
-    }
-#undef FHE_TI_CASE
-#undef FHE_TI_LAUNCH
+    // (round 6: rows below 2^50 on the F64 instances)
+    with_tile(logn, "unsupported tensor tile size", narrow, f64_hr, [&](auto lm, auto nrw, auto h) {
+        constexpr int HR = decltype(h)::value;
+        launch(kernel_c<k::tensor_intt_kernel<decltype(lm)::value, false, decltype(nrw)::value, HR>>{}, nrw, HR != 0);
+    });
 }
 
 inline void launch_tensor_intt(const Ctx &e, const k::TensorSrc &ts, u64 *out, size_t nb, hipStream_t s, bool reverse) {
@@ -1001,8 +982,7 @@ inline void launch_tensor_intt(const Ctx &e, const k::TensorSrc &ts, u64 *out, s
         int kind;   // 0: general passes, 1: moduli below 2^60 (narrow passes), 2: below 2^50 (round 6: the F64 instances)
     };
     std::vector<Run> runs;
-    const bool f64_rows = allow && e.logn >= 12 && e.logn <= 14 && e.root->d_tw_f.p && !f64_disabled();
-    auto kind_of = [&](uint32_t r) { return !allow ? 0 : (f64_rows && (e.moduli[r] >> 50) == 0) ? 2 : (e.moduli[r] >> 60) == 0 ? 1 : 0; };
+    auto kind_of = [&](uint32_t r) { return !allow ? 0 : e.f64_rows(r, 1) ? 2 : e.below_2p60(r, 1) ? 1 : 0; };
     uint32_t r0 = 0;
     while (r0 < e.L) {
         const int kd = kind_of(r0);
@@ -1109,18 +1089,23 @@ struct Scaler {
     k::ScalerDev dev{};
 };
 
-// NF of the scale_kernel<NF> instance for `nfrom` source moduli (the column's residues live in registers)
+// The NF of the scale_kernel<NF> instances (the column's residues live in registers: NF >= the source moduli).
+// 4 / 9 / 17 / 33: the operand and product bases of BASELINE's configs (L = 4, 8, 16; K = 9, 17, 33).  Round 5 added
+// 6 / 12 / 20 for the reference's stock sets (default_parameters_128: L = 3, 5, 9 and K = 6, 10, 18), which ran on
+// the next instance up -- K = 10 on NF = 17, K = 18 on NF = 33: up to 1.8 x the term loops, all of it zero padding.
+// Round 6: the exact fits that were still padded -- 3 / 5 / 10 / 18 (stock sets: L = 3 on NF = 4, L = 5 on 6, K = 10 on
+// 12, K = 18 on 20: 10-25 % of the terms were zeros) and 8 / 16 (C3's and C5's operand bases, on 9 and 17); 14 / 23 /
+// 27 / 31 for the levels of C5's chain (L = 15 ... 10: K = 31, 29, 27, 25, 23, 21 all ran on NF = 33, up to 57 % padding).
+using ScaleNFs = std::integer_sequence<int, 3, 4, 5, 6, 8, 9, 10, 12, 14, 16, 17, 18, 20, 23, 27, 31, 33, 64>;
+// f(int_c<NF>) for the smallest NF that holds `nfrom` source moduli; false when there is none
+template <int... NF, class F>
+inline bool with_scale_nf(size_t nfrom, std::integer_sequence<int, NF...>, F &&f) {
+    return ((nfrom <= (size_t)NF && (f(int_c<NF>{}), true)) || ...);
+}
 inline size_t scale_kernel_nf(size_t nfrom) {
-    // 4 / 9 / 17 / 33: the operand and product bases of BASELINE's configs (L = 4, 8, 16; K = 9, 17, 33).  Round 5 added
-    // 6 / 12 / 20 for the reference's stock sets (default_parameters_128: L = 3, 5, 9 and K = 6, 10, 18), which ran on
-    // the next instance up -- K = 10 on NF = 17, K = 18 on NF = 33: up to 1.8 x the term loops, all of it zero padding.
-    // Round 6: the exact fits that were still padded -- 3 / 5 / 10 / 18 (stock sets: L = 3 on NF = 4, L = 5 on 6, K = 10 on
-    // 12, K = 18 on 20: 10-25 % of the terms were zeros) and 8 / 16 (C3's and C5's operand bases, on 9 and 17); 14 / 23 /
-    // 27 / 31 for the levels of C5's chain (L = 15 ... 10: K = 31, 29, 27, 25, 23, 21 all ran on NF = 33, up to 57 % padding).
-    static constexpr size_t fits[] = {3, 4, 5, 6, 8, 9, 10, 12, 14, 16, 17, 18, 20, 23, 27, 31, 33};
-    for (size_t nf : fits)
-        if (nfrom <= nf) return nf;
-    return 64;
+    size_t nf = 64;   // (more than 64 source moduli: refused by scaler_upload and launch_scale)
+    with_scale_nf(nfrom, ScaleNFs{}, [&](auto c) { nf = (size_t)decltype(c)::value; });
+    return nf;
 }
 
 inline void scaler_upload(Scaler &s) {
@@ -1300,39 +1285,17 @@ inline void launch_scale(const Scaler &sc, const u64 *in, u64 in_stride, u64 *ou
     // PLAIN instances carry no w / v_hi code: factor-one scalers whose v fits one word (every basis extension of BFV)
     const bool plain = sc.dev.is_one && sc.dev.v_fits_64;
     const uint32_t asc = ascending ? 1u : 0u;
-#define FHE_SCALE_CASE(NF)                                                                                   \
-    if (plain)                                                                                               \
-        FHE_LAUNCH(label, (k::scale_kernel<NF, true>), grid, block, 0, s, in, out, in_stride, out_stride,    \
-                   sc.dev, t.dmods(), (uint32_t)f.logn, total, asc);                                         \
-    else if (sc.dev.wide_w)   /* the reference's bit tests on an out-of-range t, to the letter */             \
-        FHE_LAUNCH(label, (k::scale_kernel<NF, false, true>), grid, block, 0, s, in, out, in_stride,         \
-                   out_stride, sc.dev, t.dmods(), (uint32_t)f.logn, total, asc);                             \
-    else                                                                                                     \
-        FHE_LAUNCH(label, (k::scale_kernel<NF, false>), grid, block, 0, s, in, out, in_stride, out_stride,   \
-                   sc.dev, t.dmods(), (uint32_t)f.logn, total, asc)
-    switch (scale_kernel_nf(f.L)) {   // (the same NF scaler_upload padded the tables to)
-        case 3: FHE_SCALE_CASE(3); break;
-        case 4: FHE_SCALE_CASE(4); break;
-        case 5: FHE_SCALE_CASE(5); break;
-        case 6: FHE_SCALE_CASE(6); break;
-        case 8: FHE_SCALE_CASE(8); break;
-        case 9: FHE_SCALE_CASE(9); break;
-        case 10: FHE_SCALE_CASE(10); break;
-        case 12: FHE_SCALE_CASE(12); break;
-        case 14: FHE_SCALE_CASE(14); break;
-        case 16: FHE_SCALE_CASE(16); break;
-        case 17: FHE_SCALE_CASE(17); break;
-        case 18: FHE_SCALE_CASE(18); break;
-        case 20: FHE_SCALE_CASE(20); break;
-        case 23: FHE_SCALE_CASE(23); break;
-        case 27: FHE_SCALE_CASE(27); break;
-        case 31: FHE_SCALE_CASE(31); break;
-        case 33: FHE_SCALE_CASE(33); break;
-        default:
-            require(f.L <= 64, E_ARG, "RNS scaler supports at most 64 source moduli");
-            FHE_SCALE_CASE(64);
-    }
-#undef FHE_SCALE_CASE
+    require(f.L <= 64, E_ARG, "RNS scaler supports at most 64 source moduli");
+    with_scale_nf(f.L, ScaleNFs{}, [&](auto nf) {   // (the same NF scaler_upload padded the tables to)
+        constexpr int NF = decltype(nf)::value;
+        auto launch = [&](auto kernel) {
+            launch_k<decltype(kernel)::value>(label, grid, block, 0, s, in, out, in_stride, out_stride, sc.dev, t.dmods(),
+                                              (uint32_t)f.logn, total, asc);
+        };
+        if (plain) launch(kernel_c<k::scale_kernel<NF, true>>{});
+        else if (sc.dev.wide_w) launch(kernel_c<k::scale_kernel<NF, false, true>>{});   // the reference's bit tests on an out-of-range t, to the letter
+        else launch(kernel_c<k::scale_kernel<NF, false>>{});
+    });
 }
 
 // Scaler::scale (M/rq/scaler.rs:55-127) on npolys polynomials.
@@ -1517,8 +1480,7 @@ inline void launch_ks_fused(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0, 
 #endif
     const size_t lds = (k::lds_words(1u << LOGN) + (k::ks_acc1_in_lds_c(LOGN) ? (size_t)1 << LOGN : 0)) * sizeof(u64);
     // key moduli below 2^60: the transform runs without most conditional subtractions (fwd_butterfly_narrow)
-    bool narrow = !FHE_LAB_FLAG("NO_NARROW");
-    for (u64 q : kc.moduli) narrow = narrow && (q >> 60) == 0;
+    const bool narrow = !FHE_LAB_FLAG("NO_NARROW") && kc.below_2p60(0, kc.L);
     // N = 16384 (ks_fused_kernel's GM): radix-8 while the twiddles are scalar, radix-4 after (GM_MIXED).  Lab builds:
     // FHE_LAB_KS14_PLAN = 8 radix-8 passes throughout (24 VGPRs spilled), 4 radix-4 passes throughout.
     static const int plan14 = FHE_LAB_INT("KS14_PLAN", 0);
@@ -1537,6 +1499,15 @@ inline void launch_ks_fused(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0, 
     // round 3 that instance spilled 52 B; it no longer does, and measured again at C3 in round 4 it changes nothing --
     // relinearise of 512: 4.09 / 4.18 / 4.18 ms against 4.17 / 4.14 / 4.13, profiles/r04_ks14_rns_ab.jsonl.)
     const bool rns = (LOGN == 12 || LOGN == 13) && k_.digit_arg() == (1u << 8);
+    const uint32_t items = (uint32_t)(npolys * kc.L);
+    const size_t lds_tile = k::lds_words(1u << LOGN) * sizeof(u64);   // (tile-only LDS: both accumulator sets in registers)
+    // one launch of ks_fused_kernel; the F64 instances read the key's F64 words and the F64 tables
+    auto launch = [&](const char *name, auto kernel, unsigned grid, int threads, size_t lds_k, bool f64) {
+        launch_k<decltype(kernel)::value>(
+            name, dim3(grid), dim3(threads), lds_k, s, p, p_stride, o0, o1, out_stride, a0, a1, a_stride, f64 ? k_.c0f.p : k_.c0.p,
+            f64 ? k_.c0f.p : k_.c0s.p, f64 ? k_.c1f.p : k_.c1.p, f64 ? k_.c1f.p : k_.c1s.p, kc.dmods(), f64 ? kc.dtw_f() : kc.dtw(),
+            (uint32_t)k_.ndigits, (uint32_t)kc.L, k_.digit_arg(), xhat, xhat_stride, items, gal);
+    };
     // Round 6: every key modulus below 2^50 and RNS digits -> the F64 instances (no lift: any residue row of the basis is
     // a representative under every key modulus, whatever the widths)
     if constexpr (LOGN >= 12 && LOGN <= 14) {
@@ -1555,160 +1526,81 @@ inline void launch_ks_fused(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0, 
             // r06_m_f64_ks_modes_grid.jsonl) -- so the 512-thread instance is taken from the second workgroup per CU on.
             constexpr int F64_TT = (LOGN == 13 || (LOGN == 12 && FHE_KS12_F64_T256)) ? (1 << LOGN) / 16 : 0;
             const bool two_per_cu = F64_TT != 0 && npolys * kc.L > (size_t)device_cus(kc.device);
-#define FHE_KS_F64_G(GMV, GALV, HR, TTV)                                                                               \
-    do {                                                                                                               \
-        const size_t lds_f = TTV ? k::lds_words(1u << LOGN) * sizeof(u64) : lds;                                       \
-        const unsigned grid_f = TTV ? (unsigned)(npolys * kc.L) : ks_grid;                                             \
-        allow_big_lds((k::ks_fused_kernel<LOGN, false, GMV, TTV, true, 0, GALV, HR>), lds_f);                          \
-        FHE_LAUNCH("key_switch_fused_f64", (k::ks_fused_kernel<LOGN, false, GMV, TTV, true, 0, GALV, HR>),             \
-                   dim3(grid_f), dim3(k::ks_threads_tt(LOGN, TTV)), lds_f, s, p, p_stride, o0, o1, out_stride, a0, a1, \
-                   a_stride, k_.c0f.p, k_.c0f.p, k_.c1f.p, k_.c1f.p, kc.dmods(), kc.dtw_f(), (uint32_t)k_.ndigits,     \
-                   (uint32_t)kc.L, k_.digit_arg(), xhat, xhat_stride, (uint32_t)(npolys * kc.L), gal);                 \
-    } while (0)
-#define FHE_KS_F64_T(GMV, GALV, HR)                                                                                    \
-    do {                                                                                                               \
-        if constexpr (F64_TT != 0) {                                                                                   \
-            if (two_per_cu) {                                                                                          \
-                FHE_KS_F64_G(GMV, GALV, HR, F64_TT);                                                                   \
-                break;                                                                                                 \
-            }                                                                                                          \
-        }                                                                                                              \
-        FHE_KS_F64_G(GMV, GALV, HR, 0);                                                                                \
-    } while (0)
-#define FHE_KS_F64(HR)                                                                                                 \
-    do {                                                                                                               \
-        constexpr int GMV = k::KS_GMAX;   /* radix-8 passes at every size: one-word twiddles leave the N = 16384 tile room */ \
-        if (gal) {                                                                                                     \
-            FHE_KS_F64_T(GMV, true, HR);                                                                               \
-        } else {                                                                                                       \
-            FHE_KS_F64_T(GMV, false, HR);                                                                              \
-        }                                                                                                              \
-    } while (0)
-            if (hr == 3) FHE_KS_F64(3);
-            else if (hr == 4) FHE_KS_F64(4);
-            else FHE_KS_F64(5);
-#undef FHE_KS_F64
-#undef FHE_KS_F64_T
-#undef FHE_KS_F64_G
+            constexpr int GMV = k::KS_GMAX;   // radix-8 passes at every size: one-word twiddles leave the N = 16384 tile room
+            with_row_kind<LOGN>(false, hr, [&](auto, auto h) {
+                constexpr int HR = decltype(h)::value;
+                if constexpr (HR != 0)
+                    with_bool(gal != 0, [&](auto galv) {
+                        with_bool(two_per_cu, [&](auto two) {
+                            constexpr int TTV = decltype(two)::value ? F64_TT : 0;
+                            launch("key_switch_fused_f64",
+                                   kernel_c<k::ks_fused_kernel<LOGN, false, GMV, TTV, true, 0, decltype(galv)::value, HR>>{},
+                                   TTV ? items : ks_grid, k::ks_threads_tt(LOGN, TTV), TTV ? lds_tile : lds, true);
+                        });
+                    });
+            });
             return;
         }
     }
-#define FHE_KS_LAUNCH_G(NW, GMV, RNS, GALV)                                                                           \
-    allow_big_lds((k::ks_fused_kernel<LOGN, NW, GMV, 0, RNS, 0, GALV>), lds);                                         \
-    FHE_LAUNCH("key_switch_fused", (k::ks_fused_kernel<LOGN, NW, GMV, 0, RNS, 0, GALV>), dim3(ks_grid),               \
-               dim3(k::ks_threads_c(LOGN)), lds, s, p, p_stride, o0, o1, out_stride, a0, a1, a_stride, k_.c0.p,       \
-               k_.c0s.p, k_.c1.p, k_.c1s.p, kc.dmods(), kc.dtw(), (uint32_t)k_.ndigits, (uint32_t)kc.L,               \
-               k_.digit_arg(), xhat, xhat_stride, (uint32_t)(npolys * kc.L), gal)
-    // (the Galois instances exist from N = 4096 on: galois_apply folds the substitution only there)
-#define FHE_KS_LAUNCH_R(NW, GMV, RNS)                                                                                 \
-    do {                                                                                                              \
-        if constexpr (LOGN >= 12) {                                                                                   \
-            if (gal) {                                                                                                \
-                FHE_KS_LAUNCH_G(NW, GMV, RNS, true);                                                                  \
-            } else {                                                                                                  \
-                FHE_KS_LAUNCH_G(NW, GMV, RNS, false);                                                                 \
-            }                                                                                                         \
-        } else {                                                                                                      \
-            require(!gal, E_ARG, "folded Galois substitution below N = 4096");                                        \
-            FHE_KS_LAUNCH_G(NW, GMV, RNS, false);                                                                     \
-        }                                                                                                             \
-    } while (0)
-#define FHE_KS_LAUNCH(NW, GMV)                                                                                        \
-    do {                                                                                                              \
-        if constexpr (LOGN == 12 || LOGN == 13) {                                                                     \
-            if (rns) {                                                                                                \
-                FHE_KS_LAUNCH_R(NW, GMV, true);                                                                       \
-            } else {                                                                                                  \
-                FHE_KS_LAUNCH_R(NW, GMV, false);                                                                      \
-            }                                                                                                         \
-        } else {                                                                                                      \
-            FHE_KS_LAUNCH_R(NW, GMV, false);                                                                          \
-        }                                                                                                             \
-    } while (0)
 #if defined(FHE_LAB)
     if constexpr (LOGN == 13) {
         // FHE_LAB_KS13_T512 = 1: 512 threads x 16 coefficients, both accumulator sets in registers, tile-only LDS (two
         // workgroups per CU), mixed radix-8 / radix-4 passes; = 2: the same with radix-4 passes throughout
         static const int t512 = FHE_LAB_INT("KS13_T512", 0);
         if (t512 && !gal) {   // (the 512-thread lab instances have no gathering loader: a folded rotation takes the product launch)
-            const size_t lds2 = k::lds_words(1u << LOGN) * sizeof(u64);
-            const unsigned grid2 = (unsigned)(npolys * kc.L);
-#define FHE_KS_T512_R(NW, GMV, RNS)                                                                                \
-    allow_big_lds((k::ks_fused_kernel<LOGN, NW, GMV, 512, RNS>), lds2);                                            \
-    FHE_LAUNCH("key_switch_fused", (k::ks_fused_kernel<LOGN, NW, GMV, 512, RNS>), dim3(grid2), dim3(512), lds2, s, \
-               p, p_stride, o0, o1, out_stride, a0, a1, a_stride, k_.c0.p, k_.c0s.p, k_.c1.p, k_.c1s.p,            \
-               kc.dmods(), kc.dtw(), (uint32_t)k_.ndigits, (uint32_t)kc.L, k_.digit_arg(), xhat, xhat_stride, grid2, gal)
-#define FHE_KS_T512(NW, GMV)                                                                                       \
-    do {                                                                                                           \
-        if (rns) {                                                                                                 \
-            FHE_KS_T512_R(NW, GMV, true);                                                                          \
-        } else {                                                                                                   \
-            FHE_KS_T512_R(NW, GMV, false);                                                                         \
-        }                                                                                                          \
-    } while (0)
-            if (t512 == 2) {
-                if (narrow) { FHE_KS_T512(true, 2); } else { FHE_KS_T512(false, 2); }
-            } else if (t512 == 3) {
-                if (narrow) { FHE_KS_T512(true, k::KS_GMAX); } else { FHE_KS_T512(false, k::KS_GMAX); }
-            } else {
-                if (narrow) { FHE_KS_T512(true, k::GM_MIXED); } else { FHE_KS_T512(false, k::GM_MIXED); }
-            }
-#undef FHE_KS_T512
-#undef FHE_KS_T512_R
+            auto launch512 = [&](auto gm) {
+                with_bool(narrow, [&](auto nw) {
+                    with_bool(rns, [&](auto r) {
+                        launch("key_switch_fused",
+                               kernel_c<k::ks_fused_kernel<LOGN, decltype(nw)::value, decltype(gm)::value, 512, decltype(r)::value>>{},
+                               items, 512, lds_tile, false);
+                    });
+                });
+            };
+            if (t512 == 2) launch512(int_c<2>{});
+            else if (t512 == 3) launch512(int_c<k::KS_GMAX>{});
+            else launch512(int_c<k::GM_MIXED>{});
             return;
         }
     }
-#endif
-#if defined(FHE_LAB)
     if constexpr (LOGN == 14) {
         // FHE_LAB_KS14_T512 = 1: 512 threads x 32 coefficients, 256 VGPRs (two waves per SIMD), both accumulator sets in
         // registers, radix-16 passes (GM = 4), the RNS loader; = 2: the same with radix-8 passes
         static const int t512 = FHE_LAB_INT("KS14_T512", 0);
         if (t512 && !gal && k_.digit_arg() == (1u << 8)) {
-            const size_t lds2 = k::lds_words(1u << LOGN) * sizeof(u64);
-            const unsigned grid2 = (unsigned)(npolys * kc.L);
-#define FHE_KS14_T512(NW, GMV)                                                                                         \
-    allow_big_lds((k::ks_fused_kernel<LOGN, NW, GMV, 512, true>), lds2);                                               \
-    FHE_LAUNCH("key_switch_fused", (k::ks_fused_kernel<LOGN, NW, GMV, 512, true>), dim3(grid2), dim3(512), lds2, s, p, \
-               p_stride, o0, o1, out_stride, a0, a1, a_stride, k_.c0.p, k_.c0s.p, k_.c1.p, k_.c1s.p, kc.dmods(),       \
-               kc.dtw(), (uint32_t)k_.ndigits, (uint32_t)kc.L, k_.digit_arg(), xhat, xhat_stride, grid2, gal)
-            if (t512 == 2) {
-                if (narrow) { FHE_KS14_T512(true, 3); } else { FHE_KS14_T512(false, 3); }
-            } else {
-                if (narrow) { FHE_KS14_T512(true, 4); } else { FHE_KS14_T512(false, 4); }
-            }
-#undef FHE_KS14_T512
+            with_bool(narrow, [&](auto nw) {
+                with_bool(t512 == 2, [&](auto radix8) {
+                    launch("key_switch_fused",
+                           kernel_c<k::ks_fused_kernel<LOGN, decltype(nw)::value, decltype(radix8)::value ? 3 : 4, 512, true>>{},
+                           items, 512, lds_tile, false);
+                });
+            });
             return;
         }
     }
 #endif
+    if constexpr (LOGN < 12) require(!gal, E_ARG, "folded Galois substitution below N = 4096");
+    // the integer instances with GM = gm
+    auto launch_gm = [&](auto gm) {
+        with_bool(narrow, [&](auto nw) {
+            with_bool(rns, [&](auto r) {
+                with_bool(gal != 0, [&](auto g) {
+                    // (RNS: see `rns` above; the Galois instances exist from N = 4096 on: galois_apply folds the
+                    // substitution only there)
+                    constexpr bool RNS = decltype(r)::value && (LOGN == 12 || LOGN == 13);
+                    constexpr bool GALV = decltype(g)::value && LOGN >= 12;
+                    launch("key_switch_fused",
+                           kernel_c<k::ks_fused_kernel<LOGN, decltype(nw)::value, decltype(gm)::value, 0, RNS, 0, GALV>>{},
+                           ks_grid, k::ks_threads_c(LOGN), lds, false);
+                });
+            });
+        });
+    };
     if constexpr (LOGN == 14) {   // (radix-4 passes at N = 8192 measured slower: 0.559 vs 0.532 ms per launch)
-        if (plan14 == 4) {
-            if (narrow) {
-                FHE_KS_LAUNCH(true, 2);
-            } else {
-                FHE_KS_LAUNCH(false, 2);
-            }
-            return;
-        }
-        if (plan14 != 8) {
-            if (narrow) {
-                FHE_KS_LAUNCH(true, k::GM_MIXED);
-            } else {
-                FHE_KS_LAUNCH(false, k::GM_MIXED);
-            }
-            return;
-        }
+        if (plan14 == 4) return launch_gm(int_c<2>{});
+        if (plan14 != 8) return launch_gm(int_c<k::GM_MIXED>{});
     }
-    if (narrow) {
-        FHE_KS_LAUNCH(true, k::KS_GMAX);
-    } else {
-        FHE_KS_LAUNCH(false, k::KS_GMAX);
-    }
-#undef FHE_KS_LAUNCH
-#undef FHE_KS_LAUNCH_R
-#undef FHE_KS_LAUNCH_G
-    (void)rns;
+    launch_gm(int_c<k::KS_GMAX>{});
 }
 
 // ---- unfused key switch (kernels_ks.hpp: ks_ntt_kernel + ks_mac_kernel) ----
@@ -1784,40 +1676,28 @@ template <int LOGM, int G0>
 inline void launch_ks_ntt(const Ksk &k_, bool narrow, bool rns, unsigned grid, hipStream_t s, const u64 *p, u64 p_stride,
                           u64 *w, uint32_t j0, uint32_t jg, uint32_t skip_own, const KsExtraFwd *extra = nullptr) {
     const Ctx &kc = *k_.ksk_ctx;
-    const size_t lds = k::lds_words(1u << LOGM) * sizeof(u64);
     const bool with_extra = G0 == 0 && extra != nullptr && extra->rows != nullptr;
     u64 *const erows = with_extra ? extra->rows : nullptr;
     const u64 estride = with_extra ? extra->poly_stride : 0;
     const uint32_t enr = with_extra ? (uint32_t)extra->nrows : 1u;
     const unsigned egrid = with_extra ? (unsigned)(extra->npolys * extra->nrows) : 0u;
-#define FHE_KSN(NW, RNS)                                                                                         \
-    allow_big_lds((k::ks_ntt_kernel<LOGM, G0, NW, RNS>), lds);                                                   \
-    FHE_LAUNCH("ks_digit_ntt", (k::ks_ntt_kernel<LOGM, G0, NW, RNS>), dim3(grid + egrid), dim3(k::ntt_threads_c(LOGM)), \
-               lds, s, p, p_stride, w, kc.dmods(), kc.dtw(), (uint32_t)k_.ndigits, j0, jg, k_.digit_arg(), skip_own,   \
-               erows, estride, enr, (uint32_t)grid)
+    auto launch = [&](const char *name, auto kernel, const k::u64x2 *tw) {
+        launch_tile<decltype(kernel)::value>(name, LOGM, grid + egrid, s, p, p_stride, w, kc.dmods(), tw, (uint32_t)k_.ndigits,
+                                             j0, jg, k_.digit_arg(), skip_own, erows, estride, enr, (uint32_t)grid);
+    };
     // Round 6: RNS digits under key moduli that are all below 2^50 -> the F64 stage A (whole-row tiles of 4096 ... 16384
     // points; W in canonical words, so stage B is unchanged)
-    if constexpr (G0 == 0 && LOGM >= 12 && LOGM <= 14) {
-        const int hr = k_.log_base == 0 ? kc.f64_class(0, kc.L) : 0;
-#define FHE_KSN_F64(HR)                                                                                                 \
-    allow_big_lds((k::ks_ntt_kernel<LOGM, 0, false, true, HR>), lds);                                                   \
-    FHE_LAUNCH("ks_digit_ntt_f64", (k::ks_ntt_kernel<LOGM, 0, false, true, HR>), dim3(grid + egrid),                    \
-               dim3(k::ntt_threads_c(LOGM)), lds, s, p, p_stride, w, kc.dmods(), kc.dtw_f(), (uint32_t)k_.ndigits, j0,  \
-               jg, k_.digit_arg(), skip_own, erows, estride, enr, (uint32_t)grid)
-        if (hr == 3) { FHE_KSN_F64(3); return; }
-        if (hr == 4) { FHE_KSN_F64(4); return; }
-        if (hr == 5) { FHE_KSN_F64(5); return; }
-#undef FHE_KSN_F64
-    }
-    if constexpr (LOGM >= 12) {
-        if (rns) {
-            if (narrow) { FHE_KSN(true, true); } else { FHE_KSN(false, true); }
-            return;
-        }
-    }
-    if (narrow) { FHE_KSN(true, false); } else { FHE_KSN(false, false); }
-#undef FHE_KSN
-    (void)rns;
+    const int hr = G0 == 0 && k_.log_base == 0 ? kc.f64_rows(0, kc.L) : 0;
+    with_row_kind<G0 == 0 ? LOGM : 0>(narrow, hr, [&](auto nw, auto h) {   // (no F64 instances on sub-block tiles)
+        constexpr int HR = decltype(h)::value;
+        if constexpr (HR != 0)
+            launch("ks_digit_ntt_f64", kernel_c<k::ks_ntt_kernel<LOGM, 0, false, true, HR>>{}, kc.dtw_f());
+        else
+            with_bool(rns, [&](auto r) {   // (the RNS instances exist from N = 4096 on)
+                constexpr bool RNS = decltype(r)::value && LOGM >= 12;
+                launch("ks_digit_ntt", kernel_c<k::ks_ntt_kernel<LOGM, G0, decltype(nw)::value, RNS>>{}, kc.dtw());
+            });
+    });
 }
 inline void key_switch_polys_unfused(const Ksk &k_, int mode, const u64 *p, u64 p_stride, u64 *o0, u64 *o1,
                                      u64 out_stride, const u64 *a0, const u64 *a1, u64 a_stride, size_t npolys,
@@ -1835,8 +1715,7 @@ inline void key_switch_polys_unfused(const Ksk &k_, int mode, const u64 *p, u64 
                                       (mode == KS_AUTO && !extra && 2 * npolys * nd * Lk <= (size_t)device_cus(kc.device)));
     const uint32_t logm = logn > 14 ? 13 : sub14 ? 13 : logn;
     const uint32_t g0 = logn - logm;
-    bool narrow = !FHE_LAB_FLAG("NO_NARROW");
-    for (u64 q : kc.moduli) narrow = narrow && (q >> 60) == 0;
+    const bool narrow = !FHE_LAB_FLAG("NO_NARROW") && kc.below_2p60(0, kc.L);
     const bool rns = k_.digit_arg() == (1u << 8);
     // W = [pc][nd][jg][N]: groups of jg key moduli over chunks of pc polynomials, as large as the budget allows
     // (key-modulus groups are cut first: a group's key slice is then still read once per launch pair)
@@ -1869,22 +1748,15 @@ inline void key_switch_polys_unfused(const Ksk &k_, int mode, const u64 *p, u64 
             const size_t njg = std::min(jg, Lk - j0);
             const unsigned grid_a = (unsigned)((nb * nd * njg) << g0);
             const u64 *pp = p + b0 * p_stride;
-#define FHE_KSN_CASE(LM)                                                                                         \
-    case LM: launch_ks_ntt<LM, 0>(k_, narrow, rns, grid_a, s, pp, p_stride, w.u(), (uint32_t)j0, (uint32_t)njg, skip_own, ride); break;
-            if (g0 == 0) {
-                switch (logm) {
-                    FHE_KSN_CASE(3) FHE_KSN_CASE(4) FHE_KSN_CASE(5) FHE_KSN_CASE(6) FHE_KSN_CASE(7) FHE_KSN_CASE(8)
-                    FHE_KSN_CASE(9) FHE_KSN_CASE(10) FHE_KSN_CASE(11) FHE_KSN_CASE(12) FHE_KSN_CASE(13) FHE_KSN_CASE(14)
-                    default: throw StatusError(E_ARG, "unsupported key-switch row size");
-                }
-            } else if (g0 == 1) {
-                launch_ks_ntt<13, 1>(k_, narrow, rns, grid_a, s, pp, p_stride, w.u(), (uint32_t)j0, (uint32_t)njg, skip_own);
-            } else if (g0 == 2) {
-                launch_ks_ntt<13, 2>(k_, narrow, rns, grid_a, s, pp, p_stride, w.u(), (uint32_t)j0, (uint32_t)njg, skip_own);
-            } else {
-                launch_ks_ntt<13, 3>(k_, narrow, rns, grid_a, s, pp, p_stride, w.u(), (uint32_t)j0, (uint32_t)njg, skip_own);
-            }
-#undef FHE_KSN_CASE
+            auto stage_a = [&](auto lm, auto g, const KsExtraFwd *ex) {
+                launch_ks_ntt<decltype(lm)::value, decltype(g)::value>(k_, narrow, rns, grid_a, s, pp, p_stride, w.u(), (uint32_t)j0,
+                                                                       (uint32_t)njg, skip_own, ex);
+            };
+            if (g0 == 0)
+                with_logn<3, 14>(logm, "unsupported key-switch row size", [&](auto lm) { stage_a(lm, int_c<0>{}, ride); });
+            else if (g0 == 1) stage_a(int_c<13>{}, int_c<1>{}, nullptr);
+            else if (g0 == 2) stage_a(int_c<13>{}, int_c<2>{}, nullptr);
+            else stage_a(int_c<13>{}, int_c<3>{}, nullptr);
             const uint32_t cpr = N >= 512 ? (uint32_t)(N / 512) : 1u;
             const unsigned grid_b = (unsigned)((((njg * cpr) + 7) / 8) * nb * 8);
             FHE_LAUNCH("ks_mac", k::ks_mac_kernel, dim3(grid_b), dim3(256), 0, s, w.u(), o0 + b0 * out_stride,
@@ -1935,19 +1807,14 @@ inline void key_switch_polys(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0,
     // accumulators: two workgroups per CU), the first stage folded into the loader
     static const bool half13 = FHE_LAB_INT("KS_HALF13", 0) != 0;
     if (kc.logn <= 12 || (kc.logn == 13 && !half13) || (kc.logn == 14 && !split14)) {
-#define FHE_KS_CASE(LN) \
-    case LN: launch_ks_fused<LN>(k_, p, p_stride, o0, o1, out_stride, a0, a1, a_stride, npolys, s, xhat, xhat_stride, gal); break;
-        switch (kc.logn) {
-            FHE_KS_CASE(3) FHE_KS_CASE(4) FHE_KS_CASE(5) FHE_KS_CASE(6) FHE_KS_CASE(7) FHE_KS_CASE(8)
-            FHE_KS_CASE(9) FHE_KS_CASE(10) FHE_KS_CASE(11) FHE_KS_CASE(12) FHE_KS_CASE(13) FHE_KS_CASE(14)
-            default: throw StatusError(E_ARG, "unsupported key-switch row size");
-        }
-#undef FHE_KS_CASE
+        with_logn<3, 14>(kc.logn, "unsupported key-switch row size", [&](auto ln) {
+            launch_ks_fused<decltype(ln)::value>(k_, p, p_stride, o0, o1, out_stride, a0, a1, a_stride, npolys, s, xhat, xhat_stride,
+                                                 gal);
+        });
         return;
     }
     // Rows larger than LDS (N >= 32768): one workgroup per part of a row, the first stages folded into its loader.
-    bool narrow = !FHE_LAB_FLAG("NO_NARROW");
-    for (u64 q : kc.moduli) narrow = narrow && (q >> 60) == 0;
+    const bool narrow = !FHE_LAB_FLAG("NO_NARROW") && kc.below_2p60(0, kc.L);
     // N = 32768 / 65536 as two / four 16384-point parts on the N = 16384 kernel (one / two folded stages, knobs.hpp
     // FHE_KS_HALF15: 1 the generic loader, 2 the RNS loader where the key's digits are residue rows) -- 15 % ahead of the
     // 8192-point sub-blocks below once a launch fills the device (profiles/r04_ks_half15_ab.txt).  A launch whose
@@ -1963,76 +1830,39 @@ inline void key_switch_polys(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0,
         const size_t lds_ = k::lds_words(1u << 14) * sizeof(u64);
         const unsigned grid = (unsigned)((npolys * kc.L) << (kc.logn - 14));
         const bool rns = half15 == 2 && k_.digit_arg() == (1u << 8);
-#define FHE_KS_HALF15_LAUNCH_G(NW, RNS, G0, GALV)                                                                     \
-    allow_big_lds((k::ks_fused_kernel<14, NW, k::GM_MIXED, 0, RNS, G0, GALV>), lds_);                                 \
-    FHE_LAUNCH("key_switch_fused", (k::ks_fused_kernel<14, NW, k::GM_MIXED, 0, RNS, G0, GALV>), dim3(grid),           \
-               dim3(k::ks_threads_c(14)), lds_, s, p, p_stride, o0, o1, out_stride, a0, a1, a_stride, k_.c0.p, k_.c0s.p, \
-               k_.c1.p, k_.c1s.p, kc.dmods(), kc.dtw(), (uint32_t)k_.ndigits, (uint32_t)kc.L, k_.digit_arg(), xhat,   \
-               xhat_stride, grid, gal)
-#define FHE_KS_HALF15_LAUNCH(NW, RNS, G0)                                                                             \
-    do {                                                                                                              \
-        if (gal) {                                                                                                    \
-            FHE_KS_HALF15_LAUNCH_G(NW, RNS, G0, true);                                                                \
-        } else {                                                                                                      \
-            FHE_KS_HALF15_LAUNCH_G(NW, RNS, G0, false);                                                               \
-        }                                                                                                             \
-    } while (0)
-#define FHE_KS_HALF15_PICK(G0)                                                                                        \
-    if (narrow) {                                                                                                     \
-        if (rns) { FHE_KS_HALF15_LAUNCH(true, true, G0); } else { FHE_KS_HALF15_LAUNCH(true, false, G0); }            \
-    } else {                                                                                                          \
-        if (rns) { FHE_KS_HALF15_LAUNCH(false, true, G0); } else { FHE_KS_HALF15_LAUNCH(false, false, G0); }          \
-    }
-        if (kc.logn == 15) { FHE_KS_HALF15_PICK(1) } else { FHE_KS_HALF15_PICK(2) }
-#undef FHE_KS_HALF15_PICK
-#undef FHE_KS_HALF15_LAUNCH
-#undef FHE_KS_HALF15_LAUNCH_G
+        with_bool(kc.logn == 15, [&](auto one) {
+            with_bool(narrow, [&](auto nw) {
+                with_bool(rns, [&](auto r) {
+                    with_bool(gal != 0, [&](auto g) {
+                        constexpr int G0 = decltype(one)::value ? 1 : 2;
+                        launch_k<k::ks_fused_kernel<14, decltype(nw)::value, k::GM_MIXED, 0, decltype(r)::value, G0, decltype(g)::value>>(
+                            "key_switch_fused", dim3(grid), dim3(k::ks_threads_c(14)), lds_, s, p, p_stride, o0, o1, out_stride, a0,
+                            a1, a_stride, k_.c0.p, k_.c0s.p, k_.c1.p, k_.c1s.p, kc.dmods(), kc.dtw(), (uint32_t)k_.ndigits,
+                            (uint32_t)kc.L, k_.digit_arg(), xhat, xhat_stride, grid, gal);
+                    });
+                });
+            });
+        });
         return;
     }
     // 8192-point sub-blocks, logn - 13 folded stages (ks_fused_split_kernel; rounds 1-3: every launch)
-#define FHE_KS_SPLIT_LAUNCH_M(G0, LM, NW)                                                                          \
-    do {                                                                                                           \
-        const size_t lds_ = (k::lds_words(1u << LM) + ((size_t)1 << LM)) * sizeof(u64);                            \
-        if (k_.digit_arg() == (1u << 8)) {   /* RNS instance: residue-row digits of same-width moduli */          \
-            allow_big_lds((k::ks_fused_split_kernel<G0, LM, NW, true>), lds_);                                     \
-            FHE_LAUNCH("key_switch_fused_sub", (k::ks_fused_split_kernel<G0, LM, NW, true>),                           \
-                       dim3((unsigned)((npolys * kc.L) << G0)), dim3((1u << LM) / 8), lds_, s, p, p_stride, o0,    \
-                       o1, out_stride, a0, a1, a_stride, k_.c0.p, k_.c0s.p, k_.c1.p, k_.c1s.p, kc.dmods(),         \
-                       kc.dtw(), (uint32_t)k_.ndigits, (uint32_t)kc.L, k_.digit_arg(), xhat, xhat_stride, gal);    \
-        } else {                                                                                                   \
-            allow_big_lds((k::ks_fused_split_kernel<G0, LM, NW, false>), lds_);                                    \
-            FHE_LAUNCH("key_switch_fused_sub", (k::ks_fused_split_kernel<G0, LM, NW, false>),                          \
-                       dim3((unsigned)((npolys * kc.L) << G0)), dim3((1u << LM) / 8), lds_, s, p, p_stride, o0,    \
-                       o1, out_stride, a0, a1, a_stride, k_.c0.p, k_.c0s.p, k_.c1.p, k_.c1s.p, kc.dmods(),         \
-                       kc.dtw(), (uint32_t)k_.ndigits, (uint32_t)kc.L, k_.digit_arg(), xhat, xhat_stride, gal);    \
-        }                                                                                                          \
-    } while (0)
-#define FHE_KS_SPLIT_LAUNCH(G0, NW) FHE_KS_SPLIT_LAUNCH_M(G0, 13, NW)
+    auto launch_split = [&](auto g0, auto lm) {
+        constexpr int G0 = decltype(g0)::value, LM = decltype(lm)::value;
+        const size_t lds_ = (k::lds_words(1u << LM) + ((size_t)1 << LM)) * sizeof(u64);
+        with_bool(narrow, [&](auto nw) {
+            with_bool(k_.digit_arg() == (1u << 8), [&](auto r) {   // RNS instance: residue-row digits of same-width moduli
+                launch_k<k::ks_fused_split_kernel<G0, LM, decltype(nw)::value, decltype(r)::value>>(
+                    "key_switch_fused_sub", dim3((unsigned)((npolys * kc.L) << G0)), dim3((1u << LM) / 8), lds_, s, p, p_stride, o0,
+                    o1, out_stride, a0, a1, a_stride, k_.c0.p, k_.c0s.p, k_.c1.p, k_.c1s.p, kc.dmods(), kc.dtw(),
+                    (uint32_t)k_.ndigits, (uint32_t)kc.L, k_.digit_arg(), xhat, xhat_stride, gal);
+            });
+        });
+    };
 #if defined(FHE_LAB)
-    if (kc.logn == 13) {
-        if (narrow) {
-            FHE_KS_SPLIT_LAUNCH_M(1, 12, true);
-        } else {
-            FHE_KS_SPLIT_LAUNCH_M(1, 12, false);
-        }
-        return;
-    }
+    if (kc.logn == 13) return launch_split(int_c<1>{}, int_c<12>{});
 #endif
-#define FHE_KS_SPLIT_CASE(G0)                                                                                      \
-    case 13 + G0:                                                                                                  \
-        if (narrow) {                                                                                              \
-            FHE_KS_SPLIT_LAUNCH(G0, true);                                                                         \
-        } else {                                                                                                   \
-            FHE_KS_SPLIT_LAUNCH(G0, false);                                                                        \
-        }                                                                                                          \
-        break;
-    switch (kc.logn) {
-        FHE_KS_SPLIT_CASE(1) FHE_KS_SPLIT_CASE(2) FHE_KS_SPLIT_CASE(3)
-        default: throw StatusError(E_ARG, "unsupported key-switch row size");
-    }
-#undef FHE_KS_SPLIT_CASE
-#undef FHE_KS_SPLIT_LAUNCH
-#undef FHE_KS_SPLIT_LAUNCH_M
+    with_logn<14, 16>(kc.logn, "unsupported key-switch row size",
+                      [&](auto ln) { launch_split(int_c<decltype(ln)::value - 13>{}, int_c<13>{}); });
 }
 
 // Poly::<PowerBasis>::switch_down_to (M/rq/mod.rs:498-507): `iters` applications of switch_down.
@@ -2819,53 +2649,9 @@ inline k::u64x2 scale_pair(u64 w, u64 p, bool f64) {
     return r;
 }
 
-// The whole-row (N <= 16384) instances of the encoding kernels: integer (NARROW: every modulus below 2^60) or F64 class hr.
-#define FHE_ENC_LAUNCH(KERNEL, LM, NRW, HR, name, grid, s, ...)                                                        \
-    do {                                                                                                           \
-        const size_t _lds = k::lds_words(1u << (LM)) * sizeof(u64);                                                \
-        allow_big_lds((k::KERNEL<LM, NRW, HR>), _lds);                                                             \
-        FHE_LAUNCH(name, (k::KERNEL<LM, NRW, HR>), dim3(grid), dim3(k::ntt_threads_c(LM)), _lds, s, __VA_ARGS__);  \
-    } while (0)
-#define FHE_ENC_CASE_INT(KERNEL, LM, narrow, name, grid, s, ...)                                                       \
-    case LM:                                                                                                       \
-        if (narrow) FHE_ENC_LAUNCH(KERNEL, LM, true, 0, name, grid, s, __VA_ARGS__);                               \
-        else FHE_ENC_LAUNCH(KERNEL, LM, false, 0, name, grid, s, __VA_ARGS__);                                     \
-        break;
-#define FHE_ENC_CASE_F64(KERNEL, LM, narrow, hr, name, grid, s, ...)                                                   \
-    case LM:                                                                                                       \
-        if (hr == 3) FHE_ENC_LAUNCH(KERNEL, LM, false, 3, name, grid, s, __VA_ARGS__);                             \
-        else if (hr == 4) FHE_ENC_LAUNCH(KERNEL, LM, false, 4, name, grid, s, __VA_ARGS__);                        \
-        else if (hr == 5) FHE_ENC_LAUNCH(KERNEL, LM, false, 5, name, grid, s, __VA_ARGS__);                        \
-        else if (narrow) FHE_ENC_LAUNCH(KERNEL, LM, true, 0, name, grid, s, __VA_ARGS__);                          \
-        else FHE_ENC_LAUNCH(KERNEL, LM, false, 0, name, grid, s, __VA_ARGS__);                                     \
-        break;
-#define FHE_ENC_SWITCH(KERNEL, logn, narrow, hr, name, grid, s, ...)                                                   \
-    switch (logn) {                                                                                                \
-        FHE_ENC_CASE_INT(KERNEL, 3, narrow, name, grid, s, __VA_ARGS__)                                            \
-        FHE_ENC_CASE_INT(KERNEL, 4, narrow, name, grid, s, __VA_ARGS__)                                            \
-        FHE_ENC_CASE_INT(KERNEL, 5, narrow, name, grid, s, __VA_ARGS__)                                            \
-        FHE_ENC_CASE_INT(KERNEL, 6, narrow, name, grid, s, __VA_ARGS__)                                            \
-        FHE_ENC_CASE_INT(KERNEL, 7, narrow, name, grid, s, __VA_ARGS__)                                            \
-        FHE_ENC_CASE_INT(KERNEL, 8, narrow, name, grid, s, __VA_ARGS__)                                            \
-        FHE_ENC_CASE_INT(KERNEL, 9, narrow, name, grid, s, __VA_ARGS__)                                            \
-        FHE_ENC_CASE_INT(KERNEL, 10, narrow, name, grid, s, __VA_ARGS__)                                           \
-        FHE_ENC_CASE_INT(KERNEL, 11, narrow, name, grid, s, __VA_ARGS__)                                           \
-        FHE_ENC_CASE_F64(KERNEL, 12, narrow, hr, name, grid, s, __VA_ARGS__)                                       \
-        FHE_ENC_CASE_F64(KERNEL, 13, narrow, hr, name, grid, s, __VA_ARGS__)                                       \
-        FHE_ENC_CASE_F64(KERNEL, 14, narrow, hr, name, grid, s, __VA_ARGS__)                                       \
-        default: throw StatusError(E_ARG, "unsupported encoding tile size");                                       \
-    }
-
-// the F64 class of the encoding kernels' rows (whole rows of 4096 ... 16384 points only, as launch_ntt_f64)
-inline int f64_rows(const Ctx &c, size_t first, size_t rows, bool f64_on) {
-    return f64_on && c.logn >= 12 && c.logn <= 14 ? c.f64_class(first, rows) : 0;
-}
-
-inline bool all_below_2p60(const Ctx &c) {
-    for (size_t i = 0; i < c.L; i++)
-        if (c.moduli[i] >> 60) return false;
-    return true;
-}
+// The encoding, sampling, encryption and key-generation kernels work on whole rows (N <= 16384) through with_tile:
+// integer (NARROW: every modulus below 2^60) or F64 class hr (Ctx::f64_rows).
+constexpr const char *ENC_TILE = "unsupported encoding tile size";
 
 // PlaintextVec::try_encode (F/bfv/plaintext_vec.rs:70-102) -> Plaintext::poly_ntt, or with `scaled` Plaintext::to_poly
 // (F/bfv/plaintext.rs:172-196): values [batch][nvalues] -> out [batch][L_level][N] Ntt.
@@ -2889,14 +2675,16 @@ inline void encode(const Encoder &e, bool simd, bool scaled, size_t level, const
         const Ctx &tc = *e.tctx;
         if (e.logn <= 14) {
             // the inverse transform's N^-1 times q_mod_t for the scaled form (the same value mod t as multiplying after)
-            const int hr = f64_rows(tc, 0, 1, f64_on);
+            const int hr = tc.f64_rows(0, 1, f64_on);
             const NttTables &tt = tc.tab(0);
             const u64 c = scaled ? mulmod(tt.size_inv, qmt, e.t) : tt.size_inv;
             const u64 zc = mulmod(tt.zetas_inv[e.n - 2], c, e.t);
             const k::u64x2 ns = scale_pair(c, e.t, hr > 0), zs = scale_pair(zc, e.t, hr > 0);
             const k::u64x2 *itw = hr > 0 ? tc.ditw_f() : tc.ditw();
-            FHE_ENC_SWITCH(encode_simd_t_kernel, e.logn, (e.t >> 60) == 0, hr, "encode_simd_t", batch, s, values,
-                           (u64)nvalues, e.d_inv_map.p, trows->u(), tc.dmods(), itw, ns, zs);
+            with_tile(e.logn, ENC_TILE, (e.t >> 60) == 0, hr, [&](auto lm, auto nrw, auto h) {
+                launch_tile<k::encode_simd_t_kernel<decltype(lm)::value, decltype(nrw)::value, decltype(h)::value>>(
+                    "encode_simd_t", lm, batch, s, values, (u64)nvalues, e.d_inv_map.p, trows->u(), tc.dmods(), itw, ns, zs);
+            });
             ls.mul_t = 0;
         } else {   // rows larger than one LDS tile: the gather as a pass of its own, then launch_ntt
             const u64 total = (u64)batch * e.n;
@@ -2908,10 +2696,12 @@ inline void encode(const Encoder &e, bool simd, bool scaled, size_t level, const
         ls.stride = ls.nvalues = e.n;
     }
     if (qc->logn <= 14) {
-        const int hr = f64_rows(*qc, 0, qc->L, f64_on);
+        const int hr = qc->f64_rows(0, qc->L, f64_on);
         const k::u64x2 *tw = hr > 0 ? qc->dtw_f() : qc->dtw();
-        FHE_ENC_SWITCH(encode_lift_kernel, qc->logn, all_below_2p60(*qc), hr, "encode_lift", batch * qc->L, s, ls, out,
-                       (uint32_t)qc->L, qc->dmods(), tw);
+        with_tile(qc->logn, ENC_TILE, qc->below_2p60(0, qc->L), hr, [&](auto lm, auto nrw, auto h) {
+            launch_tile<k::encode_lift_kernel<decltype(lm)::value, decltype(nrw)::value, decltype(h)::value>>(
+                "encode_lift", lm, batch * qc->L, s, ls, out, (uint32_t)qc->L, qc->dmods(), tw);
+        });
     } else {
         const u64 total = (u64)batch * qc->L * e.n;
         FHE_LAUNCH("encode_lift", k::encode_lift_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
@@ -2933,9 +2723,11 @@ inline void decode(const Encoder &e, bool simd, const u64 *coeffs, u64 *out, siz
     }
     const Ctx &tc = *e.tctx;
     if (e.logn <= 14) {
-        const int hr = f64_rows(tc, 0, 1, !f64_disabled());
-        FHE_ENC_SWITCH(decode_simd_kernel, e.logn, (e.t >> 60) == 0, hr, "decode_simd", batch, s, coeffs, e.d_map.p, out,
-                       tc.dmods(), hr > 0 ? tc.dtw_f() : tc.dtw());
+        const int hr = tc.f64_rows(0, 1);
+        with_tile(e.logn, ENC_TILE, (e.t >> 60) == 0, hr, [&](auto lm, auto nrw, auto h) {
+            launch_tile<k::decode_simd_kernel<decltype(lm)::value, decltype(nrw)::value, decltype(h)::value>>(
+                "decode_simd", lm, batch, s, coeffs, e.d_map.p, out, tc.dmods(), hr > 0 ? tc.dtw_f() : tc.dtw());
+        });
         return;
     }
     // rows larger than one LDS tile: reduce, launch_ntt, then the index map as a gather pass
@@ -2971,6 +2763,15 @@ inline void cbd_sample(const uint8_t *seeds, size_t variance, size_t logn, size_
 // (int8 scratch rounded up to whole 16-byte words)
 inline size_t small_bytes(size_t count) { return (count + 15) & ~(size_t)15; }
 
+// Rows larger than one LDS tile (and PowerBasis output): the samples of `npolys` polynomials lifted to residue rows as a
+// pass of its own, then (to_ntt) launch_ntt; the callers' combine stages follow as element-wise passes.
+inline void small_lift(const Ctx &c, const int8_t *smp, u64 *x, size_t npolys, bool to_ntt, hipStream_t s) {
+    const u64 total = (u64)npolys * c.L * c.n;
+    FHE_LAUNCH("small_lift", k::small_lift_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s, smp, x,
+               (uint32_t)c.L, c.dmods(), (uint32_t)c.logn, total);
+    if (to_ntt) launch_ntt(c, false, x, x, full_map(c, c.L), npolys, s);
+}
+
 // Poly::small(ctx, variance, ChaCha8Rng::from_seed(seeds[b])): out [batch][L][N], PowerBasis or (to_ntt) Ntt.
 inline void sample_small(const Ctx &c, size_t variance, const uint8_t *seeds, bool to_ntt, u64 *out, size_t batch,
                          hipStream_t s) {
@@ -2983,23 +2784,23 @@ inline void sample_small(const Ctx &c, size_t variance, const uint8_t *seeds, bo
     int8_t *sp = (int8_t *)smp.p;
     cbd_sample(seeds, variance, c.logn, 1, sp, batch, s);
     if (to_ntt && c.logn <= 14) {
-        const int hr = f64_rows(c, 0, c.L, !f64_disabled());
-        FHE_ENC_SWITCH(small_ntt_kernel, c.logn, all_below_2p60(c), hr, "small_ntt", batch * c.L, s, (const int8_t *)sp,
-                       out, (uint32_t)c.L, c.dmods(), hr > 0 ? c.dtw_f() : c.dtw());
+        const int hr = c.f64_rows(0, c.L);
+        with_tile(c.logn, ENC_TILE, c.below_2p60(0, c.L), hr, [&](auto lm, auto nrw, auto h) {
+            launch_tile<k::small_ntt_kernel<decltype(lm)::value, decltype(nrw)::value, decltype(h)::value>>(
+                "small_ntt", lm, batch * c.L, s, (const int8_t *)sp, out, (uint32_t)c.L, c.dmods(), hr > 0 ? c.dtw_f() :
+                c.dtw());
+        });
         return;
     }
-    const u64 total = (u64)batch * c.L * c.n;
-    FHE_LAUNCH("small_lift", k::small_lift_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
-               (const int8_t *)sp, out, (uint32_t)c.L, c.dmods(), (uint32_t)c.logn, total);
-    if (to_ntt) launch_ntt(c, false, out, out, full_map(c, c.L), batch, s);
+    small_lift(c, sp, out, batch, to_ntt, s);
 }
 
 // Items per launch group of an encryption: the u64 scratch rows of one group (`rows_per_item` polynomials per item:
 // the seeded `a`, and for rows larger than one LDS tile the transformed samples) stay within `budget` bytes, and the
-// batch is split into groups of equal size (a small tail group would underfill the device).
-inline size_t encrypt_group(const Ctx &c, size_t rows_per_item, size_t batch, size_t budget) {
+// batch is split into groups of equal size (a small tail group would underfill the device).  `cap`: most items a launch takes.
+inline size_t encrypt_group(const Ctx &c, size_t rows_per_item, size_t batch, size_t budget, size_t cap = 65535) {
     const size_t per = std::max<size_t>(1, rows_per_item) * c.L * c.n * sizeof(u64);
-    const size_t most = std::max<size_t>(1, std::min<size_t>(65535, budget / per));
+    const size_t most = std::max<size_t>(1, std::min<size_t>(cap, budget / per));
     const size_t groups = (batch + most - 1) / most;
     return (batch + groups - 1) / groups;
 }
@@ -3014,7 +2815,7 @@ inline void encrypt_sk(const Ctx &c, size_t variance, const u64 *s_ntt, const ui
     if (!batch) return;
     require(batch * c.L <= 0x7fffffffu, E_ARG, "encrypt: batch exceeds the grid limit");
     const bool f64_on = !f64_disabled();   // (read once per call: every transform of the call takes the same kind)
-    const int hr = c.logn <= 14 ? f64_rows(c, 0, c.L, f64_on) : 0;
+    const int hr = c.f64_rows(0, c.L, f64_on);
     const u64 PL = (u64)c.L * c.n;
     // `a` is expanded into scratch: the unchanged seed_expand_kernel writes whole polynomials back to back
     // ([npolys][L][N]), so it cannot place them at out[b][1] (item stride 2 L N); the epilogue copies a into c1 while
@@ -3031,17 +2832,17 @@ inline void encrypt_sk(const Ctx &c, size_t variance, const u64 *s_ntt, const ui
         cbd_sample(e_seeds + b0 * 32, variance, c.logn, 1, sp, nb, s);
         polys_from_seeds(c, a_seeds + b0 * 32, a.u(), nb, s);
         if (c.logn <= 14) {
-            FHE_ENC_SWITCH(encrypt_sk_kernel, c.logn, all_below_2p60(c), hr, "encrypt_sk", nb * c.L, s, (const int8_t *)sp,
-                           (const u64 *)a.u(), s_ntt, ptb, pt_shared ? (u64)0 : PL, outb, (uint32_t)c.L, c.dmods(),
-                           hr > 0 ? c.dtw_f() : c.dtw());
+            with_tile(c.logn, ENC_TILE, c.below_2p60(0, c.L), hr, [&](auto lm, auto nrw, auto h) {
+                launch_tile<k::encrypt_sk_kernel<decltype(lm)::value, decltype(nrw)::value, decltype(h)::value>>(
+                    "encrypt_sk", lm, nb * c.L, s, (const int8_t *)sp, (const u64 *)a.u(), s_ntt, ptb, pt_shared ? (u64)0 : PL,
+                    outb, (uint32_t)c.L, c.dmods(), hr > 0 ? c.dtw_f() : c.dtw());
+            });
             continue;
         }
         // rows larger than one LDS tile: lift, launch_ntt, then the epilogue as a pass of its own
         WsGuard x(nb * PL * sizeof(u64), s, true);
         const u64 total = (u64)nb * PL;
-        FHE_LAUNCH("small_lift", k::small_lift_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
-                   (const int8_t *)sp, x.u(), (uint32_t)c.L, c.dmods(), (uint32_t)c.logn, total);
-        launch_ntt(c, false, x.u(), x.u(), full_map(c, c.L), nb, s);
+        small_lift(c, sp, x.u(), nb, true, s);
         FHE_LAUNCH("encrypt_combine", k::encrypt_combine_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS),
                    0, s, (const u64 *)x.u(), (const u64 *)a.u(), s_ntt, ptb, pt_shared ? (u64)0 : PL, outb, (uint32_t)c.L,
                    c.dmods(), (uint32_t)c.logn, 0u, total);
@@ -3058,7 +2859,7 @@ inline void encrypt_pk(const Ctx &c, size_t variance, const u64 *pk, const uint8
     if (!batch) return;
     require(batch * c.L <= 0x7fffffffu, E_ARG, "encrypt: batch exceeds the grid limit");
     const bool f64_on = !f64_disabled();
-    const int hr = c.logn <= 14 ? f64_rows(c, 0, c.L, f64_on) : 0;
+    const int hr = c.f64_rows(0, c.L, f64_on);
     const u64 PL = (u64)c.L * c.n;
     const size_t group = c.logn <= 14 ? 65535 : encrypt_group(c, 3, batch, (size_t)256 << 20);
     for (size_t b0 = 0; b0 < batch; b0 += group) {
@@ -3069,17 +2870,17 @@ inline void encrypt_pk(const Ctx &c, size_t variance, const u64 *pk, const uint8
         int8_t *sp = (int8_t *)smp.p;
         cbd_sample(seeds + b0 * 32, variance, c.logn, 3, sp, nb, s);
         if (c.logn <= 14) {
-            for (uint32_t stage = 0; stage < 3; stage++)
-                FHE_ENC_SWITCH(encrypt_pk_kernel, c.logn, all_below_2p60(c), hr, "encrypt_pk", nb * c.L, s,
-                               (const int8_t *)sp, pk, ptb, pt_shared ? (u64)0 : PL, outb, (uint32_t)c.L, c.dmods(),
-                               hr > 0 ? c.dtw_f() : c.dtw(), stage);
+            with_tile(c.logn, ENC_TILE, c.below_2p60(0, c.L), hr, [&](auto lm, auto nrw, auto h) {
+                for (uint32_t stage = 0; stage < 3; stage++)
+                    launch_tile<k::encrypt_pk_kernel<decltype(lm)::value, decltype(nrw)::value, decltype(h)::value>>(
+                        "encrypt_pk", lm, nb * c.L, s, (const int8_t *)sp, pk, ptb, pt_shared ? (u64)0 : PL, outb,
+                        (uint32_t)c.L, c.dmods(), hr > 0 ? c.dtw_f() : c.dtw(), stage);
+            });
             continue;
         }
         WsGuard x(nb * 3 * PL * sizeof(u64), s, true);
-        const u64 lifted = (u64)nb * 3 * PL, total = (u64)nb * PL;
-        FHE_LAUNCH("small_lift", k::small_lift_ew_kernel, dim3(blocks_for(lifted, EW_THREADS)), dim3(EW_THREADS), 0, s,
-                   (const int8_t *)sp, x.u(), (uint32_t)c.L, c.dmods(), (uint32_t)c.logn, lifted);
-        launch_ntt(c, false, x.u(), x.u(), full_map(c, c.L), nb * 3, s);
+        const u64 total = (u64)nb * PL;
+        small_lift(c, sp, x.u(), nb * 3, true, s);
         FHE_LAUNCH("encrypt_combine", k::encrypt_combine_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS),
                    0, s, (const u64 *)x.u(), (const u64 *)nullptr, pk, ptb, pt_shared ? (u64)0 : PL, outb, (uint32_t)c.L,
                    c.dmods(), (uint32_t)c.logn, 1u, total);
@@ -3135,13 +2936,12 @@ inline std::vector<std::unique_ptr<Ksk>> ksk_generate(const Ctx &ct, const Ctx &
                (uint32_t)nd, (uint32_t)Lk, (uint32_t)lb, g, rq);
     const bool whole = kc.logn <= 14;
     const bool f64_on = !f64_disabled();   // (read once per call: every transform of the call takes the same kind)
-    const int hr = whole ? f64_rows(kc, 0, Lk, f64_on) : 0;
+    const int hr = kc.f64_rows(0, Lk, f64_on);
     const u64 wpd = cbd_words_per_draw(variance, N);
     // groups: at most KG_KEYS keys (the output table travels in the kernel arguments) and 1 GiB of c1 scratch (256 MiB
     // of c1 and transformed errors for larger rows), split into groups of equal size
-    const size_t per = PK * sizeof(u64) * (whole ? 1 : 2), budget = whole ? (size_t)1 << 30 : (size_t)256 << 20;
-    const size_t most = std::max<size_t>(1, std::min<size_t>(k::KG_KEYS, budget / per));
-    const size_t groups = (nkeys + most - 1) / most, group = (nkeys + groups - 1) / groups;
+    const size_t group = whole ? encrypt_group(kc, nd, nkeys, (size_t)1 << 30, k::KG_KEYS)
+                               : encrypt_group(kc, 2 * nd, nkeys, (size_t)256 << 20, k::KG_KEYS);
     require(group * nd * Lk <= 0x7fffffffu, E_ARG, "ksk_generate: a launch group exceeds the grid limit");
     for (size_t b0 = 0; b0 < nkeys; b0 += group) {
         const size_t nb = std::min(group, nkeys - b0);
@@ -3163,17 +2963,17 @@ inline std::vector<std::unique_ptr<Ksk>> ksk_generate(const Ctx &ct, const Ctx &
         polys_from_seeds(kc, (const uint8_t *)ds.p, c1.u(), nb * nd, s);
         const u64 *fb = from_ntt + b0 * Lk * N;
         if (whole) {
-            FHE_ENC_SWITCH(ksk_gen_kernel, kc.logn, all_below_2p60(kc), hr, "ksk_gen", nb * nd * Lk, s, (const int8_t *)sp,
-                           (const u64 *)c1.u(), s_ntt, fb, (const u64 *)g, (const k::u64x2 *)rq, tab, (uint32_t)nd,
-                           (uint32_t)Lk, (uint32_t)wf, kc.dmods(), hr > 0 ? kc.dtw_f() : kc.dtw());
+            with_tile(kc.logn, ENC_TILE, kc.below_2p60(0, Lk), hr, [&](auto lm, auto nrw, auto h) {
+                launch_tile<k::ksk_gen_kernel<decltype(lm)::value, decltype(nrw)::value, decltype(h)::value>>(
+                    "ksk_gen", lm, nb * nd * Lk, s, (const int8_t *)sp, (const u64 *)c1.u(), s_ntt, fb, (const u64 *)g, (const
+                    k::u64x2 *)rq, tab, (uint32_t)nd, (uint32_t)Lk, (uint32_t)wf, kc.dmods(), hr > 0 ? kc.dtw_f() : kc.dtw());
+            });
             continue;
         }
         // rows larger than one LDS tile: lift, launch_ntt, then the epilogue as a pass of its own
         WsGuard x(nb * PK * sizeof(u64), s, true);
         const u64 total = (u64)nb * PK;
-        FHE_LAUNCH("small_lift", k::small_lift_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
-                   (const int8_t *)sp, x.u(), (uint32_t)Lk, kc.dmods(), (uint32_t)kc.logn, total);
-        launch_ntt(kc, false, x.u(), x.u(), full_map(kc, Lk), nb * nd, s);
+        small_lift(kc, sp, x.u(), nb * nd, true, s);
         FHE_LAUNCH("ksk_combine", k::ksk_combine_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
                    (const u64 *)x.u(), (const u64 *)c1.u(), s_ntt, fb, (const u64 *)g, (const k::u64x2 *)rq, tab,
                    (uint32_t)nd, (uint32_t)Lk, (uint32_t)wf, kc.dmods(), (uint32_t)kc.logn, total);
@@ -3231,10 +3031,6 @@ inline void galois_from(const Ctx &ct, const Ctx &kc, const u64 *s_ntt, const si
     }
     if (t) switch_up_ntt(ct, kc, t->u(), out, nkeys, s);
 }
-#undef FHE_ENC_SWITCH
-#undef FHE_ENC_CASE_F64
-#undef FHE_ENC_CASE_INT
-#undef FHE_ENC_LAUNCH
 
 // `&Ciphertext + &Plaintext` / `-` (F/bfv/ops/mod.rs:71-108, 166-203): c0 +- to_poly(pt), the other parts unchanged.
 // ct, out [batch][nparts][L][N]; pt [batch][L][N] Delta-scaled (pt_shared: [L][N]); out == ct allowed.
