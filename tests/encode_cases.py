@@ -37,9 +37,10 @@ def values(rng, t, batch, nvalues, wide=False):
     return g.integers(0, hi, size=(batch, nvalues), dtype=np.uint64, endpoint=True)
 
 
-def case_parity(fhe, dev, opar, par, batches, nvalues_list, levels=None, check_items=None, seed=1):
+def case_parity(fhe, dev, opar, par, batches, nvalues_list, levels=None, check_items=None, seed=1, wide=False):
     """encode (Poly / SIMD, unscaled / scaled) and decode against the restatement, every combination of the given
-    batches, value counts and levels; check_items(batch) -> item indices compared (default: all)."""
+    batches, value counts and levels; check_items(batch) -> item indices compared (default: all).  wide: the inputs of
+    both directions are any u64 words (the engine and the restatement reduce them mod t first)."""
     x = Xfer(dev)
     rng = random.Random(seed)
     n, t = opar.degree(), opar.plaintext
@@ -49,7 +50,7 @@ def case_parity(fhe, dev, opar, par, batches, nvalues_list, levels=None, check_i
     for level in levels:
         for batch in batches:
             for nv in nvalues_list:
-                v = values(rng, t, batch, nv)
+                v = values(rng, t, batch, nv, wide)
                 items = range(batch) if check_items is None else check_items(batch)
                 for encoding in ("poly", "simd"):
                     for scaled in (False, True):
@@ -59,7 +60,7 @@ def case_parity(fhe, dev, opar, par, batches, nvalues_list, levels=None, check_i
                             want = R.encode(opar, v[b], encoding, level, scaled, cctx=cctx[level])
                             assert np.array_equal(got[b], want), (encoding, scaled, level, batch, nv, b)
         for batch in batches:
-            c = values(rng, t, batch, n)
+            c = values(rng, t, batch, n, wide)
             for encoding in ("poly", "simd"):
                 got = x.back(enc.decode(x.to(c), encoding))
                 assert got.shape == (batch, n)

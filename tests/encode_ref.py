@@ -61,21 +61,30 @@ def coefficients(values, t, n, encoding, psi=None):
     return t_context(t, n, psi).ntt_backward_row(0, c)
 
 
+_delta = {}
+
+
+def _delta_rows(opar, level):
+    """delta of one level as [L][N] uint64: a constant polynomial, so every Ntt slot of row i holds delta_i."""
+    key = (id(opar), level)
+    if key not in _delta:
+        _delta[key] = (opar, np.array(opar.delta[level].coefficients, dtype=np.uint64))
+    return _delta[key][1]
+
+
 def lift(opar, coeffs, level, scaled, cctx=None):
     """Poly::try_convert_from + into_ntt (poly_ntt), or Plaintext::to_poly with scaled: coefficients times q_mod_t mod
     t, lift, NTT, times delta (parameters.rs:607-633).  -> [L_level][N] uint64."""
     t = opar.plaintext
     ctx = opar.ctx[level]
-    c = np.asarray(coeffs, dtype=np.uint64).astype(object)
+    c = np.asarray(coeffs, dtype=np.uint64)
     if scaled:
-        c = (c * opar.q_mod_t[level]) % t
-    rows = np.array([[int(x) % q for x in c] for q in ctx.moduli], dtype=np.uint64)
+        c = ((c.astype(object) * opar.q_mod_t[level]) % t).astype(np.uint64)
+    rows = np.stack([c % np.uint64(q) for q in ctx.moduli])
     cctx = cctx or coracle.CCtx(ctx)
     out = cctx.poly_ntt_forward(rows)
     if scaled:
-        for i, q in enumerate(ctx.moduli):
-            d = opar.delta[level].coefficients[i][0]   # delta is a constant polynomial: every Ntt slot holds delta_i
-            out[i] = np.array([(int(x) * d) % q for x in out[i]], dtype=np.uint64)
+        out = cctx.poly_mul(out, _delta_rows(opar, level))
     return out
 
 

@@ -68,9 +68,11 @@ def keys(fhe, opar, par, seed=5):
     return sk, R.secret_key(opar, sk_seed), s_host
 
 
-def case_encrypt_parity(fhe, dev, opar, par, levels=None, batch=3, check_items=None, seed=7):
+def case_encrypt_parity(fhe, dev, opar, par, levels=None, batch=3, check_items=None, seed=7,
+                        modes=("each", "shared", "none")):
     """SecretKey.random, SecretKey.encrypt and PublicKey / PublicKey.encrypt against the restatement, bit for bit:
-    pt given per item, shared, and None (the zero plaintext); c1 of the secret-key form equals fhe_poly_from_seed."""
+    pt given per item, shared, and None (the zero plaintext); c1 of the secret-key form equals fhe_poly_from_seed for
+    the whole batch.  check_items(batch) -> item indices compared (default: all)."""
     x = Xfer(dev)
     rng = random.Random(seed)
     n, t, v = opar.degree(), opar.plaintext, opar.variance
@@ -94,7 +96,7 @@ def case_encrypt_parity(fhe, dev, opar, par, levels=None, batch=3, check_items=N
             assert pk_l.tolist() == [p.coefficients for p in oct_.c]
         vals = E.values(rng, t, batch, n)
         pts = x.back(enc.encode(x.to(vals), "simd", level, True))
-        for mode in ("each", "shared", "none"):
+        for mode in modes:
             a_sd, e_sd, p_sd = seeds(rng, batch), seeds(rng, batch), seeds(rng, batch)
             if mode == "each":
                 pt_in, pt_of = x.to(pts), (lambda b: pts[b])

@@ -108,11 +108,15 @@ def test_variances(fhe, v):
 
 
 def test_batch_larger_than_one_launch_group(fhe):
-    """More keys than one launch group (KG_KEYS = 32) in one call: the groups split evenly and every key is right."""
+    """More keys than one launch group (KG_KEYS = 32) in one call: the groups split evenly (40 keys: 20 + 20) and the
+    keys on both sides of that boundary are right, as are those around key 32."""
+    import devop_cases as D
     opar, par = G.params(fhe, 8, 1153, moduli_sizes=[62, 60])
     n = 8
     exps = (list(range(1, 2 * n, 2)) * 5)[:40]   # 40 keys (exponents repeat: each key has its own seed)
-    G.case_galois(fhe, False, opar, par, exps, 0, 0, check={0, 31, 32, 39})
+    g = D.launch_group(2, n, 2, len(exps), 1 << 30, D.KG_KEYS)
+    assert 1 < g < len(exps)
+    G.case_galois(fhe, False, opar, par, exps, 0, 0, check={0, 31, 32, 39} | set(D.boundary_items(len(exps), g)))
 
 
 def test_f64_and_4096_points(fhe):
