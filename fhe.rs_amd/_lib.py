@@ -156,6 +156,10 @@ SIGNATURES = {
     "fhe_bfv_galois_keys_generate_dev": (i32, [vp, vp, sz, vp, vp, vp, sz, vp, vp, vp]),
     "fhe_ksk_export_dev": (i32, [vp, vp, vp, vp, vp, vp]),
     "fhe_ksk_ndigits": (sz, [vp]),
+    "fhe_ctx_lift_limbs": (sz, [vp]),
+    "fhe_poly_lift_dev": (i32, [vp, vp, vp, sz, vp]),
+    "fhe_poly_centered_bits_dev": (i32, [vp, vp, vp, sz, vp]),
+    "fhe_bfv_measure_noise_dev": (i32, [vp, vp, vp, vp, sz, vp, vp, sz, vp]),
     "fhe_generate_prime": (u64, [sz, u64, u64]),
     "fhe_supports_opt": (i32, [u64]),
     "fhe_is_prime": (i32, [u64]),

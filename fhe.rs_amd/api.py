@@ -582,6 +582,47 @@ class Context:
         finally:
             _wipe(staged)
 
+    # -- RnsContext::lift and the centered bit length (rns/mod.rs:138-143, secret_key.rs:88-95) -----
+    @property
+    def lift_limbs(self):
+        """W = ceil(bitlen(q) / 64): the u64 limbs per coefficient `lift` writes."""
+        return _lib.lib().fhe_ctx_lift_limbs(self._h)
+
+    def lift(self, polys):
+        """RnsContext::lift per coefficient (fhe_poly_lift_dev), as Vec<BigUint>::from(&Poly) applies it: polys
+        [..., L, N] canonical residues in any representation -> the integers in [0, q).  numpy in -> an object array
+        [..., N] of Python ints; a device array in -> a device array [..., N, W] of little-endian u64 limbs."""
+        b, w = self._batch(polys), self.lift_limbs
+        lead = tuple(int(d) for d in polys.shape[:-2])
+        if _is_dev(polys):
+            out = _empty_dev(polys, lead + (self.degree, w))
+            check(_lib.lib().fhe_poly_lift_dev(self._h, _dptr(polys), _dptr(out), b, _stream()))
+            return out
+        x = DeviceArray.from_numpy(_np(polys), max(self.device, 0))
+        out = DeviceArray(lead + (self.degree, w), x.device)
+        check(_lib.lib().fhe_poly_lift_dev(self._h, _dptr(x), _dptr(out), b, _stream()))
+        limbs = out.download().astype(object)
+        ints = limbs[..., 0]
+        for k in range(1, w):
+            ints = ints + (limbs[..., k] << (64 * k))
+        return ints
+
+    def centered_bits(self, polys):
+        """max over the coefficients of min(bits(x), bits(q - x)), x the lifted coefficient (fhe_poly_centered_bits_dev;
+        the loop of SecretKey::measure_noise): polys [..., L, N] -> [...] uint64, one value per polynomial.  numpy in ->
+        numpy out (an int without batch dimensions); a device array in -> a device array."""
+        b = self._batch(polys)
+        lead = tuple(int(d) for d in polys.shape[:-2])
+        if _is_dev(polys):
+            out = _empty_dev(polys, lead or (1,))
+            check(_lib.lib().fhe_poly_centered_bits_dev(self._h, _dptr(polys), _dptr(out), b, _stream()))
+            return out
+        x = DeviceArray.from_numpy(_np(polys), max(self.device, 0))
+        out = DeviceArray(lead or (1,), x.device)
+        check(_lib.lib().fhe_poly_centered_bits_dev(self._h, _dptr(x), _dptr(out), b, _stream()))
+        r = out.download()
+        return r if lead else int(r[0])
+
     def synth_uniform(self, seed, ct0, part0, nparts, batch):
         """Device-side synthetic residues [batch, nparts, L, N] (bench / parity inputs)."""
         shape = (batch, nparts, self.nmoduli, self.degree)
@@ -1172,6 +1213,7 @@ class SecretKey:
 
     def __init__(self, params, s_ntt):
         self.params, self.s_ntt = params, s_ntt
+        self._encoder = None   # (measure_noise's q_mod_t and delta per level: made on first use)
 
     @classmethod
     def random(cls, params, seed=None):
@@ -1210,6 +1252,46 @@ class SecretKey:
             return _download(d)
         finally:
             _wipe([d])   # (the plaintext coefficients)
+
+    def measure_noise(self, ct, level=0, plaintext=None):
+        """SecretKey::measure_noise (secret_key.rs:55-98, fhe_bfv_measure_noise_dev): ct [..., nparts, L - level, N] ->
+        [...] uint64, the bits of noise of each ciphertext.  plaintext=None measures against the ciphertext's own
+        decryption (the reference); plaintext [..., N] coefficients in [0, t) (what `decrypt` returns, or
+        `Encoder.decode`'s inverse) measures against the plaintext the caller expects, which keeps growing after the
+        ciphertext has stopped decrypting to it.  The key, the phase and the error stay on the device: numpy inputs
+        are uploaded (and the staged plaintext is cleared); numpy in -> numpy out (an int without batch dimensions), a
+        device array in -> a device array."""
+        par = self.params
+        if not 0 <= level <= par.max_level:
+            raise FheError(-12, "InvalidLevel")
+        sc = par.plain_scaler(level)
+        nparts = int(ct.shape[-3])
+        b = sc.from_ctx._batch(ct) // nparts
+        lead = tuple(int(d) for d in ct.shape[:-3])
+        if self._encoder is None:
+            self._encoder = par.encoder()
+        enc = self._encoder
+        if plaintext is not None and (tuple(int(d) for d in plaintext.shape) != lead + (par.degree,)):
+            raise FheError(-1, "plaintext: expected one [N] row of coefficients per ciphertext")
+        host = not _is_dev(ct)
+        staged = []
+        try:
+            x = DeviceArray.from_numpy(_np(ct), max(par.device, 0)) if host else ct
+            m = None
+            if plaintext is not None:
+                m = plaintext
+                if not _is_dev(plaintext):
+                    m = DeviceArray.from_numpy(_np(plaintext), max(par.device, 0))
+                    staged.append(m)
+            out = DeviceArray(lead or (1,), x.device) if host else _empty_dev(ct, lead or (1,))
+            check(_lib.lib().fhe_bfv_measure_noise_dev(enc._h, sc._h, _dptr(self.s_ntt), _dptr(x), nparts,
+                                                       _dptr(m) if m is not None else None, _dptr(out), b, _stream()))
+            if not host:
+                return out
+            r = out.download()
+            return r if lead else int(r[0])
+        finally:
+            _wipe(staged)
 
 
 class PublicKey:

@@ -567,6 +567,12 @@ struct Ctx {
     // modulus is below 2^50 (zq_f64.hpp; rows of wider moduli are left zero and never read: a launch takes the F64
     // kernels only when every one of its rows qualifies, f64_class below).  Empty when no modulus qualifies.
     DevBuf<k::u64x2> d_tw_f, d_itw_f, d_ninv_f;
+    // The lift's public constants (kernels_noise.hpp: q_i, M_i, q_j^-1 mod q_i with Shoup twins, the limbs of q), per
+    // context -- levels included --, built by the first call that needs them (lift_consts below): handles are shared by
+    // concurrent callers, hence the once_flag.
+    mutable std::once_flag lift_once;
+    mutable DevBuf<u64> d_lift;
+    size_t lift_w = 0;   // W = ceil(bitlen(q) / 64), q the product of the moduli (set at creation, host-only handles too)
 
     const k::u64x2 *dtw_f() const { return root->d_tw_f.p; }
     const k::u64x2 *ditw_f() const { return root->d_itw_f.p; }
@@ -627,6 +633,9 @@ struct Ctx {
 };
 
 inline void ctx_fill_inv_last(Ctx &c) {
+    BigUint q(1);
+    for (u64 m : c.moduli) q = q * BigUint(m);
+    c.lift_w = (q.bits() + 63) / 64;
     c.inv_last.clear();
     c.inv_last_shoup.clear();
     const u64 q_last = c.moduli.back();
@@ -800,6 +809,12 @@ inline bool with_logn_from(size_t logn, std::integer_sequence<int, I...>, F &f) 
 template <int LO, int HI, class F>
 inline void with_logn(size_t logn, const char *what, F &&f) {
     if (!with_logn_from<LO>(logn, std::make_integer_sequence<int, HI - LO + 1>{}, f)) throw StatusError(E_ARG, what);
+}
+
+// the same for any other small integer of a launch (a modulus count): f(int_c<V>) for V == v in [LO, HI]
+template <int LO, int HI, class F>
+inline void with_int(size_t v, const char *what, F &&f) {
+    with_logn<LO, HI>(v, what, std::forward<F>(f));
 }
 
 // f(bool_constant<NARROW>, int_c<HR>) for rows of 2^LM points: the F64 class hr = 3, 4, 5 (Ctx::f64_class) exists for
@@ -2059,24 +2074,26 @@ inline void inner_sum(const Ksk *const *gks, const size_t *exps, size_t ngk, con
 
 // SecretKey::try_decrypt, small-plaintext branch (F/bfv/keys/secret_key.rs:198-247):
 // ct [batch][nparts][L][N] Ntt, s_ntt [L][N] -> out [batch][N] in [0, t).
-inline void decrypt(const Scaler &sc, u64 t, const u64 *s_ntt, const u64 *ct, size_t nparts, u64 *out, size_t batch,
-                    hipStream_t s) {
-    const Ctx &cc = *sc.from, &pc = *sc.to;
-    cc.need_device();
-    require(nparts >= 1, E_ARG, "a ciphertext has at least one part");
+// (the three steps are shared with measure_noise, which lifts the same PowerBasis phase)
+inline void check_plain_context(const Scaler &sc) {
     // (deep levels may be shorter than the plaintext context; only q_0 has to agree, :232-234)
-    require(pc.L >= 1 && pc.moduli[0] == cc.moduli[0], E_PARAMETER_MISMATCH,
+    require(sc.to->L >= 1 && sc.to->moduli[0] == sc.from->moduli[0], E_PARAMETER_MISMATCH,
             "the plaintext context must start with the first ciphertext modulus");
-    if (!batch) return;
-    const ModConsts tm = make_mod_consts(t);
+}
+// c0 + c1 s + c2 s^2 + ... in PowerBasis: ph [batch][L][N]
+inline void phase_power_basis(const Ctx &cc, const u64 *s_ntt, const u64 *ct, size_t nparts, u64 *ph, size_t batch,
+                              hipStream_t s) {
     const u64 PL = (u64)cc.L * cc.n;
-
-    // phase and scaled plaintext are secret-dependent: cleared before the blocks go back to the pool
-    WsGuard ph(batch * PL * sizeof(u64), s, true), d(batch * pc.L * cc.n * sizeof(u64), s, true);
     FHE_LAUNCH("phase", k::phase_kernel, dim3(blocks_for(PL, EW_THREADS), (unsigned)batch), dim3(EW_THREADS), 0, s, ct,
-               s_ntt, ph.u(), cc.dmods(), (uint32_t)nparts, (uint32_t)cc.logn, PL);
-    launch_ntt(cc, true, ph.u(), ph.u(), full_map(cc, cc.L), batch, s);
-    scale_polys(sc, ph.u(), d.u(), batch, false, s);
+               s_ntt, ph, cc.dmods(), (uint32_t)nparts, (uint32_t)cc.logn, PL);
+    launch_ntt(cc, true, ph, ph, full_map(cc, cc.L), batch, s);
+}
+// Scaler::scale (t / q) of the PowerBasis phase, then ((d_0 + t) mod q_0) mod t: out [batch][N]
+inline void decrypt_tail(const Scaler &sc, u64 t, const u64 *ph, u64 *out, size_t batch, hipStream_t s) {
+    const Ctx &cc = *sc.from, &pc = *sc.to;
+    const ModConsts tm = make_mod_consts(t);
+    WsGuard d(batch * pc.L * cc.n * sizeof(u64), s, true);   // the scaled plaintext: secret-dependent
+    scale_polys(sc, ph, d.u(), batch, false, s);
     DevMod q0, tmd;
     static_assert(sizeof(DevMod) == sizeof(ModConsts), "DevMod layout");
     std::memcpy(&q0, &cc.root->mods[0], sizeof(DevMod));  // (host tables live on the chain's root)
@@ -2084,6 +2101,18 @@ inline void decrypt(const Scaler &sc, u64 t, const u64 *s_ntt, const u64 *ct, si
     const u64 total = (u64)batch * cc.n;
     FHE_LAUNCH("decrypt_tail", k::decrypt_tail_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s, d.u(),
                (u64)pc.L * cc.n, out, q0, tmd, (uint32_t)cc.logn, total);
+}
+inline void decrypt(const Scaler &sc, u64 t, const u64 *s_ntt, const u64 *ct, size_t nparts, u64 *out, size_t batch,
+                    hipStream_t s) {
+    const Ctx &cc = *sc.from;
+    cc.need_device();
+    require(nparts >= 1, E_ARG, "a ciphertext has at least one part");
+    check_plain_context(sc);
+    if (!batch) return;
+    // the phase is secret-dependent: cleared before the block goes back to the pool
+    WsGuard ph(batch * (u64)cc.L * cc.n * sizeof(u64), s, true);
+    phase_power_basis(cc, s_ntt, ct, nparts, ph.u(), batch, s);
+    decrypt_tail(sc, t, ph.u(), out, batch, s);
 }
 
 // EvaluationKey::expands (F/bfv/keys/evaluation_key.rs:192-256): ct [batch][2][L][N] ->
@@ -3044,6 +3073,112 @@ inline void add_plain(const Ctx &c, bool subtract, size_t nparts, const u64 *ct,
     FHE_LAUNCH("add_plain", k::add_plain_kernel, dim3(blocks_for(pl, EW_THREADS), (unsigned)batch), dim3(EW_THREADS), 0, s,
                ct, pt, pt_shared ? (u64)0 : pl, out, c.dmods(), (uint32_t)nparts, (uint32_t)c.logn, pl,
                subtract ? 1u : 0u, out != ct ? 1u : 0u);
+}
+
+// --------------------------------------------------------------------- lift and noise ----
+inline BigUint ctx_modulus(const Ctx &c) {
+    BigUint q(1);
+    for (u64 m : c.moduli) q = q * BigUint(m);
+    return q;
+}
+inline size_t lift_limbs(const Ctx &c) { return c.lift_w; }
+
+// The table kernels_noise.hpp describes, built and uploaded once per context.  The upload is a synchronous hipMalloc +
+// hipMemcpy inside the first call: that call blocks the host and cannot be part of a stream capture (fhe_hip.h says so).
+inline const u64 *lift_consts(const Ctx &c) {
+    std::call_once(c.lift_once, [&] {
+        const uint32_t L = (uint32_t)c.L;
+        std::vector<u64> h(k::lift_table_words(L), 0);
+        for (uint32_t i = 0; i < L; i++) {
+            const u64 qi = c.moduli[i];
+            h[i] = qi;
+            h[L + i] = qi * (u64)((((u128)1 << 62) + qi - 1) / qi);
+            for (uint32_t j = 0; j < i; j++) {
+                const u64 inv = inv_mod_general(c.moduli[j] % qi, qi);
+                const size_t at = k::lift_pairs_at(L) + (size_t)i * (i - 1) + 2 * j;
+                h[at] = inv;
+                h[at + 1] = shoup(inv, qi);
+            }
+        }
+        const BigUint q = ctx_modulus(c);
+        for (uint32_t i = 0; i < L; i++) h[k::lift_q_at(L) + i] = q.limb(i);
+        c.d_lift.upload(h);
+    });
+    return c.d_lift.p;
+}
+
+// lift_kernel<L, BITS> over polys [batch][L][N]; the instantiated L = 1 ... 16 cover the stock sets (3, 5, 9), C2 (4) and
+// C5's chain; longer chains take the generic instance.
+constexpr int LIFT_LC_MAX = 16;
+template <bool BITS>
+inline void launch_lift(const Ctx &c, const u64 *polys, const k::LiftSub &sub, u64 *out, uint32_t *partial, size_t w,
+                        size_t batch, hipStream_t s) {
+    require(c.L <= (size_t)k::LIFT_LMAX, E_ARG, "lift: more moduli than the generic instance holds");
+    const u64 nblk = blocks_for(c.n, k::LIFT_THREADS);
+    require(batch * nblk <= 0x7fffffffu, E_ARG, "lift: batch exceeds the grid limit");
+    const u64 *tab = lift_consts(c);
+    const dim3 grid((unsigned)(batch * nblk)), block(k::LIFT_THREADS);
+    const size_t lds = BITS ? k::LIFT_SMEM_BYTES : 0;
+    const char *name = BITS ? "centered_bits" : "lift";
+    if (c.L <= (size_t)LIFT_LC_MAX)
+        with_int<1, LIFT_LC_MAX>(c.L, "lift: no moduli", [&](auto lc) {
+            launch_k<k::lift_kernel<decltype(lc)::value, BITS>>(name, grid, block, lds, s, polys, tab, sub, out, partial,
+                                                                (uint32_t)c.L, (uint32_t)w, (uint32_t)c.logn, (uint32_t)nblk,
+                                                                (uint32_t)batch);
+        });
+    else
+        launch_k<k::lift_kernel<0, BITS>>(name, grid, block, lds, s, polys, tab, sub, out, partial, (uint32_t)c.L, (uint32_t)w,
+                                          (uint32_t)c.logn, (uint32_t)nblk, (uint32_t)batch);
+}
+
+// RnsContext::lift per coefficient (M/rns/mod.rs:138-143): polys [batch][L][N] -> out [batch][N][W] limbs.
+inline void poly_lift(const Ctx &c, const u64 *polys, u64 *out, size_t batch, hipStream_t s) {
+    c.need_device();
+    if (!batch) return;
+    launch_lift<false>(c, polys, k::LiftSub{nullptr, nullptr, 0, k::u64x2{0, 0}}, out, nullptr, lift_limbs(c), batch, s);
+}
+
+// max over the coefficients of min(bits(x), bits(q - x)) (secret_key.rs:88-95) of polys [batch][L][N] minus, when
+// sub.m is given, the Delta-scaled plaintext: the per-workgroup maxima go through wiping scratch, then one thread per
+// polynomial reduces them.
+inline void centered_bits(const Ctx &c, const u64 *polys, const k::LiftSub &sub, u64 *out_bits, size_t batch,
+                          hipStream_t s) {
+    c.need_device();
+    if (!batch) return;
+    const size_t nblk = blocks_for(c.n, k::LIFT_THREADS);
+    WsGuard part(batch * nblk * sizeof(uint32_t), s, true);
+    launch_lift<true>(c, polys, sub, nullptr, (uint32_t *)part.p, 0, batch, s);
+    FHE_LAUNCH("noise_max", k::noise_max_kernel, dim3(blocks_for(batch, EW_THREADS)), dim3(EW_THREADS), 0, s,
+               (const uint32_t *)part.p, (uint32_t)nblk, (uint32_t)batch, out_bits);
+}
+
+// SecretKey::measure_noise (F/bfv/keys/secret_key.rs:55-98): the phase in PowerBasis minus Plaintext::to_poly of m --
+// the ciphertext's own decryption (m == null, the reference) or the plaintext the caller expects, [batch][N] in
+// [0, t) --, lifted and measured.  ct [batch][nparts][L][N] Ntt, s_ntt [L][N] -> noise_bits [batch].
+inline void measure_noise(const Encoder &e, const Scaler &sc, const u64 *s_ntt, const u64 *ct, size_t nparts, const u64 *m,
+                          u64 *noise_bits, size_t batch, hipStream_t s) {
+    const Ctx &cc = *sc.from;
+    cc.need_device();
+    require(nparts >= 1, E_ARG, "a ciphertext has at least one part");
+    size_t level = 0;
+    const Ctx *lc = e.top;
+    while (lc && !lc->same_ring(cc)) lc = lc->next.get(), level++;
+    require(lc != nullptr, E_PARAMETER_MISMATCH, "the ciphertext context is not a level of the encoder's parameter set");
+    require(e.top->device == cc.device, E_PARAMETER_MISMATCH, "the encoder and the scaler's context live on different devices");
+    if (!m) check_plain_context(sc);
+    if (!batch) return;
+    const u64 PL = (u64)cc.L * cc.n;
+    // phase, decrypted coefficients (and centered_bits' partial maxima) are secret-dependent: cleared before reuse
+    WsGuard ph(batch * PL * sizeof(u64), s, true);
+    phase_power_basis(cc, s_ntt, ct, nparts, ph.u(), batch, s);
+    std::unique_ptr<WsGuard> dec;
+    if (!m) {
+        dec = std::make_unique<WsGuard>(batch * cc.n * sizeof(u64), s, true);
+        decrypt_tail(sc, e.t, ph.u(), dec->u(), batch, s);
+        m = dec->u();
+    }
+    const u64 qmt = e.q_mod_t[level];
+    centered_bits(cc, ph.u(), k::LiftSub{m, e.d_delta[level]->p, e.t, k::u64x2{qmt, shoup(qmt, e.t)}}, noise_bits, batch, s);
 }
 
 }  // namespace fhe

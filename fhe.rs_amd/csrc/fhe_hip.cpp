@@ -1655,6 +1655,53 @@ fhe_status fhe_bfv_add_plain_dev(const fhe_ctx *ctx, int subtract, size_t nparts
     });
 }
 
+// --------------------------------------------------------------------- lift and noise ----
+// Device-pointer forms only: the phase and the error polynomial never pass through host memory.
+size_t fhe_ctx_lift_limbs(const fhe_ctx *ctx) { return ctx ? lift_limbs(*ctx->c) : 0; }
+fhe_status fhe_poly_lift_dev(const fhe_ctx *ctx, const uint64_t *polys, uint64_t *out, size_t batch, void *stream) {
+    return guard([&] {
+        need(ctx, "ctx");
+        const Ctx &c = *ctx->c;
+        c.need_device();
+        if (batch) {
+            need(polys, "polys");
+            need(out, "out");
+        }
+        set_device(c);
+        poly_lift(c, polys, out, batch, as_stream(stream));
+    });
+}
+fhe_status fhe_poly_centered_bits_dev(const fhe_ctx *ctx, const uint64_t *polys, uint64_t *out_bits, size_t batch,
+                                      void *stream) {
+    return guard([&] {
+        need(ctx, "ctx");
+        const Ctx &c = *ctx->c;
+        c.need_device();
+        if (batch) {
+            need(polys, "polys");
+            need(out_bits, "out_bits");
+        }
+        set_device(c);
+        centered_bits(c, polys, k::LiftSub{nullptr, nullptr, 0, k::u64x2{0, 0}}, out_bits, batch, as_stream(stream));
+    });
+}
+fhe_status fhe_bfv_measure_noise_dev(const fhe_encoder *enc, const fhe_scaler *sc, const uint64_t *s_ntt, const uint64_t *ct,
+                                     size_t nparts, const uint64_t *m_or_null, uint64_t *noise_bits, size_t batch,
+                                     void *stream) {
+    return guard([&] {
+        need(enc, "encoder");
+        need(sc, "cipher_plain_scaler");
+        sc->s->from->need_device();
+        if (batch) {
+            need(s_ntt, "s_ntt");
+            need(ct, "ct");
+            need(noise_bits, "noise_bits");
+        }
+        set_device(*sc->s->from);
+        measure_noise(*enc->e, *sc->s, s_ntt, ct, nparts, m_or_null, noise_bits, batch, as_stream(stream));
+    });
+}
+
 // ------------------------------------------------------------------------- encryption ----
 // Device-pointer forms only, like the encoding entry points: secrets and errors are never staged through host memory
 // by the engine.

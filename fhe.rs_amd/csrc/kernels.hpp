@@ -30,6 +30,7 @@
 //                           PublicKey::try_encrypt   M/rq/mod.rs:298-330, F/bfv/keys/secret_key.rs:100-134, public_key.rs:47-97
 //   ksk_seeds_kernel, cbd_sample_at_kernel, ksk_consts_kernel, ksk_gen_kernel, galois_from_kernel   KeySwitchingKey::new,
 //                           RelinearizationKey / GaloisKey::new   F/bfv/keys/key_switching_key.rs:71-236, galois_key.rs:26-58
+//   lift_kernel, noise_max_kernel       RnsContext::lift, SecretKey::measure_noise   M/rns/mod.rs:138-143, F/bfv/keys/secret_key.rs:55-98
 // Compile-time knobs live in knobs.hpp (pinned in the release build); rejected kernel variants in tools/lab/ (lab builds only).
 #pragma once
 #include "kernels_common.hpp"
@@ -41,6 +42,7 @@
 #include "kernels_encode.hpp"
 #include "kernels_encrypt.hpp"
 #include "kernels_keygen.hpp"
+#include "kernels_noise.hpp"
 
 namespace fhe {
 namespace k {

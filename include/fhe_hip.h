@@ -572,6 +572,38 @@ fhe_status fhe_ksk_export_dev(const fhe_ksk *ksk, uint64_t *c0, uint64_t *c1, ui
 /* A key's digit count: each of fhe_ksk_export_dev's arrays holds ndigits * Lk * N words (0 for NULL). */
 size_t fhe_ksk_ndigits(const fhe_ksk *ksk);
 
+/* ------------------------------------------------------------ lift and noise ---- */
+/* Residues to integers, and the noise of a ciphertext.  Device-pointer forms only, with no host-pointer twin: the phase
+ * and the error polynomial are secret-dependent and are never staged through host memory by the engine.  batch == 0 is
+ * a no-op (NULL buffers allowed).  The lift's public constants (q_j^-1 mod q_i, the limbs of q) are built per context
+ * by the first call that needs them, with a synchronous allocation and copy: concurrent first calls on a shared handle
+ * are safe, but that first call blocks the host and must not be made while its stream is being captured into a graph
+ * -- make one call per context (batch 1 will do) before capturing. */
+/* W = ceil(bitlen(q) / 64) for q the product of ctx's moduli: the limbs per coefficient fhe_poly_lift_dev writes
+ * (0 for a NULL handle; works on host-only handles). */
+size_t fhe_ctx_lift_limbs(const fhe_ctx *ctx);
+/* RnsContext::lift (M/rns/mod.rs:138-143) per coefficient, as Vec<BigUint>::from(&Poly) applies it
+ * (M/rq/convert.rs:507-529): polys [batch][L][N] canonical residues (any representation: the lift is per coefficient;
+ * not modified) -> out [batch][N][W] little-endian u64 limbs of the unique x in [0, q) with x = r_i mod q_i. */
+fhe_status fhe_poly_lift_dev(const fhe_ctx *ctx, const uint64_t *polys, uint64_t *out, size_t batch, void *stream);
+/* The loop of SecretKey::measure_noise (F/bfv/keys/secret_key.rs:88-95) on its own: out_bits[b] = max over the N
+ * coefficients of polys[b] of min(bits(x), bits(q - x)), x as in fhe_poly_lift_dev, bits(0) = 0.  No limbs are written;
+ * the maximum is per polynomial. */
+fhe_status fhe_poly_centered_bits_dev(const fhe_ctx *ctx, const uint64_t *polys, uint64_t *out_bits, size_t batch,
+                                      void *stream);
+/* SecretKey::measure_noise (F/bfv/keys/secret_key.rs:55-98): noise_bits[b] = the centered bit length of
+ * phase(ct[b]) - Plaintext::to_poly(m[b]) (F/bfv/plaintext.rs:172-196), in PowerBasis.  ct [batch][nparts][L][N] Ntt and
+ * s_ntt as fhe_bfv_decrypt_dev takes them; the ciphertext context is cipher_plain_scaler's `from`, which must be a
+ * level of enc's parameter set (else FHE_E_PARAMETER_MISMATCH) and selects enc's q_mod_t and delta.
+ * m_or_null == NULL: m is the ciphertext's own decryption (fhe_bfv_decrypt_dev's value), exactly the reference.
+ * m_or_null [batch][N] coefficients in [0, t): the noise against the plaintext the caller expects -- it keeps growing
+ * past the point where the ciphertext stops decrypting to m.  nparts == 0 -> FHE_E_ARG.
+ * Phase, scaled plaintext, decrypted coefficients and partial maxima live in engine scratch that is cleared before it
+ * is reused; m_or_null and noise_bits are the caller's to clear. */
+fhe_status fhe_bfv_measure_noise_dev(const fhe_encoder *enc, const fhe_scaler *cipher_plain_scaler, const uint64_t *s_ntt,
+                                     const uint64_t *ct, size_t nparts, const uint64_t *m_or_null, uint64_t *noise_bits,
+                                     size_t batch, void *stream);
+
 /* ------------------------------------------------- zq::primes (host, no GPU) ---- */
 /* generate_prime (M/zq/primes.rs:30-59): returns 0 when none exists. */
 uint64_t fhe_generate_prime(size_t num_bits, uint64_t modulo, uint64_t upper_bound);

@@ -806,6 +806,35 @@ impl HipEncoder {
         Ok(out)
     }
 }
+impl HipEncoder {
+    /// `SecretKey::measure_noise` (keys/secret_key.rs:55-98) on a device-resident batch: the bits of noise of each
+    /// ciphertext, `[batch]`.  `scaler`: the cipher-to-plaintext scaler of the ciphertexts' level (as
+    /// `HipScaler::decrypt_dev`), whose source context must be a level of this encoder's parameter set; `s_ntt`
+    /// `[L][N]` over it.  `expected`: `None` measures against the ciphertext's own decryption (the reference);
+    /// `Some` `[batch][N]` coefficients in [0, t) measures against the plaintext the caller expects
+    /// (`fhe_bfv_measure_noise_dev`; the phase and the error stay in engine scratch that is cleared before reuse).
+    pub fn measure_noise_dev(&self, scaler: &HipScaler, s_ntt: &DeviceBuffer, ct: &DeviceCiphertexts,
+                             expected: Option<&DeviceBuffer>, stream: &Stream) -> Result<DeviceBuffer> {
+        let from = scaler.from_ctx();
+        expect_len("measure_noise_dev secret key", s_ntt.len(), from.poly_words())?;
+        if ct.rows != from.nmoduli() || ct.degree != from.degree() {
+            return Err(shape_error("measure_noise_dev: the ciphertexts are not over the scaler's source context"));
+        }
+        let m = match expected {
+            None => ptr::null(),
+            Some(p) => {
+                expect_len("measure_noise_dev expected plaintexts", p.len(), ct.batch * ct.degree)?;
+                p.as_ptr()
+            }
+        };
+        let out = DeviceBuffer::alloc_on(from.device(), ct.batch.max(1), stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_measure_noise_dev(self.ptr, scaler.as_ptr(), s_ntt.as_ptr(), ct.buf.as_ptr(), ct.parts, m,
+                                           out.as_mut_ptr(), ct.batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+}
 impl Drop for HipEncoder {
     fn drop(&mut self) { unsafe { ffi::fhe_encoder_destroy(self.ptr) } }
 }
@@ -1060,6 +1089,25 @@ impl CtxView<'_> {
             ffi::fhe_bfv_encrypt_pk_dev(self.ptr, variance, pk.buf.as_ptr(), seeds.as_ptr(), pp, shared as c_int,
                                         out.buf.as_mut_ptr(), seeds.batch, stream.as_ptr())
         })?;
+        Ok(out)
+    }
+    /// W = ceil(bitlen(q) / 64): the limbs per coefficient `lift_dev` writes (`fhe_ctx_lift_limbs`).
+    pub fn lift_limbs(&self) -> usize { unsafe { ffi::fhe_ctx_lift_limbs(self.ptr) } }
+    /// `RnsContext::lift` per coefficient (rns/mod.rs:138-143, as `Vec<BigUint>::from(&Poly)` applies it): `polys`
+    /// `[batch][L][N]` canonical residues in any representation -> `[batch][N][W]` little-endian u64 limbs of the
+    /// integers in [0, q).
+    pub fn lift_dev(&self, polys: &DeviceBuffer, stream: &Stream) -> Result<DeviceBuffer> {
+        let batch = whole_batch("lift_dev polynomials", polys.len(), self.poly_words())?;
+        let out = DeviceBuffer::alloc_on(self.device(), (batch * self.degree() * self.lift_limbs()).max(1), stream)?;
+        check(unsafe { ffi::fhe_poly_lift_dev(self.ptr, polys.as_ptr(), out.as_mut_ptr(), batch, stream.as_ptr()) })?;
+        Ok(out)
+    }
+    /// The loop of `SecretKey::measure_noise` (secret_key.rs:88-95) on its own: per polynomial of `polys`
+    /// `[batch][L][N]`, the maximum over its coefficients of min(bits(x), bits(q - x)) -> `[batch]`.
+    pub fn centered_bits_dev(&self, polys: &DeviceBuffer, stream: &Stream) -> Result<DeviceBuffer> {
+        let batch = whole_batch("centered_bits_dev polynomials", polys.len(), self.poly_words())?;
+        let out = DeviceBuffer::alloc_on(self.device(), batch.max(1), stream)?;
+        check(unsafe { ffi::fhe_poly_centered_bits_dev(self.ptr, polys.as_ptr(), out.as_mut_ptr(), batch, stream.as_ptr()) })?;
         Ok(out)
     }
     /// (plaintext pointer, shared) of an encryption's optional plaintext operand for `batch` items.
