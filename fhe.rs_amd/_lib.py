@@ -160,6 +160,14 @@ SIGNATURES = {
     "fhe_poly_lift_dev": (i32, [vp, vp, vp, sz, vp]),
     "fhe_poly_centered_bits_dev": (i32, [vp, vp, vp, sz, vp]),
     "fhe_bfv_measure_noise_dev": (i32, [vp, vp, vp, vp, sz, vp, vp, sz, vp]),
+    "fhe_mbfv_pk_share_dev": (i32, [vp, sz, vp, vp, i32, vp, vp, sz, vp]),
+    "fhe_mbfv_sks_share_dev": (i32, [vp, sz, vp, vp, i32, vp, sz, vp, vp, sz, vp]),
+    "fhe_mbfv_pks_share_dev": (i32, [vp, sz, vp, i32, vp, vp, i32, vp, vp, sz, vp]),
+    "fhe_mbfv_rlk_round1_dev": (i32, [vp, sz, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
+    "fhe_mbfv_rlk_round2_dev": (i32, [vp, sz, vp, vp, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "fhe_mbfv_aggregate_dev": (i32, [vp, vp, sz, sz, sz, vp, vp, vp]),
+    "fhe_mbfv_relin_key_aggregate_dev": (i32, [vp, vp, vp, sz, sz, vp, vp, C.POINTER(vp)]),
+    "fhe_mbfv_decrypt_dev": (i32, [vp, u64, vp, vp, sz, sz, vp, sz, vp]),
     "fhe_generate_prime": (u64, [sz, u64, u64]),
     "fhe_supports_opt": (i32, [u64]),
     "fhe_is_prime": (i32, [u64]),

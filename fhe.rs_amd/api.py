@@ -1310,6 +1310,15 @@ class PublicKey:
         self.c = c.reshape(2, c.shape[-2], c.shape[-1])
         self._levels = {0: self.c}
 
+    @classmethod
+    def from_ciphertext(cls, params, c):
+        """A key whose ciphertext c [2, L, N] (Ntt, level 0, on the device) was made elsewhere: the collective key of the
+        multiparty protocol (`PublicKeyShare.aggregate`)."""
+        self = cls.__new__(cls)
+        self.params, self.c = params, c
+        self._levels = {0: c}
+        return self
+
     def at_level(self, level):
         """The key over the context of `level` (Ciphertext::switch_down until the level matches, public_key.rs:66-74)."""
         if level not in self._levels:
@@ -1699,3 +1708,408 @@ def device_mem_info(device=0):
     f, t = C.c_size_t(), C.c_size_t()
     check(_lib.lib().fhe_device_mem_info(device, C.byref(f), C.byref(t)))
     return f.value, t.value
+
+
+# ---- multiparty BFV (crates/fhe/src/mbfv/): shares and their aggregation on the device -------------------------
+# A party's secret is a `SecretKey` (s_ntt [L, N] on the device); `SecretKey(params, s)` with s [P, L, N] holds P
+# parties, and every share made from it carries that leading party dimension: one call makes all P shares.  Public
+# inputs (the CRP, ciphertexts, a public key) are numpy arrays, torch tensors or DeviceArrays; numpy in -> numpy out.
+
+def _dev_copy(dst, src, nbytes):
+    check(_lib.lib().fhe_buf_copy_async(C.c_void_p(dst.data_ptr()), C.c_void_p(src.data_ptr()), nbytes, _stream()))
+
+
+def _nbytes(x):
+    return int(x.numel()) * int(x.element_size())
+
+
+class _Staging:
+    """Device copies of the host inputs of one call (cleared again when `secret`), and the kind of its result."""
+
+    def __init__(self, params, ref):
+        self.device = max(params.device, 0)
+        self.host = not _is_dev(ref)
+        self.ref = ref
+        self.secret = []
+        self.keep = []    # (staged copies stay alive until the object goes: the calls that read them are enqueued by then)
+
+    def dev(self, x):
+        if _is_dev(x):
+            return x
+        d = DeviceArray.from_numpy(_np(x), self.device)
+        self.keep.append(d)
+        return d
+
+    def seeds(self, seeds, count):
+        sd, n, own = _seeds(seeds, count, self.device)
+        if own:
+            self.secret.append(sd)
+        if n != count:
+            raise FheError(-1, "one seed per share: %d shares, %d seeds" % (count, n))
+        return sd
+
+    def out(self, shape):
+        return DeviceArray(shape, self.device) if self.host else _empty_dev(self.ref, shape)
+
+    def give(self, x):
+        return x.download() if self.host else x
+
+    def done(self):
+        _wipe(self.secret)
+
+
+def _parties(sk, params):
+    """(party count or None, s_shared) of a SecretKey whose s_ntt is [L, N] or [P, L, N] over level 0."""
+    sh = tuple(int(d) for d in sk.s_ntt.shape)
+    if sh[-2:] != (len(params.moduli), params.degree) or len(sh) not in (2, 3):
+        raise FheError(-1, "the secret must be [L, N] or [parties, L, N] over the level-0 context")
+    return (None, 1) if len(sh) == 2 else (sh[0], 0)
+
+
+def _level_ctx(params, level):
+    if not 0 <= level <= params.max_level:
+        raise FheError(-12, "InvalidLevel")
+    return params.context_at_level(level)
+
+
+def _mbfv_sum(ctx, shares, nshares, stride, npolys, base, out):
+    check(_lib.lib().fhe_mbfv_aggregate_dev(ctx._h, _dptr(shares), nshares, stride, npolys,
+                                            _dptr(base) if base is not None else None, _dptr(out), _stream()))
+
+
+def _first_share(shares):
+    """One party-batched share, or the first of a list (an empty list is the reference's NoShares)."""
+    if not isinstance(shares, (list, tuple)):
+        return shares
+    if not shares:
+        raise FheError(-1, "NoShares: an aggregation needs at least one share")
+    return shares[0]
+
+
+def _stack_shares(st, shares, attr):
+    """The share arrays of one party-batched share (leading party dimension) or of a list of single-party shares, as
+    one device array [P, ...] (a list is copied into one; numpy arrays are uploaded)."""
+    if not isinstance(shares, (list, tuple)):
+        a = getattr(shares, attr)
+        if not shares.parties:
+            a = a.reshape((1,) + tuple(int(d) for d in a.shape))
+        return st.dev(a)
+    if not shares:
+        raise FheError(-1, "NoShares")
+    parts = [getattr(s, attr) for s in shares]
+    if any(s.parties for s in shares):
+        raise FheError(-1, "a list holds single-party shares; a share with a party dimension aggregates on its own")
+    if not _is_dev(parts[0]):
+        return st.dev(np.stack([_np(p) for p in parts]))
+    out = _empty_dev(parts[0], (len(parts),) + tuple(int(d) for d in parts[0].shape))
+    for i, p in enumerate(parts):
+        _dev_copy(out[i], p, _nbytes(p))
+    return out
+
+
+class CommonRandomPoly:
+    """mbfv::CommonRandomPoly (mbfv/crp.rs): `poly` [L, N] Ntt over the level-0 context, or [count, L, N] for a vector
+    (CommonRandomPoly::new_vec: one per ciphertext modulus for the relinearization-key protocol)."""
+
+    def __init__(self, params, poly):
+        sh = tuple(int(d) for d in poly.shape)
+        if sh[-2:] != (len(params.moduli), params.degree) or len(sh) not in (2, 3):
+            raise FheError(-1, "a common random polynomial is [L, N] (a vector: [count, L, N]) over the level-0 context")
+        self.params, self.poly = params, poly
+
+    @classmethod
+    def from_seed(cls, params, seeds):
+        """The CRP every party derives from a public seed: Poly::random_from_seed per 32-byte seed
+        (fhe_poly_from_seed_dev).  One seed -> [L, N]; a list or a [count, 32] array -> the vector [count, L, N]."""
+        one = isinstance(seeds, (bytes, bytearray))
+        ctx = params.context_at_level(0)
+        if not _is_dev(seeds):   # host seeds -> a numpy polynomial (numpy in -> numpy out, as everywhere)
+            if isinstance(seeds, (list, tuple)):
+                seeds = b"".join(bytes(x) for x in seeds)
+            if isinstance(seeds, (bytes, bytearray)):
+                seeds = np.frombuffer(bytes(seeds), dtype=np.uint8)
+        p = ctx.random_from_seed(seeds)
+        return cls(params, p[0] if one else p)
+
+
+class PublicKeyShare:
+    """mbfv::PublicKeyShare (mbfv/public_key_gen.rs:32-57): p0_share = e - crp (.) s, [L, N] ([P, L, N] for P parties);
+    one Poly::small draw of ChaCha8Rng::from_seed(seeds[party]) each."""
+
+    def __init__(self, sk, crp, seeds=None):
+        par = self.params = sk.params
+        self.crp = crp
+        if len(crp.poly.shape) != 2:
+            raise FheError(-1, "the public-key protocol takes one common random polynomial")
+        P, shared = _parties(sk, par)
+        self.parties = P is not None
+        ctx = par.context_at_level(0)
+        st = _Staging(par, crp.poly)
+        try:
+            sd = st.seeds(seeds, P or 1)
+            out = st.out(((P,) if self.parties else ()) + (ctx.nmoduli, par.degree))
+            check(_lib.lib().fhe_mbfv_pk_share_dev(ctx._h, par.variance, _dptr(st.dev(crp.poly)), _dptr(sk.s_ntt), shared,
+                                                   _dptr8(sd), _dptr(out), P or 1, _stream()))
+            self.p0_share = st.give(out)
+        finally:
+            st.done()
+
+    @staticmethod
+    def aggregate(shares):
+        """PublicKey::from_shares (public_key_gen.rs:60-77): [sum of the p0 shares, crp] as a `PublicKey`."""
+        first = _first_share(shares)
+        par, crp = first.params, first.crp
+        ctx = par.context_at_level(0)
+        st = _Staging(par, first.p0_share)
+        h = _stack_shares(st, shares, "p0_share")
+        PL = ctx.nmoduli * par.degree
+        c = _alloc((2, ctx.nmoduli, par.degree), par.device)
+        _mbfv_sum(ctx, h, int(h.shape[0]), PL, 1, None, c[0])
+        _dev_copy(c[1], st.dev(crp.poly), PL * 8)
+        return PublicKey.from_ciphertext(par, c)
+
+
+class SecretKeySwitchShare:
+    """mbfv::SecretKeySwitchShare (mbfv/secret_key_switch.rs:38-95): h = e + c1 (.) (s_in - s_out) for every ciphertext
+    of ct [..., 2, L - level, N]: h_share [..., L - level, N], with a leading party dimension when the keys hold P
+    parties.  One Poly::small draw per (party, ciphertext), seeds in that order."""
+
+    def __init__(self, sk_in, sk_out, ct, level=0, seeds=None):
+        par = self.params = sk_in.params
+        self.level, self.ct = level, ct
+        ctx = _level_ctx(par, level)
+        P, shared = _parties(sk_in, par)
+        if sk_out is not None and _parties(sk_out, par) != (P, shared):
+            raise FheError(-3, "ParameterMismatch: the input and output secrets hold different parties")
+        self.parties = P is not None
+        if tuple(int(d) for d in ct.shape[-3:]) != (2, ctx.nmoduli, par.degree):
+            raise FheError(-13, "InvalidPolynomialCount: the multiparty switches take ciphertexts of 2 parts at `level`")
+        lead = tuple(int(d) for d in ct.shape[:-3])
+        B = int(np.prod(lead)) if lead else 1
+        PL = ctx.nmoduli * par.degree
+        L = _lib.lib()
+        st = _Staging(par, ct)
+        try:
+            sd = st.seeds(seeds, (P or 1) * B)
+            x = st.dev(ct).reshape((B, 2, ctx.nmoduli, par.degree))
+            out = st.out(((P,) if self.parties else ()) + lead + (ctx.nmoduli, par.degree))
+            c1 = C.c_void_p(_dptr(x).value + PL * 8)
+            s_out = lambda p: None if sk_out is None else _dptr(sk_out.s_ntt if p is None else sk_out.s_ntt[p])   # noqa: E731
+            if not self.parties:
+                check(L.fhe_mbfv_sks_share_dev(ctx._h, par.variance, _dptr(sk_in.s_ntt), s_out(None), 1, c1, 2 * PL,
+                                               _dptr8(sd), _dptr(out), B, _stream()))
+            elif B == 1:   # P parties, one ciphertext: one call, a secret per item
+                check(L.fhe_mbfv_sks_share_dev(ctx._h, par.variance, _dptr(sk_in.s_ntt), s_out(None), 0, c1, 0, _dptr8(sd),
+                                               _dptr(out), P, _stream()))
+            else:          # P parties, B ciphertexts: one call per party, its secret shared by the batch
+                for p in range(P):
+                    check(L.fhe_mbfv_sks_share_dev(ctx._h, par.variance, _dptr(sk_in.s_ntt[p]), s_out(p), 1, c1, 2 * PL,
+                                                   C.c_void_p(_dptr8(sd).value + 32 * B * p), _dptr(out[p]), B, _stream()))
+            self.h_share = st.give(out)
+        finally:
+            st.done()
+
+    @staticmethod
+    def _summed(shares):
+        """(params, level, ctx, staging, c0 + sum of the shares [B, L, N] on the device, the ciphertexts [B, 2, L, N])"""
+        first = _first_share(shares)
+        par, level = first.params, first.level
+        ctx = _level_ctx(par, level)
+        st = _Staging(par, first.h_share)
+        h = _stack_shares(st, shares, "h_share")
+        PL = ctx.nmoduli * par.degree
+        B = int(np.prod(h.shape[1:-2])) if len(h.shape) > 3 else 1
+        x = st.dev(first.ct).reshape((B, 2, ctx.nmoduli, par.degree))
+        return par, ctx, st, h, x, B, PL
+
+    @staticmethod
+    def aggregate(shares):
+        """Ciphertext::from_shares (secret_key_switch.rs:98-115): [c0 + sum of the shares, c1], shaped like the input
+        ciphertexts."""
+        first = _first_share(shares)
+        par, ctx, st, h, x, B, PL = SecretKeySwitchShare._summed(shares)
+        out = st.out(tuple(int(d) for d in first.ct.shape))
+        _dev_copy(out, x, B * 2 * PL * 8)
+        # (c0 of ciphertext b sits at b 2 L N: one launch per ciphertext keeps the aggregator's contiguous layout)
+        o = out.reshape((B, 2, ctx.nmoduli, par.degree))
+        for b in range(B):
+            check(_lib.lib().fhe_mbfv_aggregate_dev(ctx._h, C.c_void_p(_dptr(h).value + b * PL * 8), int(h.shape[0]), B * PL,
+                                                    1, _dptr(o[b][0]), _dptr(o[b][0]), _stream()))
+        return st.give(out)
+
+
+class DecryptionShare(SecretKeySwitchShare):
+    """mbfv::DecryptionShare (mbfv/secret_key_switch.rs:133-142): the key switch to the zero key, h = e + c1 (.) s."""
+
+    def __init__(self, sk, ct, level=0, seeds=None):
+        super().__init__(sk, None, ct, level, seeds)
+
+    @staticmethod
+    def aggregate(shares):
+        """Plaintext::from_shares (secret_key_switch.rs:145-186, fhe_mbfv_decrypt_dev): the plaintext coefficients
+        [..., N] in [0, t) (`Encoder.decode` turns them into values)."""
+        first = _first_share(shares)
+        par, ctx, st, h, x, B, PL = SecretKeySwitchShare._summed(shares)
+        sc = par.plain_scaler(first.level)
+        out = st.out(tuple(int(d) for d in first.ct.shape[:-3]) + (par.degree,))
+        check(_lib.lib().fhe_mbfv_decrypt_dev(sc._h, int(par.plaintext), _dptr(x), _dptr(h), int(h.shape[0]), B * PL,
+                                              _dptr(out), B, _stream()))
+        if not st.host:
+            return out
+        try:
+            return out.download()
+        finally:
+            _wipe([out])   # (the plaintext coefficients)
+
+
+class PublicKeySwitchShare:
+    """mbfv::PublicKeySwitchShare (mbfv/public_key_switch.rs:33-92): h0 = pk0 (.) u + s (.) c1 + e0, h1 = pk1 (.) u + e1
+    for every ciphertext of ct [..., 2, L - level, N]: `h` [..., 2, L - level, N], with a leading party dimension when
+    the key holds P parties.  Three draws (u, e0, e1) of one seed per (party, ciphertext)."""
+
+    def __init__(self, sk, pk, ct, level=0, seeds=None):
+        par = self.params = sk.params
+        self.level, self.ct = level, ct
+        ctx = _level_ctx(par, level)
+        P, shared = _parties(sk, par)
+        self.parties = P is not None
+        if tuple(int(d) for d in ct.shape[-3:]) != (2, ctx.nmoduli, par.degree):
+            raise FheError(-13, "InvalidPolynomialCount: the multiparty switches take ciphertexts of 2 parts at `level`")
+        lead = tuple(int(d) for d in ct.shape[:-3])
+        B = int(np.prod(lead)) if lead else 1
+        L = _lib.lib()
+        st = _Staging(par, ct)
+        try:
+            sd = st.seeds(seeds, (P or 1) * B)
+            x = st.dev(ct)
+            pkl = st.dev(pk.at_level(level))
+            out = st.out(((P,) if self.parties else ()) + lead + (2, ctx.nmoduli, par.degree))
+            if not self.parties:
+                check(L.fhe_mbfv_pks_share_dev(ctx._h, par.variance, _dptr(sk.s_ntt), 1, _dptr(pkl), _dptr(x), 0,
+                                               _dptr8(sd), _dptr(out), B, _stream()))
+            elif B == 1:
+                check(L.fhe_mbfv_pks_share_dev(ctx._h, par.variance, _dptr(sk.s_ntt), 0, _dptr(pkl), _dptr(x), 1,
+                                               _dptr8(sd), _dptr(out), P, _stream()))
+            else:
+                for p in range(P):
+                    check(L.fhe_mbfv_pks_share_dev(ctx._h, par.variance, _dptr(sk.s_ntt[p]), 1, _dptr(pkl), _dptr(x), 0,
+                                                   C.c_void_p(_dptr8(sd).value + 32 * B * p), _dptr(out[p]), B, _stream()))
+            self.h = st.give(out)
+        finally:
+            st.done()
+
+    @staticmethod
+    def aggregate(shares):
+        """Ciphertext::from_shares (public_key_switch.rs:95-113): [c0 + sum of the h0 shares, sum of the h1 shares]."""
+        first = _first_share(shares)
+        par = first.params
+        ctx = _level_ctx(par, first.level)
+        st = _Staging(par, first.h)
+        h = _stack_shares(st, shares, "h")
+        PL = ctx.nmoduli * par.degree
+        B = int(np.prod(h.shape[1:-3])) if len(h.shape) > 4 else 1
+        x = st.dev(first.ct)
+        out = st.out(tuple(int(d) for d in first.ct.shape))
+        # base: the ciphertexts' c0 with zero second parts
+        check(_lib.lib().fhe_buf_zero_async(C.c_void_p(out.data_ptr()), B * 2 * PL * 8, _stream()))
+        o, xi = out.reshape((B, 2, ctx.nmoduli, par.degree)), x.reshape((B, 2, ctx.nmoduli, par.degree))
+        for b in range(B):
+            _dev_copy(o[b][0], xi[b][0], PL * 8)
+        _mbfv_sum(ctx, h, int(h.shape[0]), B * 2 * PL, 2 * B, out, out)
+        return st.give(out)
+
+
+class RelinKeyGenerator:
+    """mbfv::RelinKeyGenerator (mbfv/relin_key_gen.rs:65-110): the two rounds of the relinearization-key protocol for
+    one party, or for P parties when `sk` holds P secrets.  `u` is the party's ephemeral secret (RelinKeyGenerator::new's
+    Poly::small draw of ChaCha8Rng::from_seed(u_seeds[party])); it stays on the device."""
+
+    def __init__(self, sk, crp, u_seeds=None):
+        par = self.params = sk.params
+        ctx = par.context_at_level(0)
+        if ctx.nmoduli == 1:
+            raise FheError(-17, "KeySwitchingNotSupported")
+        if len(crp.poly.shape) != 3 or int(crp.poly.shape[0]) != ctx.nmoduli:
+            raise FheError(-1, "InvalidCommonRandomPolynomialCount: one common random polynomial per ciphertext modulus")
+        self.sk, self.crp = sk, crp
+        self.P, self.shared = _parties(sk, par)
+        count = self.P or 1
+        sd, n, own = _seeds(u_seeds, count, par.device)
+        try:
+            if n != count:
+                raise FheError(-1, "one seed per party")
+            u = _alloc((count, ctx.nmoduli, par.degree), par.device)
+            check(_lib.lib().fhe_bfv_sample_small_dev(ctx._h, par.variance, _dptr8(sd), 1, _dptr(u), count, _stream()))
+        finally:
+            _wipe([sd] if own else [])
+        self.u = u if self.P else u[0]
+
+    def _round(self, fn, a0, a1, seeds, ref):
+        par = self.params
+        ctx = par.context_at_level(0)
+        Lm = ctx.nmoduli
+        st = _Staging(par, ref)
+        try:
+            sd = st.seeds(seeds, self.P or 1)
+            shape = ((self.P,) if self.P else ()) + (Lm, Lm, par.degree)
+            h0, h1 = st.out(shape), st.out(shape)
+            ins = [_dptr(st.dev(a)) for a in ((a0,) if a1 is None else (a0, a1))]
+            check(fn(ctx._h, par.variance, _dptr(self.sk.s_ntt), _dptr(self.u), self.shared, *ins, _dptr8(sd), _dptr(h0),
+                     _dptr(h1), self.P or 1, _stream()))
+            return RelinKeyShare(par, st.give(h0), st.give(h1), self.P is not None)
+        finally:
+            st.done()
+
+    def round_1(self, seeds=None):
+        """RelinKeyShare<R1>::new (relin_key_gen.rs:141-197): 2L draws of one seed per party."""
+        return self._round(_lib.lib().fhe_mbfv_rlk_round1_dev, self.crp.poly, None, seeds, self.crp.poly)
+
+    def round_2(self, r1, seeds=None):
+        """RelinKeyShare<R2>::new (relin_key_gen.rs:243-296) from the aggregated round-1 share."""
+        if r1.parties:
+            raise FheError(-1, "round 2 takes the AGGREGATED round-1 share (RelinKeyShare.aggregate_round_1)")
+        s = self._round(_lib.lib().fhe_mbfv_rlk_round2_dev, r1.h0, r1.h1, seeds, r1.h0)
+        s.last_round = r1
+        return s
+
+
+class RelinKeyShare:
+    """mbfv::RelinKeyShare (mbfv/relin_key_gen.rs:17-24): h0, h1 [L, L, N] ([P, L, L, N] for P parties)."""
+
+    def __init__(self, params, h0, h1, parties=False):
+        self.params, self.h0, self.h1, self.parties = params, h0, h1, parties
+        self.last_round = None
+
+    @staticmethod
+    def aggregate_round_1(shares):
+        """RelinKeyShare<R1Aggregated>::from_shares (relin_key_gen.rs:200-222)."""
+        first = _first_share(shares)
+        par = first.params
+        ctx = par.context_at_level(0)
+        Lm = ctx.nmoduli
+        st = _Staging(par, first.h0)
+        outs = []
+        for attr in ("h0", "h1"):
+            h = _stack_shares(st, shares, attr)
+            o = st.out((Lm, Lm, par.degree))
+            _mbfv_sum(ctx, h, int(h.shape[0]), Lm * Lm * par.degree, Lm, None, o)
+            outs.append(st.give(o))
+        return RelinKeyShare(par, outs[0], outs[1])
+
+    @staticmethod
+    def aggregate(shares):
+        """RelinearizationKey::from_shares (relin_key_gen.rs:299-351) of round-2 shares: the collective
+        `RelinearizationKey` at level 0 (fhe_mbfv_relin_key_aggregate_dev)."""
+        first = _first_share(shares)
+        if first.last_round is None:
+            raise FheError(-1, "MissingRelinearizationRoundOneShare")
+        par = first.params
+        ctx = par.context_at_level(0)
+        Lm = ctx.nmoduli
+        st = _Staging(par, first.h0)
+        h0, h1 = _stack_shares(st, shares, "h0"), _stack_shares(st, shares, "h1")
+        r1 = st.dev(first.last_round.h1)
+        h = C.c_void_p()
+        check(_lib.lib().fhe_mbfv_relin_key_aggregate_dev(ctx._h, _dptr(h0), _dptr(h1), int(h0.shape[0]),
+                                                          Lm * Lm * par.degree, _dptr(r1), _stream(), C.byref(h)))
+        return RelinearizationKey(KeySwitchingKey._adopt(ctx, ctx, h.value, None, 0))

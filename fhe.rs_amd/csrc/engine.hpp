@@ -3061,6 +3061,187 @@ inline void galois_from(const Ctx &ct, const Ctx &kc, const u64 *s_ntt, const si
     if (t) switch_up_ntt(ct, kc, t->u(), out, nkeys, s);
 }
 
+// ------------------------------------------------------------------ multiparty BFV ----
+// The shares of F/mbfv/ (kernels_mbfv.hpp).  One part of a call: the form, the operands (e, edraws filled in by
+// mbfv_shares) and out [batch][k][L][N].
+struct MbfvPart {
+    int form;
+    k::MbfvArgs g;
+    u64 *out;
+};
+
+// `edraws` consecutive Poly::small draws of ChaCha8Rng::from_seed(seeds[b]) per item, then every part's launch over the
+// draws [e0, e0 + k) of each item.  The samples and their transforms are secrets: cleared before their blocks return
+// to the pool.
+inline void mbfv_shares(const Ctx &c, size_t variance, const uint8_t *seeds, size_t edraws, std::vector<MbfvPart> parts,
+                        size_t batch, hipStream_t s) {
+    c.need_device();
+    check_variance(variance);
+    if (!batch) return;
+    require(batch * edraws * c.L <= 0x7fffffffu, E_ARG, "mbfv: batch exceeds the grid limit");
+    const bool whole = c.logn <= 14;
+    const bool f64_on = !f64_disabled();   // (read once per call: every transform of the call takes the same kind)
+    const int hr = c.f64_rows(0, c.L, f64_on);
+    const u64 PL = (u64)c.L * c.n;
+    const size_t group = whole ? encrypt_group(c, 1, batch, ~(size_t)0 >> 1) : encrypt_group(c, edraws, batch, (size_t)256 << 20);
+    for (size_t b0 = 0; b0 < batch; b0 += group) {
+        const size_t nb = std::min(group, batch - b0);
+        WsGuard smp(small_bytes(nb * edraws * c.n), s, true);
+        int8_t *sp = (int8_t *)smp.p;
+        cbd_sample(seeds + b0 * 32, variance, c.logn, edraws, sp, nb, s);
+        std::unique_ptr<WsGuard> x;   // rows larger than one LDS tile: lift, launch_ntt, then the epilogues as passes
+        if (!whole) {
+            x = std::make_unique<WsGuard>(nb * edraws * PL * sizeof(u64), s, true);
+            small_lift(c, sp, x->u(), nb * edraws, true, s);
+        }
+        for (const MbfvPart &pt : parts) {
+            k::MbfvArgs g = pt.g;
+            g.e = sp;
+            g.edraws = (uint32_t)edraws;
+            g.rows = (uint32_t)c.L;
+            g.A += b0 * g.a_stride;
+            g.X += b0 * g.s_stride;
+            if (g.X2) g.X2 += b0 * g.s_stride;
+            if (g.Y) g.Y += b0 * g.s_stride;
+            u64 *outb = pt.out + b0 * g.k * PL;
+            if (whole) {
+                with_tile(c.logn, ENC_TILE, c.below_2p60(0, c.L), hr, [&](auto lm, auto nrw, auto h) {
+                    with_int<0, 2>((size_t)pt.form, "unknown share form", [&](auto form) {
+                        launch_tile<k::mbfv_share_kernel<decltype(lm)::value, decltype(nrw)::value, decltype(h)::value,
+                                                         decltype(form)::value>>(
+                            "mbfv_share", lm, nb * g.k * c.L, s, g, outb, c.dmods(), hr > 0 ? c.dtw_f() : c.dtw());
+                    });
+                });
+                continue;
+            }
+            const u64 total = (u64)nb * g.k * PL;
+            FHE_LAUNCH("mbfv_share", k::mbfv_share_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
+                       (const u64 *)x->u(), g, (uint32_t)pt.form, outb, c.dmods(), (uint32_t)c.logn, total);
+        }
+    }
+}
+
+// words between the secrets of consecutive items: none when one party serves the batch, else a level-0 secret (the
+// first L rows of each are read, as key generation reads them)
+inline u64 mbfv_secret_stride(const Ctx &c, bool s_shared) { return s_shared ? 0 : (u64)c.root->L * c.n; }
+
+inline k::MbfvArgs mbfv_args(const u64 *A, u64 a_stride, const u64 *X, const u64 *X2, const u64 *Y, const u64 *w,
+                             u64 s_stride, size_t e0, size_t kd, bool neg) {
+    return k::MbfvArgs{nullptr, A, X, X2, Y, w, a_stride, s_stride, 0u, (uint32_t)e0, (uint32_t)kd, 0u, neg ? 1u : 0u};
+}
+
+// PublicKeyShare::new (F/mbfv/public_key_gen.rs:32-57): out[b] = e_b - crp (.) s_b.  crp [L][N]; s [L][N] shared or
+// a level-0 secret per item; one draw per item.
+inline void mbfv_pk_share(const Ctx &c, size_t variance, const u64 *crp, const u64 *s_ntt, bool s_shared,
+                          const uint8_t *seeds, u64 *out, size_t batch, hipStream_t s) {
+    mbfv_shares(c, variance, seeds, 1,
+                {{k::MBFV_AX, mbfv_args(crp, 0, s_ntt, nullptr, nullptr, nullptr, mbfv_secret_stride(c, s_shared), 0, 1, true),
+                  out}},
+                batch, s);
+}
+
+// SecretKeySwitchShare::new (F/mbfv/secret_key_switch.rs:38-95): out[b] = e_b + c1_b (.) (s_in - s_out); s_out null:
+// DecryptionShare::new (:133-142), the zero output key, with no zero key built.  c1 at c1_stride words per item.
+inline void mbfv_sks_share(const Ctx &c, size_t variance, const u64 *s_in, const u64 *s_out, bool s_shared, const u64 *c1,
+                           u64 c1_stride, const uint8_t *seeds, u64 *out, size_t batch, hipStream_t s) {
+    mbfv_shares(c, variance, seeds, 1,
+                {{s_out ? k::MBFV_AXX : k::MBFV_AX,
+                  mbfv_args(c1, c1_stride, s_in, s_out, nullptr, nullptr, mbfv_secret_stride(c, s_shared), 0, 1, false), out}},
+                batch, s);
+}
+
+// PublicKeySwitchShare::new (F/mbfv/public_key_switch.rs:33-92): h0 = pk0 (.) u + s (.) c1 + e0, h1 = pk1 (.) u + e1
+// with u, e0, e1 three consecutive draws: encrypt_pk with the addend s (.) c1, which is secret-dependent and lives in
+// scratch that is cleared before reuse.  ct [batch][2][L][N] ([2][L][N] when shared); out [batch][2][L][N].
+inline void mbfv_pks_share(const Ctx &c, size_t variance, const u64 *s_ntt, bool s_shared, const u64 *pk, const u64 *ct,
+                           bool ct_shared, const uint8_t *seeds, u64 *out, size_t batch, hipStream_t s) {
+    c.need_device();
+    check_variance(variance);
+    if (!batch) return;
+    const u64 PL = (u64)c.L * c.n, total = (u64)batch * PL;
+    WsGuard sc1(total * sizeof(u64), s, true);
+    FHE_LAUNCH("mbfv_mul", k::mbfv_mul_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s, s_ntt,
+               mbfv_secret_stride(c, s_shared), ct + PL, ct_shared ? (u64)0 : 2 * PL, sc1.u(), (uint32_t)c.L, c.dmods(),
+               (uint32_t)c.logn, total);
+    encrypt_pk(c, variance, pk, seeds, sc1.u(), false, out, batch, s);
+}
+
+// RelinKeyShare<R1>::new (F/mbfv/relin_key_gen.rs:141-197): 2L draws per item, h0_i = e_i - a_i (.) u + g_i s (draws
+// 0 ... L - 1), h1_i = e'_i + a_i (.) s (draws L ... 2L - 1); g_i = get_garner(i) mod q_r from ksk_consts_kernel.
+// crp [L][L][N]; out_h0, out_h1 [batch][L][L][N].
+inline void mbfv_rlk_round1(const Ctx &c, size_t variance, const u64 *s_ntt, const u64 *u_ntt, bool s_shared,
+                            const u64 *crp, const uint8_t *seeds, u64 *out_h0, u64 *out_h1, size_t batch, hipStream_t s) {
+    c.need_device();
+    check_variance(variance);
+    require(c.L >= 2, E_KEYSWITCH_UNSUPPORTED, "KeySwitchingNotSupported: a relinearization key needs two moduli");
+    if (!batch) return;
+    const size_t L = c.L;
+    const u64 st = mbfv_secret_stride(c, s_shared);
+    WsGuard cst((2 * L + L * L) * sizeof(u64), s);
+    k::u64x2 *rq = (k::u64x2 *)cst.p;
+    u64 *g = cst.u() + 2 * L;
+    FHE_LAUNCH("ksk_consts", k::ksk_consts_kernel, dim3(blocks_for(L * L, 64)), dim3(64), 0, s, c.dmods(), (uint32_t)L,
+               (uint32_t)L, 0u, g, rq);
+    mbfv_shares(c, variance, seeds, 2 * L,
+                {{k::MBFV_AX_WY, mbfv_args(crp, 0, u_ntt, nullptr, s_ntt, g, st, 0, L, true), out_h0},
+                 {k::MBFV_AX, mbfv_args(crp, 0, s_ntt, nullptr, nullptr, nullptr, st, L, L, false), out_h1}},
+                batch, s);
+}
+
+// RelinKeyShare<R2>::new (F/mbfv/relin_key_gen.rs:243-296): h0'_i = e_i + H0_i (.) s, h1'_i = e'_i + H1_i (.) (u - s),
+// H0, H1 [L][L][N] the aggregated round-1 shares; draws as round 1.
+inline void mbfv_rlk_round2(const Ctx &c, size_t variance, const u64 *s_ntt, const u64 *u_ntt, bool s_shared,
+                            const u64 *r1_h0, const u64 *r1_h1, const uint8_t *seeds, u64 *out_h0, u64 *out_h1,
+                            size_t batch, hipStream_t s) {
+    c.need_device();
+    check_variance(variance);
+    require(c.L >= 2, E_KEYSWITCH_UNSUPPORTED, "KeySwitchingNotSupported: a relinearization key needs two moduli");
+    if (!batch) return;
+    const size_t L = c.L;
+    const u64 st = mbfv_secret_stride(c, s_shared);
+    mbfv_shares(c, variance, seeds, 2 * L,
+                {{k::MBFV_AX, mbfv_args(r1_h0, 0, s_ntt, nullptr, nullptr, nullptr, st, 0, L, false), out_h0},
+                 {k::MBFV_AXX, mbfv_args(r1_h1, 0, u_ntt, s_ntt, nullptr, nullptr, st, L, L, false), out_h1}},
+                batch, s);
+}
+
+// Aggregate::from_shares: out[j] = base[j] + sum_p shares[p][j] over npolys polynomials [L][N]; polynomial j of base at
+// j base_stride words.  Strides are even and the buffers 16-byte aligned (the kernel moves two words at a time).
+inline void mbfv_sum(const Ctx &c, const u64 *shares, size_t nshares, u64 share_stride, size_t npolys, const u64 *base,
+                     u64 base_stride, u64 *out, hipStream_t s) {
+    c.need_device();
+    require(nshares >= 1, E_ARG, "NoShares: an aggregation needs at least one share");
+    require(nshares <= 0xffffffffu && (share_stride & 1) == 0 && (base_stride & 1) == 0, E_ARG,
+            "mbfv: share strides must be even");
+    require(((uintptr_t)shares | (uintptr_t)base | (uintptr_t)out) % 16 == 0, E_ARG, "mbfv: buffers must be 16-byte aligned");
+    if (!npolys) return;
+    const u64 PL = (u64)c.L * c.n;
+    require(PL / 2 <= 0x7fffffffu, E_ARG, "mbfv: polynomial exceeds the grid limit");
+    for (size_t j0 = 0; j0 < npolys; j0 += 65535) {   // (the polynomial is the grid's second dimension)
+        const size_t nj = std::min<size_t>(65535, npolys - j0);
+        FHE_LAUNCH("mbfv_sum", k::mbfv_sum_kernel, dim3(blocks_for(PL / 2, EW_THREADS), (unsigned)nj), dim3(EW_THREADS), 0, s,
+                   shares + j0 * PL, (uint32_t)nshares, share_stride, base ? base + j0 * base_stride : nullptr, base_stride,
+                   out + j0 * PL, c.dmods(), (uint32_t)c.logn, (uint32_t)(PL / 2));
+    }
+}
+
+// Plaintext::from_shares (F/mbfv/secret_key_switch.rs:145-186): c0 + the sum of the decryption shares in one launch,
+// then the inverse transform, the scale and the tail of decrypt().  ct [batch][2][L][N]; shares [nshares] x
+// [batch][L][N] at share_stride words; out [batch][N] in [0, t).
+inline void mbfv_decrypt(const Scaler &sc, u64 t, const u64 *ct, const u64 *shares, size_t nshares, u64 share_stride,
+                         u64 *out, size_t batch, hipStream_t s) {
+    const Ctx &cc = *sc.from;
+    cc.need_device();
+    require(nshares >= 1, E_ARG, "NoShares: an aggregation needs at least one share");
+    check_plain_context(sc);
+    if (!batch) return;
+    const u64 PL = (u64)cc.L * cc.n;
+    WsGuard ph(batch * PL * sizeof(u64), s, true);   // the phase: cleared before the block goes back to the pool
+    mbfv_sum(cc, shares, nshares, share_stride, batch, ct, 2 * PL, ph.u(), s);
+    launch_ntt(cc, true, ph.u(), ph.u(), full_map(cc, cc.L), batch, s);
+    decrypt_tail(sc, t, ph.u(), out, batch, s);
+}
+
 // `&Ciphertext + &Plaintext` / `-` (F/bfv/ops/mod.rs:71-108, 166-203): c0 +- to_poly(pt), the other parts unchanged.
 // ct, out [batch][nparts][L][N]; pt [batch][L][N] Delta-scaled (pt_shared: [L][N]); out == ct allowed.
 inline void add_plain(const Ctx &c, bool subtract, size_t nparts, const u64 *ct, const u64 *pt, bool pt_shared, u64 *out,

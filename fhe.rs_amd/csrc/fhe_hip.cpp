@@ -1860,6 +1860,159 @@ fhe_status fhe_ksk_export_dev(const fhe_ksk *ksk, uint64_t *c0, uint64_t *c1, ui
     });
 }
 
+// --------------------------------------------------------------------- multiparty BFV ----
+// Device-pointer forms only, like encryption.  Each checks its handle, the device and the variance before it looks at a
+// buffer; batch == 0 is a no-op.
+static const Ctx &mbfv_ctx(const fhe_ctx *ctx, size_t variance) {
+    need(ctx, "ctx");
+    const Ctx &c = *ctx->c;
+    c.need_device();
+    check_variance(variance);
+    return c;
+}
+static void mbfv_need_rlk(const Ctx &c) {
+    require(c.L >= 2, E_KEYSWITCH_UNSUPPORTED, "KeySwitchingNotSupported: a relinearization key needs two moduli");
+}
+fhe_status fhe_mbfv_pk_share_dev(const fhe_ctx *ctx, size_t variance, const uint64_t *crp, const uint64_t *s_ntt,
+                                 int s_shared, const uint8_t *seeds, uint64_t *out, size_t batch, void *stream) {
+    return guard([&] {
+        const Ctx &c = mbfv_ctx(ctx, variance);
+        if (!batch) return;
+        need(crp, "crp");
+        need(s_ntt, "s_ntt");
+        need(seeds, "seeds");
+        need(out, "out");
+        set_device(c);
+        mbfv_pk_share(c, variance, crp, s_ntt, s_shared != 0, seeds, out, batch, as_stream(stream));
+    });
+}
+fhe_status fhe_mbfv_sks_share_dev(const fhe_ctx *ctx, size_t variance, const uint64_t *s_in_ntt,
+                                  const uint64_t *s_out_ntt_or_null, int s_shared, const uint64_t *c1, size_t c1_stride,
+                                  const uint8_t *seeds, uint64_t *out, size_t batch, void *stream) {
+    return guard([&] {
+        const Ctx &c = mbfv_ctx(ctx, variance);
+        if (!batch) return;
+        need(s_in_ntt, "s_in_ntt");
+        need(c1, "c1");
+        need(seeds, "seeds");
+        need(out, "out");
+        set_device(c);
+        mbfv_sks_share(c, variance, s_in_ntt, s_out_ntt_or_null, s_shared != 0, c1, (u64)c1_stride, seeds, out, batch,
+                       as_stream(stream));
+    });
+}
+fhe_status fhe_mbfv_pks_share_dev(const fhe_ctx *ctx, size_t variance, const uint64_t *s_ntt, int s_shared,
+                                  const uint64_t *pk, const uint64_t *ct, int ct_shared, const uint8_t *seeds,
+                                  uint64_t *out, size_t batch, void *stream) {
+    return guard([&] {
+        const Ctx &c = mbfv_ctx(ctx, variance);
+        if (!batch) return;
+        need(s_ntt, "s_ntt");
+        need(pk, "pk");
+        need(ct, "ct");
+        need(seeds, "seeds");
+        need(out, "out");
+        set_device(c);
+        mbfv_pks_share(c, variance, s_ntt, s_shared != 0, pk, ct, ct_shared != 0, seeds, out, batch, as_stream(stream));
+    });
+}
+fhe_status fhe_mbfv_rlk_round1_dev(const fhe_ctx *ctx, size_t variance, const uint64_t *s_ntt, const uint64_t *u_ntt,
+                                   int s_shared, const uint64_t *crp, const uint8_t *seeds, uint64_t *out_h0,
+                                   uint64_t *out_h1, size_t batch, void *stream) {
+    return guard([&] {
+        const Ctx &c = mbfv_ctx(ctx, variance);
+        mbfv_need_rlk(c);
+        if (!batch) return;
+        need(s_ntt, "s_ntt");
+        need(u_ntt, "u_ntt");
+        need(crp, "crp");
+        need(seeds, "seeds");
+        need(out_h0, "out_h0");
+        need(out_h1, "out_h1");
+        set_device(c);
+        mbfv_rlk_round1(c, variance, s_ntt, u_ntt, s_shared != 0, crp, seeds, out_h0, out_h1, batch, as_stream(stream));
+    });
+}
+fhe_status fhe_mbfv_rlk_round2_dev(const fhe_ctx *ctx, size_t variance, const uint64_t *s_ntt, const uint64_t *u_ntt,
+                                   int s_shared, const uint64_t *r1_h0, const uint64_t *r1_h1, const uint8_t *seeds,
+                                   uint64_t *out_h0, uint64_t *out_h1, size_t batch, void *stream) {
+    return guard([&] {
+        const Ctx &c = mbfv_ctx(ctx, variance);
+        mbfv_need_rlk(c);
+        if (!batch) return;
+        need(s_ntt, "s_ntt");
+        need(u_ntt, "u_ntt");
+        need(r1_h0, "r1_h0");
+        need(r1_h1, "r1_h1");
+        need(seeds, "seeds");
+        need(out_h0, "out_h0");
+        need(out_h1, "out_h1");
+        set_device(c);
+        mbfv_rlk_round2(c, variance, s_ntt, u_ntt, s_shared != 0, r1_h0, r1_h1, seeds, out_h0, out_h1, batch,
+                        as_stream(stream));
+    });
+}
+fhe_status fhe_mbfv_aggregate_dev(const fhe_ctx *ctx, const uint64_t *shares, size_t nshares, size_t share_stride,
+                                  size_t npolys, const uint64_t *base_or_null, uint64_t *out, void *stream) {
+    return guard([&] {
+        need(ctx, "ctx");
+        const Ctx &c = *ctx->c;
+        c.need_device();
+        require(nshares >= 1, E_ARG, "NoShares: an aggregation needs at least one share");
+        if (!npolys) return;
+        need(shares, "shares");
+        need(out, "out");
+        set_device(c);
+        mbfv_sum(c, shares, nshares, (u64)share_stride, npolys, base_or_null, (u64)c.L * c.n, out, as_stream(stream));
+    });
+}
+fhe_status fhe_mbfv_relin_key_aggregate_dev(const fhe_ctx *ctx, const uint64_t *r2_h0, const uint64_t *r2_h1,
+                                            size_t nshares, size_t share_stride, const uint64_t *r1_h1, void *stream,
+                                            fhe_ksk **out) {
+    return guard([&] {
+        need(ctx, "ctx");
+        need(out, "out");
+        *out = nullptr;
+        const Ctx &c = *ctx->c;
+        c.need_device();
+        mbfv_need_rlk(c);
+        require(nshares >= 1, E_ARG, "NoShares: an aggregation needs at least one share");
+        need(r2_h0, "r2_h0");
+        need(r2_h1, "r2_h1");
+        need(r1_h1, "r1_h1");
+        set_device(c);
+        hipStream_t s = as_stream(stream);
+        const size_t L = c.L, count = L * L * c.n;
+        auto h = ksk_new(ctx, ctx, L, r2_h0, r1_h1, 0, out);
+        std::vector<u64> h0(count), h1(count);
+        {
+            WsGuard c0(count * sizeof(u64), s);
+            mbfv_sum(c, r2_h0, nshares, (u64)share_stride, L, nullptr, 0, c0.u(), s);
+            mbfv_sum(c, r2_h1, nshares, (u64)share_stride, L, c0.u(), (u64)L * c.n, c0.u(), s);
+            // the key words come down once and take the host path, as in fhe_ksk_create_dev
+            FHE_HIP_CHECK(hipStreamSynchronize(s));
+            FHE_HIP_CHECK(hipMemcpy(h0.data(), c0.p, count * sizeof(u64), hipMemcpyDeviceToHost));
+            FHE_HIP_CHECK(hipMemcpy(h1.data(), r1_h1, count * sizeof(u64), hipMemcpyDeviceToHost));
+        }
+        ksk_upload(*h->k, h0.data(), nullptr, h1.data(), nullptr);
+        *out = h.release();
+    });
+}
+fhe_status fhe_mbfv_decrypt_dev(const fhe_scaler *sc, uint64_t t, const uint64_t *ct, const uint64_t *shares,
+                                size_t nshares, size_t share_stride, uint64_t *out, size_t batch, void *stream) {
+    return guard([&] {
+        need(sc, "cipher_plain_scaler");
+        sc->s->from->need_device();
+        require(nshares >= 1, E_ARG, "NoShares: an aggregation needs at least one share");
+        if (!batch) return;
+        need(ct, "ct");
+        need(shares, "shares");
+        need(out, "out");
+        set_device(*sc->s->from);
+        mbfv_decrypt(*sc->s, t, ct, shares, nshares, (u64)share_stride, out, batch, as_stream(stream));
+    });
+}
+
 // --------------------------------------------------------------------------- primes ----
 uint64_t fhe_generate_prime(size_t num_bits, uint64_t modulo, uint64_t upper_bound) {
     return generate_prime(num_bits, modulo, upper_bound);

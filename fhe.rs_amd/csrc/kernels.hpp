@@ -31,6 +31,7 @@
 //   ksk_seeds_kernel, cbd_sample_at_kernel, ksk_consts_kernel, ksk_gen_kernel, galois_from_kernel   KeySwitchingKey::new,
 //                           RelinearizationKey / GaloisKey::new   F/bfv/keys/key_switching_key.rs:71-236, galois_key.rs:26-58
 //   lift_kernel, noise_max_kernel       RnsContext::lift, SecretKey::measure_noise   M/rns/mod.rs:138-143, F/bfv/keys/secret_key.rs:55-98
+//   mbfv_share_kernel, mbfv_sum_kernel  the shares of the multiparty protocols and their aggregation   F/mbfv/*.rs
 // Compile-time knobs live in knobs.hpp (pinned in the release build); rejected kernel variants in tools/lab/ (lab builds only).
 #pragma once
 #include "kernels_common.hpp"
@@ -43,6 +44,7 @@
 #include "kernels_encrypt.hpp"
 #include "kernels_keygen.hpp"
 #include "kernels_noise.hpp"
+#include "kernels_mbfv.hpp"
 
 namespace fhe {
 namespace k {

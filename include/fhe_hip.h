@@ -604,6 +604,81 @@ fhe_status fhe_bfv_measure_noise_dev(const fhe_encoder *enc, const fhe_scaler *c
                                      const uint64_t *ct, size_t nparts, const uint64_t *m_or_null, uint64_t *noise_bits,
                                      size_t batch, void *stream);
 
+/* --------------------------------------------------------- multiparty BFV ---- */
+/* The threshold protocols of eprint 2020/304 (crates/fhe/src/mbfv/): a party's shares and the aggregator's sums.
+ * Device-pointer forms only, with no host-pointer twin: secret shares and errors are never staged through host memory
+ * by the engine.  The common random polynomial (CRP) is an input, as Ntt words (the reference draws it with
+ * Poly::random; fhe_poly_from_seed_dev makes one from a seed).
+ *
+ * Draws: every share takes its errors from ChaCha8Rng::from_seed(seeds[b]) as consecutive Poly::small draws, draw j
+ * starting at u64 word j wpd -- the layout of fhe_bfv_sample_small_dev, PARITY UNPINNED like it.  Each entry point
+ * states its draw order.  variance outside [1, 32] -> FHE_E_INVALID_VARIANCE; batch == 0 is a no-op (NULL buffers
+ * allowed); a NULL handle or buffer -> FHE_E_ARG; a host-only context -> FHE_E_NO_DEVICE.
+ *
+ * Secrets: s_ntt (and u_ntt) are a party's secret in Ntt form, as fhe_bfv_sample_small_dev(to_ntt = 1) writes it over
+ * the level-0 context; over a deeper ctx its first L rows are read.  s_shared != 0: one secret [L][N] serves the whole
+ * batch; s_shared == 0: one party per item, [batch][L0][N] level-0 secrets (L0 rows each, the moduli count of level 0).
+ * Secret hygiene: the engine's scratch that holds samples, their transforms or a product with a secret is cleared on the
+ * stream before it returns to the pool; the caller's buffers are the caller's to clear.  No branch or address of the
+ * kernels depends on a sample or a secret word.  Outputs are canonical Ntt words. */
+/* PublicKeyShare::new (mbfv/public_key_gen.rs:32-57): out[b] = e - crp (.) s.  Draws: e.  crp [L][N] over ctx (level
+ * 0); out [batch][L][N]. */
+fhe_status fhe_mbfv_pk_share_dev(const fhe_ctx *ctx, size_t variance, const uint64_t *crp, const uint64_t *s_ntt,
+                                 int s_shared, const uint8_t *seeds, uint64_t *out, size_t batch, void *stream);
+/* SecretKeySwitchShare::new (mbfv/secret_key_switch.rs:38-95): out[b] = e + c1[b] (.) (s_in - s_out).  Draws: e.
+ * s_out_ntt_or_null == NULL is DecryptionShare::new (:133-142): the zero output key, e + c1 (.) s_in, with no zero key
+ * built.  ctx is the ciphertext's level.  c1: the ciphertexts' second parts, item b at c1 + b c1_stride words (2 L N
+ * for a [batch][2][L][N] buffer passed at its part 1; 0: one ciphertext for the batch); out [batch][L][N]. */
+fhe_status fhe_mbfv_sks_share_dev(const fhe_ctx *ctx, size_t variance, const uint64_t *s_in_ntt,
+                                  const uint64_t *s_out_ntt_or_null, int s_shared, const uint64_t *c1, size_t c1_stride,
+                                  const uint8_t *seeds, uint64_t *out, size_t batch, void *stream);
+/* PublicKeySwitchShare::new (mbfv/public_key_switch.rs:33-92): out[b][0] = pk[0] (.) u + s (.) ct[b][1] + e0,
+ * out[b][1] = pk[1] (.) u + e1.  Draws: u, e0, e1 -- fhe_bfv_encrypt_pk_dev with the addend s (.) c1, which lives in
+ * engine scratch that is cleared before reuse.  pk [2][L][N] must already be at the ciphertext's level (ctx), as for
+ * fhe_bfv_encrypt_pk_dev; ct [batch][2][L][N] ([2][L][N] when ct_shared != 0); out [batch][2][L][N]. */
+fhe_status fhe_mbfv_pks_share_dev(const fhe_ctx *ctx, size_t variance, const uint64_t *s_ntt, int s_shared,
+                                  const uint64_t *pk, const uint64_t *ct, int ct_shared, const uint8_t *seeds,
+                                  uint64_t *out, size_t batch, void *stream);
+/* RelinKeyShare<R1>::new (mbfv/relin_key_gen.rs:141-197) over the level-0 context: out_h0[b][i] = e_i - crp[i] (.) u +
+ * g_i s, out_h1[b][i] = e'_i + crp[i] (.) s, g_i = RnsContext(moduli).get_garner(i) mod q_r.  Draws: e_0 ... e_{L-1},
+ * then e'_0 ... e'_{L-1}.  u_ntt is the party's RelinKeyGenerator::new draw (:92), a fhe_bfv_sample_small_dev(to_ntt =
+ * 1) output laid out like s_ntt.  crp [L][L][N]; out_h0, out_h1 [batch][L][L][N].  A single-modulus context ->
+ * FHE_E_KEYSWITCH_UNSUPPORTED. */
+fhe_status fhe_mbfv_rlk_round1_dev(const fhe_ctx *ctx, size_t variance, const uint64_t *s_ntt, const uint64_t *u_ntt,
+                                   int s_shared, const uint64_t *crp, const uint8_t *seeds, uint64_t *out_h0,
+                                   uint64_t *out_h1, size_t batch, void *stream);
+/* RelinKeyShare<R2>::new (mbfv/relin_key_gen.rs:243-296): out_h0[b][i] = e_i + r1_h0[i] (.) s, out_h1[b][i] = e'_i +
+ * r1_h1[i] (.) (u - s).  Draws: as round 1.  r1_h0, r1_h1 [L][L][N]: the aggregated round-1 shares
+ * (fhe_mbfv_aggregate_dev of every party's out_h0 / out_h1).  A single-modulus context -> FHE_E_KEYSWITCH_UNSUPPORTED. */
+fhe_status fhe_mbfv_rlk_round2_dev(const fhe_ctx *ctx, size_t variance, const uint64_t *s_ntt, const uint64_t *u_ntt,
+                                   int s_shared, const uint64_t *r1_h0, const uint64_t *r1_h1, const uint8_t *seeds,
+                                   uint64_t *out_h0, uint64_t *out_h1, size_t batch, void *stream);
+/* Aggregate::from_shares: out[j] = (base_or_null ? base[j] : 0) + sum_{p < nshares} shares[p share_stride + j] over
+ * npolys polynomials [L][N] of canonical words (moduli below 2^62); share_stride in words.  nshares == 0 -> FHE_E_ARG (the
+ * reference's NoShares).  out == base_or_null is allowed.  Buffers are 16-byte aligned and share_stride is even.  No
+ * draws, no secrets.  With npolys = 1 and no base this is PublicKey::from_shares' part 0 (public_key_gen.rs:60-77; part 1
+ * is the CRP, copied by the caller); with base = the ciphertexts' c0 it is Ciphertext::from_shares of both switch
+ * protocols (secret_key_switch.rs:98-115, public_key_switch.rs:95-113); with npolys = L it is
+ * RelinKeyShare<R1Aggregated>::from_shares (relin_key_gen.rs:200-222). */
+fhe_status fhe_mbfv_aggregate_dev(const fhe_ctx *ctx, const uint64_t *shares, size_t nshares, size_t share_stride,
+                                  size_t npolys, const uint64_t *base_or_null, uint64_t *out, void *stream);
+/* RelinearizationKey::from_shares (mbfv/relin_key_gen.rs:299-351): c0[i] = sum_p r2_h0[p][i] + sum_p r2_h1[p][i],
+ * c1[i] = r1_h1[i] (the aggregated round-1 h1), log_base 0, ciphertext and key level 0 (ctx).  r2_h0, r2_h1: nshares
+ * arrays [L][L][N] at share_stride words; r1_h1 [L][L][N].  The handle is made as fhe_ksk_create_dev makes it (the
+ * public key words come down once for the checks and Shoup twins; the call waits for `stream`).  nshares == 0 ->
+ * FHE_E_ARG; a single-modulus context -> FHE_E_KEYSWITCH_UNSUPPORTED.  No draws, no secrets. */
+fhe_status fhe_mbfv_relin_key_aggregate_dev(const fhe_ctx *ctx, const uint64_t *r2_h0, const uint64_t *r2_h1,
+                                            size_t nshares, size_t share_stride, const uint64_t *r1_h1, void *stream,
+                                            fhe_ksk **out);
+/* Plaintext::from_shares (mbfv/secret_key_switch.rs:145-186): ct[b][0] + the sum of the decryption shares, then the
+ * inverse transform, Scaler::scale and ((d_0 + t) mod q_0) mod t exactly as fhe_bfv_decrypt_dev after its phase.
+ * cipher_plain_scaler as fhe_bfv_decrypt_dev; ct [batch][2][L][N] Ntt; shares: nshares arrays [batch][L][N] at
+ * share_stride words; out [batch][N] coefficients in [0, t).  nshares == 0 -> FHE_E_ARG.  No draws.  The summed phase
+ * and the scaled plaintext live in engine scratch that is cleared before reuse; `out` is the caller's to clear. */
+fhe_status fhe_mbfv_decrypt_dev(const fhe_scaler *cipher_plain_scaler, uint64_t plaintext_modulus, const uint64_t *ct,
+                                const uint64_t *shares, size_t nshares, size_t share_stride, uint64_t *out, size_t batch,
+                                void *stream);
+
 /* ------------------------------------------------- zq::primes (host, no GPU) ---- */
 /* generate_prime (M/zq/primes.rs:30-59): returns 0 when none exists. */
 uint64_t fhe_generate_prime(size_t num_bits, uint64_t modulo, uint64_t upper_bound);

@@ -1123,6 +1123,187 @@ impl CtxView<'_> {
     }
 }
 
+/// The secret operand of a multiparty share call: one party's level-0 secret serving the whole batch (its first L rows
+/// are read), or one level-0 secret of `level0_rows` rows per item -- many parties in one call.
+pub enum PartySecrets<'a> {
+    Shared(&'a DeviceBuffer),
+    PerItem { secrets: &'a DeviceBuffer, level0_rows: usize },
+}
+
+/// Multiparty BFV over one level's context (crates/fhe/src/mbfv/): a party's shares and the aggregator's sums.  Errors
+/// are `Poly::small` draws of `ChaCha8Rng::from_seed(seeds[b])`; the engine clears its own scratch of samples and of
+/// products with a secret, the secrets and the shares are the caller's to clear.
+impl CtxView<'_> {
+    /// (pointer, shared) of a call's secrets after checking their length for `batch` items.
+    fn party_secrets(&self, what: &str, s: &PartySecrets<'_>, batch: usize) -> Result<(*const u64, bool)> {
+        match s {
+            PartySecrets::Shared(b) => {
+                if b.len() < self.poly_words() {
+                    return Err(shape_error(&format!("{what}: the secret is shorter than one polynomial over this context")));
+                }
+                Ok((b.as_ptr(), true))
+            }
+            PartySecrets::PerItem { secrets, level0_rows } => {
+                if *level0_rows < self.nmoduli() {
+                    return Err(shape_error(&format!("{what}: a level-0 secret has at least this context's rows")));
+                }
+                expect_len(what, secrets.len(), batch * level0_rows * self.degree())?;
+                Ok((secrets.as_ptr(), false))
+            }
+        }
+    }
+    /// `PublicKeyShare::new` (mbfv/public_key_gen.rs:32-57): e - crp s per seed -> `[batch][L][N]`.  `crp` `[L][N]`.
+    pub fn mbfv_pk_share_dev(&self, variance: usize, crp: &DeviceBuffer, s: &PartySecrets<'_>, seeds: &DeviceSeeds,
+                             stream: &Stream) -> Result<DeviceBuffer> {
+        expect_len("mbfv_pk_share_dev crp", crp.len(), self.poly_words())?;
+        let (sp, shared) = self.party_secrets("mbfv_pk_share_dev secrets", s, seeds.batch)?;
+        let out = DeviceBuffer::alloc_on(self.device(), (seeds.batch * self.poly_words()).max(1), stream)?;
+        check(unsafe {
+            ffi::fhe_mbfv_pk_share_dev(self.ptr, variance, crp.as_ptr(), sp, shared as c_int, seeds.as_ptr(), out.as_mut_ptr(),
+                                       seeds.batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+    /// `SecretKeySwitchShare::new` (mbfv/secret_key_switch.rs:38-95): e + c1 (s_in - s_out) for every ciphertext of
+    /// `ct` (one: shared by the batch of parties) -> `[batch][L][N]`; `s_out` `None` is `DecryptionShare::new`
+    /// (:133-142).  `s_out` takes the form of `s_in`.
+    pub fn mbfv_sks_share_dev(&self, variance: usize, s_in: &PartySecrets<'_>, s_out: Option<&DeviceBuffer>,
+                              ct: &DeviceCiphertexts, seeds: &DeviceSeeds, stream: &Stream) -> Result<DeviceBuffer> {
+        if ct.parts != 2 || ct.rows != self.nmoduli() || ct.degree != self.degree() || (ct.batch != 1 && ct.batch != seeds.batch) {
+            return Err(shape_error("mbfv_sks_share_dev: two-part ciphertexts over this context, one or one per seed"));
+        }
+        let (sp, shared) = self.party_secrets("mbfv_sks_share_dev secrets", s_in, seeds.batch)?;
+        let so = match (s_out, s_in) {
+            (None, _) => ptr::null(),
+            (Some(o), PartySecrets::Shared(i)) => { expect_len("mbfv_sks_share_dev output secret", o.len(), i.len())?; o.as_ptr() }
+            (Some(o), PartySecrets::PerItem { secrets, .. }) => {
+                expect_len("mbfv_sks_share_dev output secrets", o.len(), secrets.len())?;
+                o.as_ptr()
+            }
+        };
+        let stride = if ct.batch == 1 { 0 } else { ct.words_per_ct() };
+        let out = DeviceBuffer::alloc_on(self.device(), (seeds.batch * self.poly_words()).max(1), stream)?;
+        check(unsafe {
+            ffi::fhe_mbfv_sks_share_dev(self.ptr, variance, sp, so, shared as c_int, ct.buf.as_ptr().add(self.poly_words()),
+                                        stride, seeds.as_ptr(), out.as_mut_ptr(), seeds.batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+    /// `PublicKeySwitchShare::new` (mbfv/public_key_switch.rs:33-92): (pk0 u + s c1 + e0, pk1 u + e1) per seed, as a
+    /// batch of two-part ciphertexts.  `pk`: the output key over this context, as for `encrypt_pk_dev`.
+    pub fn mbfv_pks_share_dev(&self, variance: usize, s: &PartySecrets<'_>, pk: &DeviceCiphertexts, ct: &DeviceCiphertexts,
+                              seeds: &DeviceSeeds, stream: &Stream) -> Result<DeviceCiphertexts> {
+        for c in [pk, ct] {
+            if c.parts != 2 || c.rows != self.nmoduli() || c.degree != self.degree() {
+                return Err(shape_error("mbfv_pks_share_dev: the key and the ciphertexts have two parts over this context"));
+            }
+        }
+        if pk.batch != 1 || (ct.batch != 1 && ct.batch != seeds.batch) {
+            return Err(shape_error("mbfv_pks_share_dev: one public key; one ciphertext or one per seed"));
+        }
+        let (sp, shared) = self.party_secrets("mbfv_pks_share_dev secrets", s, seeds.batch)?;
+        let out = DeviceCiphertexts::alloc_on(self.device(), seeds.batch.max(1), 2, self.nmoduli(), self.degree(), ct.level, stream)?;
+        check(unsafe {
+            ffi::fhe_mbfv_pks_share_dev(self.ptr, variance, sp, shared as c_int, pk.buf.as_ptr(), ct.buf.as_ptr(),
+                                        (ct.batch == 1) as c_int, seeds.as_ptr(), out.buf.as_mut_ptr(), seeds.batch,
+                                        stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+    /// `RelinKeyShare<R1>::new` (round 1, mbfv/relin_key_gen.rs:141-197) or, with the aggregated round-1 shares
+    /// `r1 = Some((h0, h1))`, `RelinKeyShare<R2>::new` (:243-296) -> (h0, h1), `[batch][L][L][N]` each.  `crp`
+    /// `[L][L][N]` (round 1 only); `u`: the parties' `RelinKeyGenerator::new` draws (`sample_small_dev`, Ntt), in the
+    /// form of `s`.
+    pub fn mbfv_rlk_round_dev(&self, variance: usize, s: &PartySecrets<'_>, u: &DeviceBuffer, crp: &DeviceBuffer,
+                              r1: Option<(&DeviceBuffer, &DeviceBuffer)>, seeds: &DeviceSeeds, stream: &Stream)
+                              -> Result<(DeviceBuffer, DeviceBuffer)> {
+        let key_words = self.nmoduli() * self.poly_words();
+        expect_len("mbfv_rlk_round_dev crp", crp.len(), key_words)?;
+        let (sp, shared) = self.party_secrets("mbfv_rlk_round_dev secrets", s, seeds.batch)?;
+        match s {
+            PartySecrets::Shared(b) => expect_len("mbfv_rlk_round_dev u", u.len(), b.len())?,
+            PartySecrets::PerItem { secrets, .. } => expect_len("mbfv_rlk_round_dev u", u.len(), secrets.len())?,
+        }
+        let len = (seeds.batch * key_words).max(1);
+        let (h0, h1) = (DeviceBuffer::alloc_on(self.device(), len, stream)?, DeviceBuffer::alloc_on(self.device(), len, stream)?);
+        check(match r1 {
+            None => unsafe {
+                ffi::fhe_mbfv_rlk_round1_dev(self.ptr, variance, sp, u.as_ptr(), shared as c_int, crp.as_ptr(), seeds.as_ptr(),
+                                             h0.as_mut_ptr(), h1.as_mut_ptr(), seeds.batch, stream.as_ptr())
+            },
+            Some((a0, a1)) => {
+                expect_len("mbfv_rlk_round_dev aggregated h0", a0.len(), key_words)?;
+                expect_len("mbfv_rlk_round_dev aggregated h1", a1.len(), key_words)?;
+                unsafe {
+                    ffi::fhe_mbfv_rlk_round2_dev(self.ptr, variance, sp, u.as_ptr(), shared as c_int, a0.as_ptr(), a1.as_ptr(),
+                                                 seeds.as_ptr(), h0.as_mut_ptr(), h1.as_mut_ptr(), seeds.batch, stream.as_ptr())
+                }
+            }
+        })?;
+        Ok((h0, h1))
+    }
+    /// `Aggregate::from_shares`: `base` + the sum of `nshares` shares of `npolys` polynomials each, laid out
+    /// `[nshares][npolys][L][N]` -> `[npolys][L][N]`.  `base` (`[npolys][L][N]`, e.g. the c0 parts) is optional.
+    pub fn mbfv_aggregate_dev(&self, shares: &DeviceBuffer, nshares: usize, base: Option<&DeviceBuffer>, stream: &Stream)
+                              -> Result<DeviceBuffer> {
+        if nshares == 0 {
+            return Err(shape_error("mbfv_aggregate_dev: NoShares"));
+        }
+        let per = whole_batch("mbfv_aggregate_dev shares", shares.len(), nshares)?;
+        let npolys = whole_batch("mbfv_aggregate_dev share", per, self.poly_words())?;
+        if let Some(b) = base { expect_len("mbfv_aggregate_dev base", b.len(), per)?; }
+        let out = DeviceBuffer::alloc_on(self.device(), per.max(1), stream)?;
+        check(unsafe {
+            ffi::fhe_mbfv_aggregate_dev(self.ptr, shares.as_ptr(), nshares, per, npolys, base.map_or(ptr::null(), |b| b.as_ptr()),
+                                        out.as_mut_ptr(), stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+}
+
+impl HipScaler {
+    /// `Plaintext::from_shares` (mbfv/secret_key_switch.rs:145-186) with this cipher-to-plaintext scaler: c0 + the sum
+    /// of the `nshares` decryption shares (`[nshares][batch][L][N]`), scaled -> the coefficients mod t, `[batch][N]`.
+    pub fn mbfv_decrypt_dev(&self, plaintext_modulus: u64, ct: &DeviceCiphertexts, shares: &DeviceBuffer, nshares: usize,
+                            stream: &Stream) -> Result<DeviceBuffer> {
+        if ct.parts != 2 || ct.rows != self.from.nmoduli() || ct.degree != self.from.degree() {
+            return Err(shape_error("mbfv_decrypt_dev: two-part ciphertexts over the scaler's source context"));
+        }
+        if nshares == 0 {
+            return Err(shape_error("mbfv_decrypt_dev: NoShares"));
+        }
+        let stride = ct.batch * self.from.poly_words();
+        expect_len("mbfv_decrypt_dev shares", shares.len(), nshares * stride)?;
+        let out = DeviceBuffer::alloc_on(self.from.device(), (ct.batch * ct.degree).max(1), stream)?;
+        check(unsafe {
+            ffi::fhe_mbfv_decrypt_dev(self.ptr, plaintext_modulus, ct.buf.as_ptr(), shares.as_ptr(), nshares, stride,
+                                      out.as_mut_ptr(), ct.batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+}
+
+impl HipKsk {
+    /// `RelinearizationKey::from_shares` (mbfv/relin_key_gen.rs:299-351): the collective key of `nshares` round-2
+    /// shares (`r2_h0`, `r2_h1` `[nshares][L][L][N]`) and the aggregated round-1 `r1_h1` `[L][L][N]`, at level 0.
+    pub fn from_relin_shares_dev(ctx: &Arc<HipCtx>, r2_h0: &DeviceBuffer, r2_h1: &DeviceBuffer, nshares: usize,
+                                 r1_h1: &DeviceBuffer, stream: &Stream) -> Result<Self> {
+        let key_words = ctx.nmoduli() * ctx.poly_words();
+        if nshares == 0 {
+            return Err(shape_error("from_relin_shares_dev: NoShares"));
+        }
+        expect_len("from_relin_shares_dev h0 shares", r2_h0.len(), nshares * key_words)?;
+        expect_len("from_relin_shares_dev h1 shares", r2_h1.len(), nshares * key_words)?;
+        expect_len("from_relin_shares_dev round-1 h1", r1_h1.len(), key_words)?;
+        let mut out: *mut ffi::FheKsk = ptr::null_mut();
+        check(unsafe {
+            ffi::fhe_mbfv_relin_key_aggregate_dev(ctx.as_ptr(), r2_h0.as_ptr(), r2_h1.as_ptr(), nshares, key_words,
+                                                  r1_h1.as_ptr(), stream.as_ptr(), &mut out)
+        })?;
+        Ok(Self { ptr: out, ct_ctx: ctx.clone(), ksk_ctx: ctx.clone() })
+    }
+}
+
 /// A batch of `bfv::Ciphertext`s that stays on the GPU between operations: `[batch][parts][rows][N]` u64, Ntt form,
 /// plus the `level` bookkeeping of `Ciphertext` (ciphertext.rs:18-30).  Made by `upload` (or by an operation), consumed
 /// by `HipMul::multiply_dev`, `HipKsk::{relinearize_dev, galois_dev}`, `CtxView::ciphertexts_switch_to_level_dev`;
