@@ -168,6 +168,14 @@ SIGNATURES = {
     "fhe_mbfv_aggregate_dev": (i32, [vp, vp, sz, sz, sz, vp, vp, vp]),
     "fhe_mbfv_relin_key_aggregate_dev": (i32, [vp, vp, vp, sz, sz, vp, vp, C.POINTER(vp)]),
     "fhe_mbfv_decrypt_dev": (i32, [vp, u64, vp, vp, sz, sz, vp, sz, vp]),
+    "fhe_params_create_big": (i32, [i32, sz, sz, u64p, u64p, sz, C.POINTER(vp)]),
+    "fhe_params_create_big_with_tables": (i32, [i32, sz, sz, u64p, u64p, sz, NTT_TABLES_FN, vp, C.POINTER(vp)]),
+    "fhe_params_plaintext_limbs": (sz, [vp]),
+    "fhe_bfv_encode_big_dev": (i32, [vp, i32, i32, sz, vp, sz, vp, sz, vp]),
+    "fhe_bfv_reduce_big_dev": (i32, [vp, vp, sz, vp, sz, vp]),
+    "fhe_encoder_plain_rows": (sz, [vp]),
+    "fhe_bfv_decrypt_big_dev": (i32, [vp, vp, vp, vp, sz, vp, sz, vp]),
+    "fhe_mbfv_decrypt_big_dev": (i32, [vp, vp, vp, vp, sz, sz, vp, sz, vp]),
     "fhe_generate_prime": (u64, [sz, u64, u64]),
     "fhe_supports_opt": (i32, [u64]),
     "fhe_is_prime": (i32, [u64]),

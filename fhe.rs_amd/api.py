@@ -248,6 +248,22 @@ def _limbs(x: int):
     return np.array(out, dtype=np.uint64)
 
 
+def _to_limbs(values, wt):
+    """Python ints [...] (a list or an object array) -> uint64 [..., wt] little-endian limbs."""
+    v = np.asarray(values, dtype=object)
+    flat = [int(x) for x in v.reshape(-1)]
+    if any(x < 0 or x >> (64 * wt) for x in flat):
+        raise FheError(-1, "values must be in [0, 2^%d)" % (64 * wt))
+    out = np.array([[(x >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(wt)] for x in flat], dtype=np.uint64)
+    return out.reshape(tuple(v.shape) + (wt,))
+
+
+def _from_limbs(a):
+    """uint64 [..., wt] limbs -> an object array [...] of Python ints."""
+    a = np.asarray(a, dtype=np.uint64).astype(object)
+    return sum(a[..., k] << (64 * k) for k in range(a.shape[-1]))
+
+
 class Context:
     """rq::Context (crates/fhe-math/src/rq/context.rs:9-92)."""
 
@@ -1088,6 +1104,26 @@ class Encoder:
         L = _lib.lib()
         enc = _encoding(encoding)
         nmod = len(self._params.moduli) - level if 0 <= level < len(self._params.moduli) else 1
+        wt = self._params.plaintext_limbs
+        if wt > 1:
+            # PlaintextVec::try_encode for Vec<BigUint> (plaintext_vec.rs:105-132): Python ints [..., nvalues] (a list or
+            # an object array), or a device array of limbs [..., nvalues, W_t]
+            if not _is_dev(values):
+                values = _to_limbs(values, wt)
+            if len(values.shape) < 2 or int(values.shape[-1]) != wt:
+                raise FheError(-1, "values: expected [..., nvalues, %d] limbs" % wt)
+            lead, nvalues = tuple(int(d) for d in values.shape[:-2]), int(values.shape[-2])
+            batch = int(np.prod(lead)) if lead else 1
+            oshape = lead + (nmod, self.degree)
+            host = not _is_dev(values)
+            x = DeviceArray.from_numpy(values, max(self._params.device, 0)) if host else values
+            try:
+                out = DeviceArray(oshape, x.device) if host else _empty_dev(values, oshape)
+                check(L.fhe_bfv_encode_big_dev(self._h, enc, 1 if scaled else 0, level, _dptr(x), nvalues, _dptr(out),
+                                               batch, _stream()))
+                return out.download() if host else out
+            finally:
+                _wipe([x] if host else [])
         lead, nvalues = tuple(values.shape[:-1]), int(values.shape[-1])
         batch = int(np.prod(lead)) if lead else 1
         oshape = lead + (nmod, self.degree)
@@ -1102,11 +1138,36 @@ class Encoder:
                                    _stream()))
         return out.download()
 
+    def reduce(self, polys):
+        """The tail of SecretKey::try_decrypt's Large branch alone (secret_key.rs:238-250, fhe_bfv_reduce_big_dev):
+        PowerBasis residues over the plaintext context [..., P, N] -> ((x + t) mod Q_p) mod t of each lifted column,
+        Python ints [..., N] for numpy input and limbs [..., N, W_t] for a device array."""
+        wt = self._params.plaintext_limbs
+        rows = int(_lib.lib().fhe_encoder_plain_rows(self._h))
+        if len(polys.shape) < 2 or (int(polys.shape[-2]), int(polys.shape[-1])) != (rows, self.degree):
+            raise FheError(-1, "polys: expected [..., %d, %d] over the plaintext context" % (rows, self.degree))
+        lead = tuple(int(d) for d in polys.shape[:-2])
+        batch = int(np.prod(lead)) if lead else 1
+        host = not _is_dev(polys)
+        x = DeviceArray.from_numpy(_np(polys), max(self._params.device, 0)) if host else polys
+        oshape = lead + (self.degree, wt)
+        out = DeviceArray(oshape, x.device) if host else _empty_dev(polys, oshape)
+        try:
+            check(_lib.lib().fhe_bfv_reduce_big_dev(self._h, _dptr(x), rows, _dptr(out), batch, _stream()))
+            return _from_limbs(out.download()) if host else out
+        finally:
+            _wipe([x, out] if host else [])
+
     def decode(self, coeffs, encoding="simd"):
         """Vec<u64>::try_decode (plaintext.rs:157-170, 408-431): coefficients mod t [..., N] (what decrypt returns)
         -> values [..., N]."""
         L = _lib.lib()
         enc = _encoding(encoding)
+        if self._params.plaintext_limbs > 1:
+            # (a plaintext modulus above 64 bits has no NTT operator: Poly only, and its values are the coefficients)
+            if enc != 0:
+                raise FheError(-22, "SimdUnavailable: no NTT modulo a plaintext modulus above 64 bits")
+            return coeffs
         if int(coeffs.shape[-1]) != self.degree:
             raise FheError(-1, "coefficients: the last dimension must be the degree")
         batch = int(np.prod(coeffs.shape[:-1])) if len(coeffs.shape) > 1 else 1
@@ -1249,7 +1310,7 @@ class SecretKey:
         x = DeviceArray.from_numpy(_np(ct), max(self.params.device, 0))
         d = self.params.decrypt(self.s_ntt, x, level)
         try:
-            return _download(d)
+            return _from_limbs(_download(d)) if self.params.plaintext_limbs > 1 else _download(d)
         finally:
             _wipe([d])   # (the plaintext coefficients)
 
@@ -1271,7 +1332,11 @@ class SecretKey:
         if self._encoder is None:
             self._encoder = par.encoder()
         enc = self._encoder
-        if plaintext is not None and (tuple(int(d) for d in plaintext.shape) != lead + (par.degree,)):
+        wt = par.plaintext_limbs
+        if wt > 1 and plaintext is not None and not _is_dev(plaintext):
+            plaintext = _to_limbs(plaintext, wt)   # (Python ints [..., N] -> limbs [..., N, W_t])
+        want = lead + ((par.degree,) if wt == 1 else (par.degree, wt))
+        if plaintext is not None and (tuple(int(d) for d in plaintext.shape) != want):
             raise FheError(-1, "plaintext: expected one [N] row of coefficients per ciphertext")
         host = not _is_dev(ct)
         staged = []
@@ -1406,8 +1471,17 @@ class BfvParameters:
             moduli = [int(x) for x in out]
         m = _np(moduli)
         h = C.c_void_p()
-        if tables_fn is None:
+        plaintext_modulus = int(plaintext_modulus)
+        big = plaintext_modulus >> 64 != 0   # PlaintextModulus::Large: the limbs go through the _big constructors
+        tl = _limbs(plaintext_modulus)
+        if tables_fn is None and big:
+            check(L.fhe_params_create_big(device, degree, len(m), _ptr(m), _ptr(tl), len(tl), C.byref(h)))
+        elif tables_fn is None:
             check(L.fhe_params_create(device, degree, len(m), _ptr(m), plaintext_modulus, C.byref(h)))
+        elif big:
+            cb = _tables_cb(tables_fn)
+            check(L.fhe_params_create_big_with_tables(device, degree, len(m), _ptr(m), _ptr(tl), len(tl), cb, None,
+                                                      C.byref(h)))
         else:
             cb = _tables_cb(tables_fn)
             check(L.fhe_params_create_with_tables(device, degree, len(m), _ptr(m), plaintext_modulus, cb, None,
@@ -1418,6 +1492,7 @@ class BfvParameters:
         self.degree, self.plaintext, self.moduli, self.device = degree, plaintext_modulus, [int(x) for x in m], device
         self.variance = variance
         self.max_level = L.fhe_params_max_level(h)
+        self.plaintext_limbs = int(L.fhe_params_plaintext_limbs(h))   # W_t: 1 unless t exceeds 64 bits
 
     def __del__(self):
         if getattr(self, "_h", None) is not None and _lib._lib is not None:
@@ -1478,6 +1553,22 @@ class BfvParameters:
         nparts = int(ct.shape[-3])
         b = sc.from_ctx._batch(ct) // nparts
         oshape = tuple(ct.shape[:-3]) + (self.degree,)
+        if self.plaintext_limbs > 1:
+            # the Large branch (secret_key.rs:238-250, fhe_bfv_decrypt_big_dev): device in -> limbs [..., N, W_t];
+            # numpy in -> Python ints [..., N] (staged: the big forms have no host-pointer twin)
+            if getattr(self, "_big_encoder", None) is None:
+                self._big_encoder = self.encoder()
+            host = not _is_dev(ct)
+            staged = [DeviceArray.from_numpy(_np(a), max(self.device, 0)) for a in (ct, s_ntt)] if host else []
+            x, sk = staged if host else (ct, s_ntt)
+            out = (DeviceArray(oshape + (self.plaintext_limbs,), x.device) if host
+                   else _empty_dev(ct, oshape + (self.plaintext_limbs,)))
+            try:
+                check(L.fhe_bfv_decrypt_big_dev(self._big_encoder._h, sc._h, _dptr(sk), _dptr(x), nparts, _dptr(out), b,
+                                                _stream()))
+                return _from_limbs(out.download()) if host else out
+            finally:
+                _wipe(staged[1:] + ([out] if host else []))
         if _is_dev(ct):
             out = _empty_dev(ct, oshape)
             check(L.fhe_bfv_decrypt_dev(sc._h, int(self.plaintext), _dptr(s_ntt), _dptr(ct), nparts, _dptr(out), b,
@@ -1951,13 +2042,20 @@ class DecryptionShare(SecretKeySwitchShare):
         first = _first_share(shares)
         par, ctx, st, h, x, B, PL = SecretKeySwitchShare._summed(shares)
         sc = par.plain_scaler(first.level)
-        out = st.out(tuple(int(d) for d in first.ct.shape[:-3]) + (par.degree,))
-        check(_lib.lib().fhe_mbfv_decrypt_dev(sc._h, int(par.plaintext), _dptr(x), _dptr(h), int(h.shape[0]), B * PL,
-                                              _dptr(out), B, _stream()))
+        wt = par.plaintext_limbs
+        out = st.out(tuple(int(d) for d in first.ct.shape[:-3]) + ((par.degree,) if wt == 1 else (par.degree, wt)))
+        if wt > 1:   # the Large tail (fhe_mbfv_decrypt_big_dev): limbs [..., N, W_t], Python ints for host input
+            if getattr(par, "_big_encoder", None) is None:
+                par._big_encoder = par.encoder()
+            check(_lib.lib().fhe_mbfv_decrypt_big_dev(par._big_encoder._h, sc._h, _dptr(x), _dptr(h), int(h.shape[0]),
+                                                      B * PL, _dptr(out), B, _stream()))
+        else:
+            check(_lib.lib().fhe_mbfv_decrypt_dev(sc._h, int(par.plaintext), _dptr(x), _dptr(h), int(h.shape[0]), B * PL,
+                                                  _dptr(out), B, _stream()))
         if not st.host:
             return out
         try:
-            return out.download()
+            return _from_limbs(out.download()) if wt > 1 else out.download()
         finally:
             _wipe([out])   # (the plaintext coefficients)
 

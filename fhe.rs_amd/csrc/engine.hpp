@@ -1099,6 +1099,7 @@ inline void polys_from_seeds(const Ctx &c, const uint8_t *seeds, u64 *polys, siz
 struct Scaler {
     const Ctx *from = nullptr, *to = nullptr;
     size_t ncommon = 0;
+    bool wide_num = false;   // the numerator exceeds 64 bits: a cipher -> plain scaler of a plaintext modulus above 2^64
     ScalerConstants c;
     DevBuf<u64> d_all;
     k::ScalerDev dev{};
@@ -1279,6 +1280,7 @@ inline std::unique_ptr<Scaler> scaler_create(const Ctx &from, const Ctx &to, con
     s->to = &to;
     RnsContext rf(from.moduli), rt(to.moduli);
     s->c = make_scaler_constants(rf, rt, num, den);
+    s->wide_num = !num.fits_u64();
     if (s->c.is_one) {
         size_t k = 0;
         while (k < from.L && k < to.L && from.moduli[k] == to.moduli[k]) k++;
@@ -2108,6 +2110,7 @@ inline void decrypt(const Scaler &sc, u64 t, const u64 *s_ntt, const u64 *ct, si
     cc.need_device();
     require(nparts >= 1, E_ARG, "a ciphertext has at least one part");
     check_plain_context(sc);
+    require(!sc.wide_num, E_PARAMETER_MISMATCH, "the scaler's plaintext modulus exceeds 64 bits: use fhe_bfv_decrypt_big_dev");
     if (!batch) return;
     // the phase is secret-dependent: cleared before the block goes back to the pool
     WsGuard ph(batch * (u64)cc.L * cc.n * sizeof(u64), s, true);
@@ -2616,6 +2619,14 @@ struct Encoder {
     DevBuf<uint32_t> d_map, d_inv_map;
     std::vector<u64> q_mod_t;         // per level (parameters.rs:616-633)
     std::vector<std::unique_ptr<DevBuf<k::u64x2>>> d_delta;   // per level [L] {delta_i, shoup}, delta_i = (-t)^-1 mod q_i
+    // The big form (PlaintextModulus::Large, t >= 2^64; encoder_create_big): wt = W_t > 1 limbs, `t` and `tm` unused, no
+    // tctx.  t, mu = floor(2^(128 W_t) / t) and the per-level q_mod_t travel to the kernels by value.
+    size_t wt = 1;
+    BigUint t_big;
+    std::vector<u64> mu_big;                    // [wt + 2]
+    std::vector<std::vector<u64>> q_mod_t_big;  // per level [wt]
+    const Ctx *plain = nullptr;                 // the plaintext context: the level of `top` with the first P moduli
+    bool big() const { return wt > 1; }
 };
 
 // matrix_reps_index_map (parameters.rs:711-725): generator 3, m = 2N, bit-reversed positions
@@ -2686,6 +2697,7 @@ constexpr const char *ENC_TILE = "unsupported encoding tile size";
 // (F/bfv/plaintext.rs:172-196): values [batch][nvalues] -> out [batch][L_level][N] Ntt.
 inline void encode(const Encoder &e, bool simd, bool scaled, size_t level, const u64 *values, size_t nvalues, u64 *out,
                    size_t batch, hipStream_t s) {
+    require(!e.big(), E_PARAMETER_MISMATCH, "the plaintext modulus exceeds 64 bits: use fhe_bfv_encode_big_dev");
     const Ctx *qc = e.top->at_level(level);
     if (!qc) throw StatusError(E_INVALID_LEVEL, "InvalidLevel");
     if (simd && !e.tctx) throw StatusError(E_SIMD_UNAVAILABLE, "SimdUnavailable: the plaintext modulus admits no degree-N NTT");
@@ -2741,6 +2753,7 @@ inline void encode(const Encoder &e, bool simd, bool scaled, size_t level, const
 
 // Vec<u64>::try_decode (F/bfv/plaintext.rs:157-170, 408-431): coefficients mod t [batch][N] -> values [batch][N].
 inline void decode(const Encoder &e, bool simd, const u64 *coeffs, u64 *out, size_t batch, hipStream_t s) {
+    require(!e.big(), E_PARAMETER_MISMATCH, "the plaintext modulus exceeds 64 bits: the coefficients are limbs");
     if (simd && !e.tctx) throw StatusError(E_SIMD_UNAVAILABLE, "SimdUnavailable: the plaintext modulus admits no degree-N NTT");
     if (!batch) return;
     require(batch <= 0x7fffffffu, E_ARG, "decode: batch exceeds the grid limit");
@@ -3234,6 +3247,7 @@ inline void mbfv_decrypt(const Scaler &sc, u64 t, const u64 *ct, const u64 *shar
     cc.need_device();
     require(nshares >= 1, E_ARG, "NoShares: an aggregation needs at least one share");
     check_plain_context(sc);
+    require(!sc.wide_num, E_PARAMETER_MISMATCH, "the scaler's plaintext modulus exceeds 64 bits: use fhe_mbfv_decrypt_big_dev");
     if (!batch) return;
     const u64 PL = (u64)cc.L * cc.n;
     WsGuard ph(batch * PL * sizeof(u64), s, true);   // the phase: cleared before the block goes back to the pool
@@ -3333,6 +3347,180 @@ inline void centered_bits(const Ctx &c, const u64 *polys, const k::LiftSub &sub,
                (const uint32_t *)part.p, (uint32_t)nblk, (uint32_t)batch, out_bits);
 }
 
+// ------------------------------------------------------- plaintext moduli above 64 bits ----
+// PlaintextModulus::Large (F/bfv/parameters.rs:560-738): the encoder of a t with W_t = 2 ... 4 limbs.  The plaintext
+// context is the shortest prefix of the moduli with at least bits(t) + 60 bits, capped at all of them (:578-595).
+inline size_t plain_rows(const Ctx &top, size_t t_bits) {
+    size_t acc = 0, count = 0;
+    for (u64 q : top.moduli) {
+        acc += 64 - (size_t)__builtin_clzll(q | 1);
+        count++;
+        if (acc >= t_bits + 60) break;
+    }
+    return count;
+}
+inline std::unique_ptr<Encoder> encoder_create_big(const Ctx &top, const BigUint &t) {
+    top.need_device();
+    auto e = std::make_unique<Encoder>();
+    e->top = &top;
+    e->n = top.n;
+    e->logn = top.logn;
+    e->wt = t.w.size();
+    require(e->wt >= 2 && e->wt <= (size_t)k::BIGT_WMAX, E_INVALID_MODULUS, "the plaintext modulus must be below 2^256");
+    e->t_big = t;
+    const BigUint mu = BigUint::pow2(128 * e->wt) / t;
+    for (size_t i = 0; i < e->wt + 2; i++) e->mu_big.push_back(mu.limb(i));
+    e->plain = top.at_level(top.L - plain_rows(top, t.bits()));
+    // the tail reduces a value below Q_p with a Barrett step that holds 2 W_t limbs
+    require(e->plain->lift_w <= 2 * e->wt && e->plain->L >= e->wt, E_INVALID_MODULUS,
+            "the plaintext context is too long for the plaintext modulus");
+    for (const Ctx *c = &top; c; c = c->next.get()) {
+        std::vector<k::u64x2> d(c->L);
+        for (size_t i = 0; i < c->L; i++) {
+            const u64 q = c->moduli[i];
+            const u64 neg_t = (q - t.mod_u64(q)) % q;
+            require(neg_t != 0, E_INVALID_MODULUS, "the plaintext modulus must be invertible modulo every q_i");
+            const u64 inv = powmod(neg_t, q - 2, q);
+            d[i] = k::u64x2{inv, shoup(inv, q)};
+        }
+        const BigUint qt = ctx_modulus(*c) % t;
+        std::vector<u64> limbs(e->wt);
+        for (size_t i = 0; i < e->wt; i++) limbs[i] = qt.limb(i);
+        e->q_mod_t_big.push_back(limbs);
+        e->d_delta.push_back(std::make_unique<DevBuf<k::u64x2>>());
+        e->d_delta.back()->upload(d);
+    }
+    return e;
+}
+template <int WT>
+inline k::BigT<WT> bigt_consts(const Encoder &e) {
+    k::BigT<WT> bt;
+    for (int i = 0; i < WT; i++) bt.t[i] = e.t_big.limb(i);
+    for (int i = 0; i < WT + 2; i++) bt.mu[i] = e.mu_big[i];
+    return bt;
+}
+inline void need_big(const Encoder &e) {
+    require(e.big(), E_PARAMETER_MISMATCH, "the plaintext modulus fits 64 bits: use the u64 entry point");
+}
+
+// PlaintextVec::try_encode for Vec<BigUint>, Encoding::poly (F/bfv/plaintext_vec.rs:105-132), or with `scaled`
+// Plaintext::to_poly's Large branch (F/bfv/plaintext.rs:172-197): values [batch][nvalues][W_t] -> out
+// [batch][L_level][N] Ntt.  The projection writes the rows, the forward transform runs on them in place.
+inline void encode_big(const Encoder &e, bool simd, bool scaled, size_t level, const u64 *values, size_t nvalues, u64 *out,
+                       size_t batch, hipStream_t s) {
+    need_big(e);
+    const Ctx *qc = e.top->at_level(level);
+    if (!qc) throw StatusError(E_INVALID_LEVEL, "InvalidLevel");
+    if (simd) throw StatusError(E_SIMD_UNAVAILABLE, "SimdUnavailable: no NTT modulo a plaintext modulus above 64 bits");
+    if (nvalues > e.n) throw StatusError(E_TOO_MANY_VALUES, "TooManyValues: more values than the degree");
+    if (!batch) return;
+    const u64 total = (u64)batch * e.n;
+    require(blocks_for(total, k::BIGT_THREADS) <= 0x7fffffffu, E_ARG, "encode: batch exceeds the grid limit");
+    with_int<2, k::BIGT_WMAX>(e.wt, "encode: unsupported plaintext limbs", [&](auto w) {
+        constexpr int WT = decltype(w)::value;
+        k::BigVal<WT> qmt;
+        for (int i = 0; i < WT; i++) qmt.w[i] = e.q_mod_t_big[level][i];
+        launch_k<k::bigt_project_kernel<WT>>("bigt_project", dim3(blocks_for(total, k::BIGT_THREADS)), dim3(k::BIGT_THREADS),
+                                             0, s, values, (u64)nvalues, out, (uint32_t)qc->L, qc->dmods(),
+                                             (const k::u64x2 *)e.d_delta[level]->p, bigt_consts<WT>(e), qmt,
+                                             scaled ? 1u : 0u, (uint32_t)e.logn, total);
+    });
+    launch_ntt(*qc, false, out, out, full_map(*qc, qc->L), batch, s);
+}
+
+// The tail of the Large branch of SecretKey::try_decrypt (F/bfv/keys/secret_key.rs:238-250): polys [batch][P][N],
+// PowerBasis residues over the plaintext context -> out [batch][N][W_t], ((x + t) mod Q_p) mod t of the lifted x.
+constexpr int BIGT_PC_MAX = 8;
+inline void reduce_big(const Encoder &e, const u64 *polys, size_t rows, u64 *out, size_t batch, hipStream_t s) {
+    need_big(e);
+    const Ctx &pc = *e.plain;
+    require(rows == pc.L, E_PARAMETER_MISMATCH, "reduce: the polynomials must have one row per plaintext-context modulus");
+    if (!batch) return;
+    require(pc.L <= (size_t)k::LIFT_LMAX, E_ARG, "reduce: more plaintext-context moduli than the generic instance holds");
+    const u64 nblk = blocks_for(pc.n, k::BIGT_THREADS);
+    require(batch * nblk <= 0x7fffffffu, E_ARG, "reduce: batch exceeds the grid limit");
+    const u64 *tab = lift_consts(pc);
+    const dim3 grid((unsigned)(batch * nblk)), block(k::BIGT_THREADS);
+    with_int<2, k::BIGT_WMAX>(e.wt, "reduce: unsupported plaintext limbs", [&](auto w) {
+        constexpr int WT = decltype(w)::value;
+        const k::BigT<WT> bt = bigt_consts<WT>(e);
+        if (pc.L <= (size_t)BIGT_PC_MAX)
+            with_int<WT, BIGT_PC_MAX>(pc.L, "reduce: plaintext context shorter than the plaintext modulus", [&](auto p) {
+                launch_k<k::bigt_tail_kernel<decltype(p)::value, WT>>("bigt_tail", grid, block, 0, s, polys, tab, bt, out,
+                                                                      (uint32_t)pc.L, (uint32_t)pc.logn, (uint32_t)nblk);
+            });
+        else
+            launch_k<k::bigt_tail_kernel<0, WT>>("bigt_tail", grid, block, 0, s, polys, tab, bt, out, (uint32_t)pc.L,
+                                                 (uint32_t)pc.logn, (uint32_t)nblk);
+    });
+}
+// Scaler::scale (t / Q_level) of the PowerBasis phase into the plaintext context, then the tail: out [batch][N][W_t]
+inline void check_plain_context_big(const Encoder &e, const Scaler &sc) {
+    const Ctx *lc = e.top;
+    while (lc && !lc->same_ring(*sc.from)) lc = lc->next.get();
+    require(lc != nullptr, E_PARAMETER_MISMATCH, "the scaler's source is not a level of the encoder's parameter set");
+    require(sc.to->same_ring(*e.plain), E_PARAMETER_MISMATCH, "the scaler's target is not the plaintext context");
+    require(e.top->device == sc.from->device, E_PARAMETER_MISMATCH, "the encoder and the scaler live on different devices");
+}
+inline void decrypt_tail_big(const Encoder &e, const Scaler &sc, const u64 *ph, u64 *out, size_t batch, hipStream_t s) {
+    WsGuard d(batch * sc.to->L * sc.from->n * sizeof(u64), s, true);   // the scaled plaintext: secret-dependent
+    scale_polys(sc, ph, d.u(), batch, false, s);
+    reduce_big(e, d.u(), sc.to->L, out, batch, s);
+}
+// SecretKey::try_decrypt, Large branch (F/bfv/keys/secret_key.rs:198-250): ct [batch][nparts][L][N] Ntt, s_ntt [L][N]
+// -> out [batch][N][W_t].
+inline void decrypt_big(const Encoder &e, const Scaler &sc, const u64 *s_ntt, const u64 *ct, size_t nparts, u64 *out,
+                        size_t batch, hipStream_t s) {
+    need_big(e);
+    const Ctx &cc = *sc.from;
+    cc.need_device();
+    require(nparts >= 1, E_ARG, "a ciphertext has at least one part");
+    check_plain_context_big(e, sc);
+    if (!batch) return;
+    WsGuard ph(batch * (u64)cc.L * cc.n * sizeof(u64), s, true);   // the phase: cleared before the block is reused
+    phase_power_basis(cc, s_ntt, ct, nparts, ph.u(), batch, s);
+    decrypt_tail_big(e, sc, ph.u(), out, batch, s);
+}
+// Plaintext::from_shares (F/mbfv/secret_key_switch.rs:145-186) with the Large tail: as mbfv_decrypt, out [batch][N][W_t].
+inline void mbfv_decrypt_big(const Encoder &e, const Scaler &sc, const u64 *ct, const u64 *shares, size_t nshares,
+                             u64 share_stride, u64 *out, size_t batch, hipStream_t s) {
+    need_big(e);
+    const Ctx &cc = *sc.from;
+    cc.need_device();
+    require(nshares >= 1, E_ARG, "NoShares: an aggregation needs at least one share");
+    check_plain_context_big(e, sc);
+    if (!batch) return;
+    const u64 PL = (u64)cc.L * cc.n;
+    WsGuard ph(batch * PL * sizeof(u64), s, true);
+    mbfv_sum(cc, shares, nshares, share_stride, batch, ct, 2 * PL, ph.u(), s);
+    launch_ntt(cc, true, ph.u(), ph.u(), full_map(cc, cc.L), batch, s);
+    decrypt_tail_big(e, sc, ph.u(), out, batch, s);
+}
+// SecretKey::measure_noise with a Large plaintext modulus: to_poly(m) comes from encode_big in Ntt form and is
+// subtracted from the phase before the inverse transform (one forward transform more than the u64 path, whose loader
+// subtracts in PowerBasis); m [batch][N][W_t] or null.
+inline void measure_noise_big(const Encoder &e, const Scaler &sc, size_t level, const u64 *s_ntt, const u64 *ct,
+                              size_t nparts, const u64 *m, u64 *noise_bits, size_t batch, hipStream_t s) {
+    const Ctx &cc = *sc.from;
+    if (!m) check_plain_context_big(e, sc);
+    if (!batch) return;
+    const u64 PL = (u64)cc.L * cc.n;
+    WsGuard ph(batch * PL * sizeof(u64), s, true), mp(batch * PL * sizeof(u64), s, true);
+    FHE_LAUNCH("phase", k::phase_kernel, dim3(blocks_for(PL, EW_THREADS), (unsigned)batch), dim3(EW_THREADS), 0, s, ct,
+               s_ntt, ph.u(), cc.dmods(), (uint32_t)nparts, (uint32_t)cc.logn, PL);
+    std::unique_ptr<WsGuard> dec;
+    if (!m) {
+        dec = std::make_unique<WsGuard>(batch * cc.n * e.wt * sizeof(u64), s, true);
+        launch_ntt(cc, true, ph.u(), mp.u(), full_map(cc, cc.L), batch, s);
+        decrypt_tail_big(e, sc, mp.u(), dec->u(), batch, s);
+        m = dec->u();
+    }
+    encode_big(e, false, true, level, m, e.n, mp.u(), batch, s);
+    ew_op(cc, ph.u(), mp.u(), batch, k::EW_SUB, s);
+    launch_ntt(cc, true, ph.u(), ph.u(), full_map(cc, cc.L), batch, s);
+    centered_bits(cc, ph.u(), k::LiftSub{nullptr, nullptr, 0, k::u64x2{0, 0}}, noise_bits, batch, s);
+}
+
 // SecretKey::measure_noise (F/bfv/keys/secret_key.rs:55-98): the phase in PowerBasis minus Plaintext::to_poly of m --
 // the ciphertext's own decryption (m == null, the reference) or the plaintext the caller expects, [batch][N] in
 // [0, t) --, lifted and measured.  ct [batch][nparts][L][N] Ntt, s_ntt [L][N] -> noise_bits [batch].
@@ -3346,6 +3534,7 @@ inline void measure_noise(const Encoder &e, const Scaler &sc, const u64 *s_ntt, 
     while (lc && !lc->same_ring(cc)) lc = lc->next.get(), level++;
     require(lc != nullptr, E_PARAMETER_MISMATCH, "the ciphertext context is not a level of the encoder's parameter set");
     require(e.top->device == cc.device, E_PARAMETER_MISMATCH, "the encoder and the scaler's context live on different devices");
+    if (e.big()) return measure_noise_big(e, sc, level, s_ntt, ct, nparts, m, noise_bits, batch, s);
     if (!m) check_plain_context(sc);
     if (!batch) return;
     const u64 PL = (u64)cc.L * cc.n;

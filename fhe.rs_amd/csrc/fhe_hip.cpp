@@ -43,7 +43,8 @@ struct fhe_params {
     bool host_tables = false;               // created with the host's NTT tables (callback)
     std::map<u64, HostTables> table_cache;  // modulus -> tables, filled while the callback was alive
     size_t degree = 0;
-    u64 plaintext = 0;
+    u64 plaintext = 0;                      // t when it fits 64 bits, else 0
+    BigUint plaintext_big;                  // t, of any size (PlaintextModulus::Large above 64 bits)
     std::vector<u64> moduli;
     std::vector<size_t> moduli_sizes;
     std::unique_ptr<fhe_ctx> top;                       // level-0 context (+ chain)
@@ -1476,47 +1477,78 @@ fhe_status fhe_bfv_tensor_dev(const fhe_mul *m, size_t lhs_parts, size_t rhs_par
 }
 
 // -------------------------------------------------------------------------- params ----
+static void params_create(int device, size_t degree, size_t nmoduli, const uint64_t *moduli, const BigUint &t,
+                          fhe_ntt_tables_fn tables, void *user, fhe_params **out) {
+    need(out, "out");
+    *out = nullptr;
+    if (nmoduli == 0) throw StatusError(FHE_E_EMPTY_MODULI, "EmptyModuli");
+    need(moduli, "moduli");
+    require(t >= BigUint(2), E_ARG, "plaintext modulus must be >= 2");
+    auto p = std::make_unique<fhe_params>();
+    p->device = device;
+    p->host_tables = tables != nullptr;
+    p->degree = degree;
+    p->plaintext = t.fits_u64() ? t.to_u64() : 0;
+    p->plaintext_big = t;
+    p->moduli.assign(moduli, moduli + nmoduli);
+    for (u64 q : p->moduli) p->moduli_sizes.push_back(64 - (size_t)__builtin_clzll(q | 1));
+    p->top = wrap_ctx(ctx_create_cb(device, degree, p->moduli, tables, user, p->host_tables, p->table_cache));
+    if (!t.fits_u64()) {
+        // PlaintextModulus::Large: t below Q, invertible modulo every q_i (parameters.rs:607-633)
+        require(t < ctx_modulus(*p->top->c), E_INVALID_MODULUS, "the plaintext modulus must be below the ciphertext modulus");
+        for (u64 q : p->moduli)
+            require(t.mod_u64(q) != 0, E_INVALID_MODULUS, "the plaintext modulus must be invertible modulo every q_i");
+    }
+    // extended basis: n+1 primes of 62 bits (parameters.rs:660-676)
+    std::vector<u64> ext = extended_basis_primes(degree, p->moduli, nmoduli + 1);
+    for (size_t level = 0; level < nmoduli; level++) {
+        const size_t nl = nmoduli - level;
+        size_t modulus_size = 0;
+        for (size_t i = 0; i < nl; i++) modulus_size += p->moduli_sizes[i];
+        const size_t n_moduli = (modulus_size + 60 + 61) / 62;  // div_ceil
+        std::vector<u64> mm(p->moduli.begin(), p->moduli.begin() + nl);
+        mm.insert(mm.end(), ext.begin(), ext.begin() + n_moduli);
+        auto mc = wrap_ctx(ctx_create_cb(device, degree, mm, tables, user, p->host_tables, p->table_cache));
+        const Ctx &base = *p->top->c->at_level(level);
+        RnsContext rb(base.moduli);
+        auto e = std::make_unique<fhe_scaler>();
+        e->s = scaler_create(base, *mc->c, BigUint(1), BigUint(1));
+        auto d = std::make_unique<fhe_scaler>();
+        d->s = scaler_create(*mc->c, base, t, rb.product);
+        p->mul_ctx.push_back(std::move(mc));
+        p->extender.push_back(std::move(e));
+        p->down.push_back(std::move(d));
+    }
+    *out = p.release();
+}
 fhe_status fhe_params_create_with_tables(int device, size_t degree, size_t nmoduli, const uint64_t *moduli,
                                          uint64_t plaintext_modulus, fhe_ntt_tables_fn tables, void *user,
                                          fhe_params **out) {
+    return guard([&] { params_create(device, degree, nmoduli, moduli, BigUint(plaintext_modulus), tables, user, out); });
+}
+// BfvParametersBuilder::set_plaintext_modulus_biguint + build (F/bfv/parameters.rs:560-738)
+fhe_status fhe_params_create_big_with_tables(int device, size_t degree, size_t nmoduli, const uint64_t *moduli,
+                                             const uint64_t *t_limbs, size_t t_nlimbs, fhe_ntt_tables_fn tables,
+                                             void *user, fhe_params **out) {
     return guard([&] {
         need(out, "out");
         *out = nullptr;
-        if (nmoduli == 0) throw StatusError(FHE_E_EMPTY_MODULI, "EmptyModuli");
-        need(moduli, "moduli");
-        require(plaintext_modulus >= 2, E_ARG, "plaintext modulus must be >= 2");
-        auto p = std::make_unique<fhe_params>();
-        p->device = device;
-        p->host_tables = tables != nullptr;
-        p->degree = degree;
-        p->plaintext = plaintext_modulus;
-        p->moduli.assign(moduli, moduli + nmoduli);
-        for (u64 q : p->moduli) p->moduli_sizes.push_back(64 - (size_t)__builtin_clzll(q | 1));
-        p->top = wrap_ctx(ctx_create_cb(device, degree, p->moduli, tables, user, p->host_tables, p->table_cache));
-        // extended basis: n+1 primes of 62 bits (parameters.rs:660-676)
-        std::vector<u64> ext = extended_basis_primes(degree, p->moduli, nmoduli + 1);
-        BigUint t(plaintext_modulus);
-        for (size_t level = 0; level < nmoduli; level++) {
-            const size_t nl = nmoduli - level;
-            size_t modulus_size = 0;
-            for (size_t i = 0; i < nl; i++) modulus_size += p->moduli_sizes[i];
-            const size_t n_moduli = (modulus_size + 60 + 61) / 62;  // div_ceil
-            std::vector<u64> mm(p->moduli.begin(), p->moduli.begin() + nl);
-            mm.insert(mm.end(), ext.begin(), ext.begin() + n_moduli);
-            auto mc = wrap_ctx(ctx_create_cb(device, degree, mm, tables, user, p->host_tables, p->table_cache));
-            const Ctx &base = *p->top->c->at_level(level);
-            RnsContext rb(base.moduli);
-            auto e = std::make_unique<fhe_scaler>();
-            e->s = scaler_create(base, *mc->c, BigUint(1), BigUint(1));
-            auto d = std::make_unique<fhe_scaler>();
-            d->s = scaler_create(*mc->c, base, t, rb.product);
-            p->mul_ctx.push_back(std::move(mc));
-            p->extender.push_back(std::move(e));
-            p->down.push_back(std::move(d));
+        need(t_limbs, "t_limbs");
+        const BigUint t = BigUint::from_limbs(t_limbs, t_nlimbs);
+        if (!t.fits_u64()) {
+            require(t.w.size() <= (size_t)k::BIGT_WMAX, E_INVALID_MODULUS, "the plaintext modulus must be below 2^256");
+        } else if (nmoduli) {
+            // (the reference's PlaintextModulus::Small holds a Modulus: below 2^62)
+            require((t.to_u64() >> 62) == 0, E_INVALID_MODULUS, "InvalidPlaintextModulus: a 64-bit t must be below 2^62");
         }
-        *out = p.release();
+        params_create(device, degree, nmoduli, moduli, t, tables, user, out);
     });
 }
+fhe_status fhe_params_create_big(int device, size_t degree, size_t nmoduli, const uint64_t *moduli, const uint64_t *t_limbs,
+                                 size_t t_nlimbs, fhe_params **out) {
+    return fhe_params_create_big_with_tables(device, degree, nmoduli, moduli, t_limbs, t_nlimbs, nullptr, nullptr, out);
+}
+size_t fhe_params_plaintext_limbs(const fhe_params *p) { return p ? std::max<size_t>(1, p->plaintext_big.w.size()) : 0; }
 fhe_status fhe_params_create(int device, size_t degree, size_t nmoduli, const uint64_t *moduli,
                              uint64_t plaintext_modulus, fhe_params **out) {
     return fhe_params_create_with_tables(device, degree, nmoduli, moduli, plaintext_modulus, nullptr, nullptr, out);
@@ -1578,7 +1610,7 @@ fhe_status fhe_mul_create_default(const fhe_params *p, size_t level, const fhe_k
                 auto e = std::make_unique<fhe_scaler>();
                 e->s = scaler_create(base, *mc->c, BigUint(1), BigUint(1));
                 auto d = std::make_unique<fhe_scaler>();
-                d->s = scaler_create(*mc->c, base, BigUint(p->plaintext), rb.product);
+                d->s = scaler_create(*mc->c, base, p->plaintext_big, rb.product);
                 ext = e->s.get();
                 down = d->s.get();
                 h->ctxs.push_back(std::move(mc));
@@ -1602,6 +1634,12 @@ fhe_status fhe_encoder_create(const fhe_params *par, fhe_ntt_tables_fn tables, v
         top.need_device();
         set_device(top);
         // NttOperator::new(t, N) exists iff t supports it (parameters.rs:71-75, 598); otherwise SIMD is unavailable
+        if (!par->plaintext_big.fits_u64()) {   // PlaintextModulus::Large: no ntt_operator, SIMD unavailable
+            auto h = std::make_unique<fhe_encoder>();
+            h->e = encoder_create_big(top, par->plaintext_big);
+            *out = h.release();
+            return;
+        }
         std::unique_ptr<Ctx> tctx;
         if (supports_ntt(par->plaintext, par->degree)) {
             std::map<u64, HostTables> cache;
@@ -1699,6 +1737,69 @@ fhe_status fhe_bfv_measure_noise_dev(const fhe_encoder *enc, const fhe_scaler *s
         }
         set_device(*sc->s->from);
         measure_noise(*enc->e, *sc->s, s_ntt, ct, nparts, m_or_null, noise_bits, batch, as_stream(stream));
+    });
+}
+
+// ------------------------------------------------------ plaintext moduli above 64 bits ----
+// Device-pointer forms only, like the u64 encoding entry points.
+fhe_status fhe_bfv_encode_big_dev(const fhe_encoder *enc, int encoding, int scaled, size_t level, const uint64_t *values,
+                                  size_t nvalues, uint64_t *out, size_t batch, void *stream) {
+    return guard([&] {
+        need(enc, "encoder");
+        require(encoding == FHE_ENCODING_POLY || encoding == FHE_ENCODING_SIMD, E_ARG, "unknown encoding");
+        if (batch) {
+            if (nvalues) need(values, "values");
+            need(out, "out");
+        }
+        set_device(*enc->e->top);
+        encode_big(*enc->e, encoding == FHE_ENCODING_SIMD, scaled != 0, level, values, nvalues, out, batch, as_stream(stream));
+    });
+}
+size_t fhe_encoder_plain_rows(const fhe_encoder *enc) {
+    if (!enc) return 0;
+    const Encoder &e = *enc->e;
+    return e.big() ? e.plain->L : plain_rows(*e.top, 64 - (size_t)__builtin_clzll(e.t | 1));
+}
+fhe_status fhe_bfv_reduce_big_dev(const fhe_encoder *enc, const uint64_t *polys, size_t rows, uint64_t *out, size_t batch,
+                                  void *stream) {
+    return guard([&] {
+        need(enc, "encoder");
+        if (batch) {
+            need(polys, "polys");
+            need(out, "out");
+        }
+        set_device(*enc->e->top);
+        reduce_big(*enc->e, polys, rows, out, batch, as_stream(stream));
+    });
+}
+fhe_status fhe_bfv_decrypt_big_dev(const fhe_encoder *enc, const fhe_scaler *sc, const uint64_t *s_ntt, const uint64_t *ct,
+                                   size_t nparts, uint64_t *out, size_t batch, void *stream) {
+    return guard([&] {
+        need(enc, "encoder");
+        need(sc, "cipher_plain_scaler");
+        sc->s->from->need_device();
+        if (batch) {
+            need(s_ntt, "s_ntt");
+            need(ct, "ct");
+            need(out, "out");
+        }
+        set_device(*sc->s->from);
+        decrypt_big(*enc->e, *sc->s, s_ntt, ct, nparts, out, batch, as_stream(stream));
+    });
+}
+fhe_status fhe_mbfv_decrypt_big_dev(const fhe_encoder *enc, const fhe_scaler *sc, const uint64_t *ct, const uint64_t *shares,
+                                    size_t nshares, size_t share_stride, uint64_t *out, size_t batch, void *stream) {
+    return guard([&] {
+        need(enc, "encoder");
+        need(sc, "cipher_plain_scaler");
+        sc->s->from->need_device();
+        if (batch) {
+            need(ct, "ct");
+            need(shares, "shares");
+            need(out, "out");
+        }
+        set_device(*sc->s->from);
+        mbfv_decrypt_big(*enc->e, *sc->s, ct, shares, nshares, share_stride, out, batch, as_stream(stream));
     });
 }
 

@@ -32,6 +32,8 @@
 //                           RelinearizationKey / GaloisKey::new   F/bfv/keys/key_switching_key.rs:71-236, galois_key.rs:26-58
 //   lift_kernel, noise_max_kernel       RnsContext::lift, SecretKey::measure_noise   M/rns/mod.rs:138-143, F/bfv/keys/secret_key.rs:55-98
 //   mbfv_share_kernel, mbfv_sum_kernel  the shares of the multiparty protocols and their aggregation   F/mbfv/*.rs
+//   bigt_project_kernel, bigt_tail_kernel   plaintext moduli above 64 bits: Vec<BigUint> encoding and the Large branch of
+//                           SecretKey::try_decrypt   F/bfv/plaintext_vec.rs:105-132, plaintext.rs:172-197, secret_key.rs:238-250
 // Compile-time knobs live in knobs.hpp (pinned in the release build); rejected kernel variants in tools/lab/ (lab builds only).
 #pragma once
 #include "kernels_common.hpp"
@@ -45,6 +47,7 @@
 #include "kernels_keygen.hpp"
 #include "kernels_noise.hpp"
 #include "kernels_mbfv.hpp"
+#include "kernels_bigt.hpp"
 
 namespace fhe {
 namespace k {

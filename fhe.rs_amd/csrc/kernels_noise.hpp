@@ -73,6 +73,7 @@ __global__ void __launch_bounds__(LIFT_THREADS)
         }
     }
     // Garner: d_i = (..((r_i - d_0) q_0^-1 - d_1) q_1^-1 ...) mod q_i, lazily below 2 q_i inside the chain
+    // (kernels_bigt.hpp's bigt_garner_horner restates this loop and Horner's below: a change here belongs there too)
 #pragma unroll UF
     for (int i = 1; i < L; i++) {
         const u64 q = tab[i], mq = tab[L + i];

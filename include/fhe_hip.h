@@ -679,6 +679,55 @@ fhe_status fhe_mbfv_decrypt_dev(const fhe_scaler *cipher_plain_scaler, uint64_t 
                                 const uint64_t *shares, size_t nshares, size_t share_stride, uint64_t *out, size_t batch,
                                 void *stream);
 
+/* ------------------------------------------- plaintext moduli above 64 bits ---- */
+/* PlaintextModulus::Large (BfvParametersBuilder::set_plaintext_modulus_biguint, F/bfv/parameters.rs:560-738): t as
+ * t_nlimbs little-endian limbs, leading zero limbs trimmed.  W_t = ceil(bits(t) / 64).  A t that fits one limb behaves
+ * exactly as fhe_params_create.  Otherwise t < 2^256 (W_t <= 4: the limit of this engine; more ->
+ * FHE_E_INVALID_MODULUS), t < Q at level 0 and no q_i divides t (else FHE_E_INVALID_MODULUS); t in [2^62, 2^64) ->
+ * FHE_E_INVALID_MODULUS (the reference's InvalidPlaintextModulus).  The down-scalers have the factor t / Q_level; the
+ * plaintext context is the shortest prefix of the moduli with at least bits(t) + 60 bits, capped at all of them.
+ * Every other handle of the set (contexts, extenders, Multiplicator) is made and used as for a u64 t.  The u64-t entry
+ * points return FHE_E_PARAMETER_MISMATCH: fhe_bfv_encode_dev and fhe_bfv_decode_dev given such a set's encoder,
+ * fhe_bfv_decrypt(_dev) and fhe_mbfv_decrypt_dev given a scaler whose numerator exceeds 64 bits (fhe_scaler_create
+ * remembers that; a scaler made by fhe_scaler_create_from_constants cannot tell).  Nothing computes with a truncated t.  Device-pointer forms only, with no host-pointer twin. */
+fhe_status fhe_params_create_big(int device, size_t degree, size_t nmoduli, const uint64_t *moduli,
+                                 const uint64_t *t_limbs, size_t t_nlimbs, fhe_params **out);
+fhe_status fhe_params_create_big_with_tables(int device, size_t degree, size_t nmoduli, const uint64_t *moduli,
+                                             const uint64_t *t_limbs, size_t t_nlimbs, fhe_ntt_tables_fn tables,
+                                             void *user, fhe_params **out);
+/* W_t, or 1 for a parameter set whose t fits 64 bits (0 for NULL). */
+size_t fhe_params_plaintext_limbs(const fhe_params *p);
+/* PlaintextVec::try_encode for Vec<BigUint> with Encoding::poly_at_level (F/bfv/plaintext_vec.rs:105-132), or with
+ * scaled = 1 the Large branch of Plaintext::to_poly (F/bfv/plaintext.rs:172-197): values [batch][nvalues][W_t] limbs
+ * (nvalues <= N, zero-padded; more -> FHE_E_TOO_MANY_VALUES) -> out [batch][L_level][N] Ntt.  Every value is reduced
+ * modulo t first, as the u64 encoder does; the result is the reference's bit for bit whenever the value is below t.
+ * enc is fhe_encoder_create of a big set (a u64 set's -> FHE_E_PARAMETER_MISMATCH).  FHE_ENCODING_SIMD ->
+ * FHE_E_SIMD_UNAVAILABLE (the reference has no NttOperator for a Large t).  level > max -> FHE_E_INVALID_LEVEL. */
+fhe_status fhe_bfv_encode_big_dev(const fhe_encoder *enc, int encoding, int scaled, size_t level, const uint64_t *values,
+                                  size_t nvalues, uint64_t *out, size_t batch, void *stream);
+/* The tail of the Large branch of SecretKey::try_decrypt (F/bfv/keys/secret_key.rs:238-250) alone: polys [batch][P][N],
+ * PowerBasis residues over the plaintext context (P rows, product Q_p) -> out [batch][N][W_t] limbs of
+ * ((x + t) mod Q_p) mod t, x the CRT lift of the column in [0, Q_p).  `rows` is the row count of the caller's
+ * polynomials: anything but P (fhe_encoder_plain_rows) -> FHE_E_PARAMETER_MISMATCH, so that a buffer laid out for
+ * another context is never read.  The first call on an encoder uploads the context's lift table (as
+ * fhe_poly_lift_dev: it blocks the host and cannot be part of a stream capture). */
+fhe_status fhe_bfv_reduce_big_dev(const fhe_encoder *enc, const uint64_t *polys, size_t rows, uint64_t *out, size_t batch,
+                                  void *stream);
+/* P: the moduli of the encoder's plaintext context (F/bfv/parameters.rs:578-595), for any encoder; 0 for NULL. */
+size_t fhe_encoder_plain_rows(const fhe_encoder *enc);
+/* SecretKey::try_decrypt, Large branch (F/bfv/keys/secret_key.rs:198-250): as fhe_bfv_decrypt_dev with out
+ * [batch][N][W_t] limbs in [0, t).  cipher_plain_scaler: from a level of enc's set to its plaintext context with the
+ * factor t / Q_level (any other pair of contexts -> FHE_E_PARAMETER_MISMATCH).  Phase and scaled plaintext live in
+ * engine scratch that is cleared before it is reused. */
+fhe_status fhe_bfv_decrypt_big_dev(const fhe_encoder *enc, const fhe_scaler *cipher_plain_scaler, const uint64_t *s_ntt,
+                                   const uint64_t *ct, size_t nparts, uint64_t *out, size_t batch, void *stream);
+/* Plaintext::from_shares (mbfv/secret_key_switch.rs:145-186) with the Large tail: as fhe_mbfv_decrypt_dev with out
+ * [batch][N][W_t] limbs. */
+fhe_status fhe_mbfv_decrypt_big_dev(const fhe_encoder *enc, const fhe_scaler *cipher_plain_scaler, const uint64_t *ct,
+                                    const uint64_t *shares, size_t nshares, size_t share_stride, uint64_t *out,
+                                    size_t batch, void *stream);
+/* fhe_bfv_measure_noise_dev given the encoder of a big set reads m_or_null as [batch][N][W_t] limbs. */
+
 /* ------------------------------------------------- zq::primes (host, no GPU) ---- */
 /* generate_prime (M/zq/primes.rs:30-59): returns 0 when none exists. */
 uint64_t fhe_generate_prime(size_t num_bits, uint64_t modulo, uint64_t upper_bound);

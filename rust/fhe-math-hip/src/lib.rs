@@ -720,6 +720,20 @@ impl HipParams {
         })?;
         Ok(Arc::new(Self { ptr: out }))
     }
+    /// The same for `BfvParametersBuilder::set_plaintext_modulus_biguint`: `t_limbs` are t's little-endian limbs
+    /// (`fhe_params_create_big_with_tables`; a t that fits one limb behaves as `with_tables`, t >= 2^256 is refused).
+    pub fn with_tables_big(device: i32, degree: usize, moduli: &[u64], t_limbs: &[u64],
+                           tables: &mut TablesFn<'_>) -> Result<Arc<Self>> {
+        let mut out: *mut ffi::FheParams = ptr::null_mut();
+        let mut fat: &mut TablesFn<'_> = tables;
+        check(unsafe {
+            ffi::fhe_params_create_big_with_tables(device as c_int, degree, moduli.len(), moduli.as_ptr(), t_limbs.as_ptr(),
+                t_limbs.len(), Some(tables_trampoline), &mut fat as *mut &mut TablesFn<'_> as *mut c_void, &mut out)
+        })?;
+        Ok(Arc::new(Self { ptr: out }))
+    }
+    /// W_t = ceil(bits(t) / 64): the limbs per plaintext coefficient of the `_big` calls (1 for a u64 t).
+    pub fn plaintext_limbs(&self) -> usize { unsafe { ffi::fhe_params_plaintext_limbs(self.ptr) } }
     /// `Multiplicator::default(rk)` (+ `enable_mod_switching`) at `level`; `rk = None`: `&ct * &ct`.
     /// (The engine cached every table `with_tables` supplied; the closure is not called again.)  The handle keeps
     /// the parameter set (and the key) alive.
@@ -831,6 +845,60 @@ impl HipEncoder {
         check(unsafe {
             ffi::fhe_bfv_measure_noise_dev(self.ptr, scaler.as_ptr(), s_ntt.as_ptr(), ct.buf.as_ptr(), ct.parts, m,
                                            out.as_mut_ptr(), ct.batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+}
+impl HipEncoder {
+    /// `PlaintextVec::try_encode` for `Vec<BigUint>` (plaintext_vec.rs:105-132) of a parameter set whose t exceeds 64
+    /// bits: `values` `[batch][nvalues][W_t]` limbs -> `[batch][L_level][N]` Ntt, `poly_ntt` or with `scaled` the Large
+    /// branch of `to_poly()` (plaintext.rs:172-197).  `Encoding::Simd` is unavailable (`fhe_bfv_encode_big_dev`).
+    pub fn encode_big_dev(&self, encoding: Encoding, scaled: bool, level: usize, values: &DeviceBuffer, nvalues: usize,
+                          stream: &Stream) -> Result<DeviceBuffer> {
+        if nvalues > self.degree {
+            return Err(HipError { status: status::TOO_MANY_VALUES, message: "TooManyValues".into() });
+        }
+        let wt = self.params.plaintext_limbs();
+        let batch = whole_batch("encode_big_dev values", values.len(), nvalues * wt)?;
+        let ctx = self.params.context_at_level(level)?;
+        let out = DeviceBuffer::alloc_on(ctx.device(), batch * ctx.poly_words(), stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_encode_big_dev(self.ptr, encoding as c_int, scaled as c_int, level, values.as_ptr(), nvalues,
+                                        out.as_mut_ptr(), batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+    /// The tail of `SecretKey::try_decrypt`'s Large branch alone (keys/secret_key.rs:238-250): PowerBasis residues over
+    /// the plaintext context `[batch][P][N]` -> `[batch][N][W_t]` limbs of ((x + t) mod Q_p) mod t
+    /// (`fhe_bfv_reduce_big_dev`).  `rows` is the row count the caller laid `polys` out with: anything but
+    /// `plain_rows()` is refused before the device reads a word.
+    pub fn reduce_big_dev(&self, polys: &DeviceBuffer, rows: usize, stream: &Stream) -> Result<DeviceBuffer> {
+        if rows == 0 || rows != self.plain_rows() {
+            return Err(shape_error("reduce_big_dev: one row per modulus of the plaintext context"));
+        }
+        let batch = whole_batch("reduce_big_dev polynomials", polys.len(), rows * self.degree)?;
+        let device = self.params.context_at_level(0)?.device();
+        let out = DeviceBuffer::alloc_on(device, (batch * self.degree * self.params.plaintext_limbs()).max(1), stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_reduce_big_dev(self.ptr, polys.as_ptr(), rows, out.as_mut_ptr(), batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+    /// P: the moduli of the parameter set's plaintext context (`fhe_encoder_plain_rows`).
+    pub fn plain_rows(&self) -> usize { unsafe { ffi::fhe_encoder_plain_rows(self.ptr) } }
+    /// `SecretKey::try_decrypt`, Large branch (keys/secret_key.rs:198-250), on a device-resident batch: as
+    /// `HipScaler::decrypt_dev` with `[batch][N][W_t]` limbs out (`fhe_bfv_decrypt_big_dev`).
+    pub fn decrypt_big_dev(&self, scaler: &HipScaler, s_ntt: &DeviceBuffer, ct: &DeviceCiphertexts, stream: &Stream)
+                           -> Result<DeviceBuffer> {
+        let from = scaler.from_ctx();
+        expect_len("decrypt_big_dev secret key", s_ntt.len(), from.poly_words())?;
+        if ct.rows != from.nmoduli() || ct.degree != from.degree() {
+            return Err(shape_error("decrypt_big_dev: the ciphertexts are not over the scaler's source context"));
+        }
+        let out = DeviceBuffer::alloc_on(from.device(), (ct.batch * ct.degree * self.params.plaintext_limbs()).max(1), stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_decrypt_big_dev(self.ptr, scaler.as_ptr(), s_ntt.as_ptr(), ct.buf.as_ptr(), ct.parts,
+                                         out.as_mut_ptr(), ct.batch, stream.as_ptr())
         })?;
         Ok(out)
     }
@@ -1278,6 +1346,29 @@ impl HipScaler {
         check(unsafe {
             ffi::fhe_mbfv_decrypt_dev(self.ptr, plaintext_modulus, ct.buf.as_ptr(), shares.as_ptr(), nshares, stride,
                                       out.as_mut_ptr(), ct.batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+}
+
+impl HipScaler {
+    /// `Plaintext::from_shares` with the Large tail, for `encoder`'s parameter set (t above 64 bits): as
+    /// `mbfv_decrypt_dev` with `[batch][N][W_t]` limbs out (`fhe_mbfv_decrypt_big_dev`).
+    pub fn mbfv_decrypt_big_dev(&self, encoder: &HipEncoder, ct: &DeviceCiphertexts, shares: &DeviceBuffer, nshares: usize,
+                                stream: &Stream) -> Result<DeviceBuffer> {
+        if ct.parts != 2 || ct.rows != self.from.nmoduli() || ct.degree != self.from.degree() {
+            return Err(shape_error("mbfv_decrypt_big_dev: two-part ciphertexts over the scaler's source context"));
+        }
+        if nshares == 0 {
+            return Err(shape_error("mbfv_decrypt_big_dev: NoShares"));
+        }
+        let stride = ct.batch * self.from.poly_words();
+        expect_len("mbfv_decrypt_big_dev shares", shares.len(), nshares * stride)?;
+        let wt = encoder.params.plaintext_limbs();
+        let out = DeviceBuffer::alloc_on(self.from.device(), (ct.batch * ct.degree * wt).max(1), stream)?;
+        check(unsafe {
+            ffi::fhe_mbfv_decrypt_big_dev(encoder.ptr, self.ptr, ct.buf.as_ptr(), shares.as_ptr(), nshares, stride,
+                                          out.as_mut_ptr(), ct.batch, stream.as_ptr())
         })?;
         Ok(out)
     }
