@@ -849,6 +849,42 @@ inline void launch_tile(const char *name, int lm, size_t grid, hipStream_t s, A.
     launch_k<KERNEL>(name, dim3((unsigned)grid), dim3(k::ntt_threads_c(lm)), k::lds_words(1u << lm) * sizeof(u64), s, args...);
 }
 
+// A whole-row launch (rows of at most one LDS tile, N <= 16384: the encoding, sampling, encryption, key-generation
+// and share kernels) over the moduli [0, rows) of a context.  It decides the instance -- integer (narrow: every modulus
+// below 2^60) or the F64 class of those rows (Ctx::f64_rows; `f64_on`: the caller's reading of the switch, taken once
+// for all launches of a call) -- and the twiddle table that goes with it.  A site names its kernel as a generic lambda
+// (lm, nrw, h) -> kernel_c<...<lm(), nrw(), h()>> and its own arguments: rows(name, grid, s, kernel, args...).
+constexpr const char *ENC_TILE = "unsupported encoding tile size";
+struct RowLaunch {
+    const Ctx &c;
+    bool narrow;
+    int hr;
+    RowLaunch(const Ctx &c_, size_t rows, bool f64_on) : c(c_), narrow(c_.below_2p60(0, rows)), hr(c_.f64_rows(0, rows, f64_on)) {}
+    bool f64() const { return hr > 0; }
+    const k::u64x2 *tw() const { return hr > 0 ? c.dtw_f() : c.dtw(); }
+    const k::u64x2 *itw() const { return hr > 0 ? c.ditw_f() : c.ditw(); }
+    template <class K, class... A>
+    void operator()(const char *name, size_t grid, hipStream_t s, K kernel, A... args) const {
+        with_tile(c.logn, ENC_TILE, narrow, hr, [&](auto lm, auto nrw, auto h) {
+            launch_tile<decltype(kernel(lm, nrw, h))::value>(name, lm, grid, s, args...);
+        });
+    }
+};
+
+// f(int_c<V>) for V == v in [LO, HI], f(int_c<0>) above: a compile-time count where an instance exists, else the
+// generic instance (run-time count, arrays in scratch); E_ARG with `what` below LO
+template <int LO, int HI, class F>
+inline void with_int_or_generic(size_t v, const char *what, F &&f) {
+    if (v > (size_t)HI) f(int_c<0>{});
+    else with_int<LO, HI>(v, what, std::forward<F>(f));
+}
+
+// f(b0, nb) for the launch groups [b0, b0 + nb) of a batch, `group` items each (the last one the rest)
+template <class F>
+inline void for_groups(size_t batch, size_t group, F &&f) {
+    for (size_t b0 = 0; b0 < batch; b0 += group) f(b0, std::min(group, batch - b0));
+}
+
 #if defined(FHE_LAB)
 // rejected kernel variants, selected by FHE_LAB_* environment switches in lab builds only (lab/lab_engine.hpp)
 struct Ksk;
@@ -2642,6 +2678,21 @@ inline std::vector<uint32_t> simd_index_map(size_t n, size_t logn) {
     return map;
 }
 
+// One level's [L] {delta_i, shoup}, delta_i = (-t)^-1 mod q_i, uploaded; t_mod(q) = t mod q
+template <class TMod>
+inline void push_delta(Encoder &e, const Ctx &c, TMod &&t_mod) {
+    std::vector<k::u64x2> d(c.L);
+    for (size_t i = 0; i < c.L; i++) {
+        const u64 q = c.moduli[i];
+        const u64 neg_t = (q - t_mod(q)) % q;
+        require(neg_t != 0, E_INVALID_MODULUS, "the plaintext modulus must be invertible modulo every q_i");
+        const u64 inv = powmod(neg_t, q - 2, q);
+        d[i] = k::u64x2{inv, shoup(inv, q)};
+    }
+    e.d_delta.push_back(std::make_unique<DevBuf<k::u64x2>>());
+    e.d_delta.back()->upload(d);
+}
+
 // `tctx`: the context over {t} (null when t admits no degree-N NTT).
 inline std::unique_ptr<Encoder> encoder_create(const Ctx &top, u64 t, std::unique_ptr<Ctx> tctx) {
     top.need_device();
@@ -2663,18 +2714,9 @@ inline std::unique_ptr<Encoder> encoder_create(const Ctx &top, u64 t, std::uniqu
     }
     for (const Ctx *c = &top; c; c = c->next.get()) {
         u64 qt = 1 % t;
-        std::vector<k::u64x2> d(c->L);
-        for (size_t i = 0; i < c->L; i++) {
-            const u64 q = c->moduli[i];
-            qt = mulmod(qt, q % t, t);
-            const u64 neg_t = (q - t % q) % q;
-            require(neg_t != 0, E_INVALID_MODULUS, "the plaintext modulus must be invertible modulo every q_i");
-            const u64 inv = powmod(neg_t, q - 2, q);
-            d[i] = k::u64x2{inv, shoup(inv, q)};
-        }
+        for (u64 q : c->moduli) qt = mulmod(qt, q % t, t);
+        push_delta(*e, *c, [&](u64 q) { return t % q; });
         e->q_mod_t.push_back(qt);
-        e->d_delta.push_back(std::make_unique<DevBuf<k::u64x2>>());
-        e->d_delta.back()->upload(d);
     }
     return e;
 }
@@ -2689,10 +2731,7 @@ inline k::u64x2 scale_pair(u64 w, u64 p, bool f64) {
     return r;
 }
 
-// The encoding, sampling, encryption and key-generation kernels work on whole rows (N <= 16384) through with_tile:
-// integer (NARROW: every modulus below 2^60) or F64 class hr (Ctx::f64_rows).
-constexpr const char *ENC_TILE = "unsupported encoding tile size";
-
+// The encoding, sampling, encryption and key-generation kernels work on whole rows (N <= 16384) through RowLaunch.
 // PlaintextVec::try_encode (F/bfv/plaintext_vec.rs:70-102) -> Plaintext::poly_ntt, or with `scaled` Plaintext::to_poly
 // (F/bfv/plaintext.rs:172-196): values [batch][nvalues] -> out [batch][L_level][N] Ntt.
 inline void encode(const Encoder &e, bool simd, bool scaled, size_t level, const u64 *values, size_t nvalues, u64 *out,
@@ -2715,17 +2754,15 @@ inline void encode(const Encoder &e, bool simd, bool scaled, size_t level, const
         trows = std::make_unique<WsGuard>(batch * e.n * sizeof(u64), s, true);
         const Ctx &tc = *e.tctx;
         if (e.logn <= 14) {
+            const RowLaunch rows(tc, 1, f64_on);
             // the inverse transform's N^-1 times q_mod_t for the scaled form (the same value mod t as multiplying after)
-            const int hr = tc.f64_rows(0, 1, f64_on);
             const NttTables &tt = tc.tab(0);
             const u64 c = scaled ? mulmod(tt.size_inv, qmt, e.t) : tt.size_inv;
             const u64 zc = mulmod(tt.zetas_inv[e.n - 2], c, e.t);
-            const k::u64x2 ns = scale_pair(c, e.t, hr > 0), zs = scale_pair(zc, e.t, hr > 0);
-            const k::u64x2 *itw = hr > 0 ? tc.ditw_f() : tc.ditw();
-            with_tile(e.logn, ENC_TILE, (e.t >> 60) == 0, hr, [&](auto lm, auto nrw, auto h) {
-                launch_tile<k::encode_simd_t_kernel<decltype(lm)::value, decltype(nrw)::value, decltype(h)::value>>(
-                    "encode_simd_t", lm, batch, s, values, (u64)nvalues, e.d_inv_map.p, trows->u(), tc.dmods(), itw, ns, zs);
-            });
+            const k::u64x2 ns = scale_pair(c, e.t, rows.f64()), zs = scale_pair(zc, e.t, rows.f64());
+            rows("encode_simd_t", batch, s,
+                 [](auto lm, auto nrw, auto h) { return kernel_c<k::encode_simd_t_kernel<lm(), nrw(), h()>>{}; },
+                 values, (u64)nvalues, e.d_inv_map.p, trows->u(), tc.dmods(), rows.itw(), ns, zs);
             ls.mul_t = 0;
         } else {   // rows larger than one LDS tile: the gather as a pass of its own, then launch_ntt
             const u64 total = (u64)batch * e.n;
@@ -2737,12 +2774,10 @@ inline void encode(const Encoder &e, bool simd, bool scaled, size_t level, const
         ls.stride = ls.nvalues = e.n;
     }
     if (qc->logn <= 14) {
-        const int hr = qc->f64_rows(0, qc->L, f64_on);
-        const k::u64x2 *tw = hr > 0 ? qc->dtw_f() : qc->dtw();
-        with_tile(qc->logn, ENC_TILE, qc->below_2p60(0, qc->L), hr, [&](auto lm, auto nrw, auto h) {
-            launch_tile<k::encode_lift_kernel<decltype(lm)::value, decltype(nrw)::value, decltype(h)::value>>(
-                "encode_lift", lm, batch * qc->L, s, ls, out, (uint32_t)qc->L, qc->dmods(), tw);
-        });
+        const RowLaunch rows(*qc, qc->L, f64_on);
+        rows("encode_lift", batch * qc->L, s,
+             [](auto lm, auto nrw, auto h) { return kernel_c<k::encode_lift_kernel<lm(), nrw(), h()>>{}; },
+             ls, out, (uint32_t)qc->L, qc->dmods(), rows.tw());
     } else {
         const u64 total = (u64)batch * qc->L * e.n;
         FHE_LAUNCH("encode_lift", k::encode_lift_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
@@ -2765,11 +2800,10 @@ inline void decode(const Encoder &e, bool simd, const u64 *coeffs, u64 *out, siz
     }
     const Ctx &tc = *e.tctx;
     if (e.logn <= 14) {
-        const int hr = tc.f64_rows(0, 1);
-        with_tile(e.logn, ENC_TILE, (e.t >> 60) == 0, hr, [&](auto lm, auto nrw, auto h) {
-            launch_tile<k::decode_simd_kernel<decltype(lm)::value, decltype(nrw)::value, decltype(h)::value>>(
-                "decode_simd", lm, batch, s, coeffs, e.d_map.p, out, tc.dmods(), hr > 0 ? tc.dtw_f() : tc.dtw());
-        });
+        const RowLaunch rows(tc, 1, !f64_disabled());
+        rows("decode_simd", batch, s,
+             [](auto lm, auto nrw, auto h) { return kernel_c<k::decode_simd_kernel<lm(), nrw(), h()>>{}; },
+             coeffs, e.d_map.p, out, tc.dmods(), rows.tw());
         return;
     }
     // rows larger than one LDS tile: reduce, launch_ntt, then the index map as a gather pass
@@ -2792,16 +2826,6 @@ inline u64 cbd_words_per_draw(size_t variance, u64 n) {
     return variance <= 16 ? (n * 4 * variance + 63) / 64 : 2 * n;
 }
 
-// sample_vec_cbd draws of ChaCha8Rng::from_seed(seeds[b]): `kdraws` consecutive draws of N = 2^logn samples ->
-// smp [batch][kdraws N]
-inline void cbd_sample(const uint8_t *seeds, size_t variance, size_t logn, size_t kdraws, int8_t *smp, size_t batch,
-                       hipStream_t s) {
-    const u64 n = 1ull << logn, ns = (u64)kdraws * n;
-    const u64 wpd = cbd_words_per_draw(variance, n);
-    FHE_LAUNCH("cbd_sample", k::cbd_sample_kernel, dim3(blocks_for(ns, k::CBD_THREADS), (unsigned)batch),
-               dim3(k::CBD_THREADS), k::CBD_SMEM_BYTES, s, seeds, smp, (uint32_t)variance, ns, (uint32_t)logn, wpd);
-}
-
 // (int8 scratch rounded up to whole 16-byte words)
 inline size_t small_bytes(size_t count) { return (count + 15) & ~(size_t)15; }
 
@@ -2814,6 +2838,33 @@ inline void small_lift(const Ctx &c, const int8_t *smp, u64 *x, size_t npolys, b
     if (to_ntt) launch_ntt(c, false, x, x, full_map(c, c.L), npolys, s);
 }
 
+// The draws of one launch group: `kdraws` consecutive sample_vec_cbd draws of N samples per item, from next_u64 word
+// `word0` of ChaCha8Rng::from_seed(seeds[b]) (key generation draws after the 32 bytes of K: word0 = 4), as int8
+// e() [nb][kdraws N]; for rows larger than one LDS tile (!whole) also x() [nb][kdraws][L][N], lifted and transformed.
+// The samples are secrets (SecretKey::random, the errors): both blocks are cleared before they return to the pool.
+struct GroupDraws {
+    WsGuard smp;
+    std::unique_ptr<WsGuard> xw;
+    GroupDraws(const Ctx &c, const uint8_t *seeds, size_t variance, size_t kdraws, u64 word0, size_t nb, bool whole,
+               hipStream_t s)
+        : smp(small_bytes(nb * kdraws * c.n), s, true) {
+        const u64 ns = (u64)kdraws * c.n;
+        const u64 wpd = cbd_words_per_draw(variance, c.n);
+        const dim3 grid(blocks_for(ns, k::CBD_THREADS), (unsigned)nb), block(k::CBD_THREADS);
+        if (word0)
+            FHE_LAUNCH("cbd_sample_at", k::cbd_sample_at_kernel, grid, block, k::CBD_AT_SMEM_BYTES, s, seeds, (int8_t *)smp.p,
+                       (uint32_t)variance, ns, (uint32_t)c.logn, wpd, word0);
+        else
+            FHE_LAUNCH("cbd_sample", k::cbd_sample_kernel, grid, block, k::CBD_SMEM_BYTES, s, seeds, (int8_t *)smp.p,
+                       (uint32_t)variance, ns, (uint32_t)c.logn, wpd);
+        if (whole) return;
+        xw = std::make_unique<WsGuard>(nb * kdraws * c.L * c.n * sizeof(u64), s, true);
+        small_lift(c, e(), xw->u(), nb * kdraws, true, s);
+    }
+    const int8_t *e() const { return (const int8_t *)smp.p; }
+    const u64 *x() const { return xw->u(); }
+};
+
 // Poly::small(ctx, variance, ChaCha8Rng::from_seed(seeds[b])): out [batch][L][N], PowerBasis or (to_ntt) Ntt.
 inline void sample_small(const Ctx &c, size_t variance, const uint8_t *seeds, bool to_ntt, u64 *out, size_t batch,
                          hipStream_t s) {
@@ -2821,20 +2872,15 @@ inline void sample_small(const Ctx &c, size_t variance, const uint8_t *seeds, bo
     check_variance(variance);
     if (!batch) return;
     require(batch <= 65535 && batch * c.L <= 0x7fffffffu, E_ARG, "sample_small: batch exceeds the grid limit");
-    // the samples are secrets (SecretKey::random, the errors): cleared before the block returns to the pool
-    WsGuard smp(small_bytes(batch * c.n), s, true);
-    int8_t *sp = (int8_t *)smp.p;
-    cbd_sample(seeds, variance, c.logn, 1, sp, batch, s);
+    const GroupDraws d(c, seeds, variance, 1, 0, batch, true, s);   // (larger rows: lifted into `out`, not into scratch)
     if (to_ntt && c.logn <= 14) {
-        const int hr = c.f64_rows(0, c.L);
-        with_tile(c.logn, ENC_TILE, c.below_2p60(0, c.L), hr, [&](auto lm, auto nrw, auto h) {
-            launch_tile<k::small_ntt_kernel<decltype(lm)::value, decltype(nrw)::value, decltype(h)::value>>(
-                "small_ntt", lm, batch * c.L, s, (const int8_t *)sp, out, (uint32_t)c.L, c.dmods(), hr > 0 ? c.dtw_f() :
-                c.dtw());
-        });
+        const RowLaunch rows(c, c.L, !f64_disabled());
+        rows("small_ntt", batch * c.L, s,
+             [](auto lm, auto nrw, auto h) { return kernel_c<k::small_ntt_kernel<lm(), nrw(), h()>>{}; },
+             d.e(), out, (uint32_t)c.L, c.dmods(), rows.tw());
         return;
     }
-    small_lift(c, sp, out, batch, to_ntt, s);
+    small_lift(c, d.e(), out, batch, to_ntt, s);
 }
 
 // Items per launch group of an encryption: the u64 scratch rows of one group (`rows_per_item` polynomials per item:
@@ -2856,39 +2902,31 @@ inline void encrypt_sk(const Ctx &c, size_t variance, const u64 *s_ntt, const ui
     check_variance(variance);
     if (!batch) return;
     require(batch * c.L <= 0x7fffffffu, E_ARG, "encrypt: batch exceeds the grid limit");
-    const bool f64_on = !f64_disabled();   // (read once per call: every transform of the call takes the same kind)
-    const int hr = c.f64_rows(0, c.L, f64_on);
+    const bool whole = c.logn <= 14;
+    const RowLaunch rows(c, c.L, !f64_disabled());   // (read once per call: every transform of the call takes the same kind)
     const u64 PL = (u64)c.L * c.n;
     // `a` is expanded into scratch: the unchanged seed_expand_kernel writes whole polynomials back to back
     // ([npolys][L][N]), so it cannot place them at out[b][1] (item stride 2 L N); the epilogue copies a into c1 while
     // it reads it for a (.) s.  Whole rows: groups of up to 1 GiB of `a` (seed_expand_kernel walks one polynomial per
     // workgroup and needs wide launches); larger rows: 256 MiB of `a` and transformed samples.
-    const size_t group = c.logn <= 14 ? encrypt_group(c, 1, batch, (size_t)1 << 30)
-                                      : encrypt_group(c, 2, batch, (size_t)256 << 20);
-    for (size_t b0 = 0; b0 < batch; b0 += group) {
-        const size_t nb = std::min(group, batch - b0);
+    const size_t group = whole ? encrypt_group(c, 1, batch, (size_t)1 << 30) : encrypt_group(c, 2, batch, (size_t)256 << 20);
+    for_groups(batch, group, [&](size_t b0, size_t nb) {
         const u64 *ptb = pt ? pt + (pt_shared ? 0 : b0 * PL) : nullptr;
+        const u64 pts = pt_shared ? (u64)0 : PL;
         u64 *outb = out + b0 * 2 * PL;
-        WsGuard smp(small_bytes(nb * c.n), s, true), a(nb * PL * sizeof(u64), s);
-        int8_t *sp = (int8_t *)smp.p;
-        cbd_sample(e_seeds + b0 * 32, variance, c.logn, 1, sp, nb, s);
+        const GroupDraws d(c, e_seeds + b0 * 32, variance, 1, 0, nb, whole, s);
+        WsGuard a(nb * PL * sizeof(u64), s);
         polys_from_seeds(c, a_seeds + b0 * 32, a.u(), nb, s);
-        if (c.logn <= 14) {
-            with_tile(c.logn, ENC_TILE, c.below_2p60(0, c.L), hr, [&](auto lm, auto nrw, auto h) {
-                launch_tile<k::encrypt_sk_kernel<decltype(lm)::value, decltype(nrw)::value, decltype(h)::value>>(
-                    "encrypt_sk", lm, nb * c.L, s, (const int8_t *)sp, (const u64 *)a.u(), s_ntt, ptb, pt_shared ? (u64)0 : PL,
-                    outb, (uint32_t)c.L, c.dmods(), hr > 0 ? c.dtw_f() : c.dtw());
-            });
-            continue;
-        }
-        // rows larger than one LDS tile: lift, launch_ntt, then the epilogue as a pass of its own
-        WsGuard x(nb * PL * sizeof(u64), s, true);
+        if (whole)
+            return rows("encrypt_sk", nb * c.L, s,
+                        [](auto lm, auto nrw, auto h) { return kernel_c<k::encrypt_sk_kernel<lm(), nrw(), h()>>{}; },
+                        d.e(), (const u64 *)a.u(), s_ntt, ptb, pts, outb, (uint32_t)c.L, c.dmods(), rows.tw());
+        // rows larger than one LDS tile: the epilogue as a pass of its own over the transformed samples
         const u64 total = (u64)nb * PL;
-        small_lift(c, sp, x.u(), nb, true, s);
         FHE_LAUNCH("encrypt_combine", k::encrypt_combine_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS),
-                   0, s, (const u64 *)x.u(), (const u64 *)a.u(), s_ntt, ptb, pt_shared ? (u64)0 : PL, outb, (uint32_t)c.L,
-                   c.dmods(), (uint32_t)c.logn, 0u, total);
-    }
+                   0, s, d.x(), (const u64 *)a.u(), s_ntt, ptb, pts, outb, (uint32_t)c.L, c.dmods(), (uint32_t)c.logn, 0u,
+                   total);
+    });
 }
 
 // PublicKey::try_encrypt (F/bfv/keys/public_key.rs:47-97) with u, e1, e2 three consecutive Poly::small draws of
@@ -2900,33 +2938,27 @@ inline void encrypt_pk(const Ctx &c, size_t variance, const u64 *pk, const uint8
     check_variance(variance);
     if (!batch) return;
     require(batch * c.L <= 0x7fffffffu, E_ARG, "encrypt: batch exceeds the grid limit");
-    const bool f64_on = !f64_disabled();
-    const int hr = c.f64_rows(0, c.L, f64_on);
+    const bool whole = c.logn <= 14;
+    const RowLaunch rows(c, c.L, !f64_disabled());
     const u64 PL = (u64)c.L * c.n;
-    const size_t group = c.logn <= 14 ? 65535 : encrypt_group(c, 3, batch, (size_t)256 << 20);
-    for (size_t b0 = 0; b0 < batch; b0 += group) {
-        const size_t nb = std::min(group, batch - b0);
+    const size_t group = whole ? 65535 : encrypt_group(c, 3, batch, (size_t)256 << 20);
+    for_groups(batch, group, [&](size_t b0, size_t nb) {
         const u64 *ptb = pt ? pt + (pt_shared ? 0 : b0 * PL) : nullptr;
+        const u64 pts = pt_shared ? (u64)0 : PL;
         u64 *outb = out + b0 * 2 * PL;
-        WsGuard smp(small_bytes(nb * 3 * c.n), s, true);
-        int8_t *sp = (int8_t *)smp.p;
-        cbd_sample(seeds + b0 * 32, variance, c.logn, 3, sp, nb, s);
-        if (c.logn <= 14) {
-            with_tile(c.logn, ENC_TILE, c.below_2p60(0, c.L), hr, [&](auto lm, auto nrw, auto h) {
-                for (uint32_t stage = 0; stage < 3; stage++)
-                    launch_tile<k::encrypt_pk_kernel<decltype(lm)::value, decltype(nrw)::value, decltype(h)::value>>(
-                        "encrypt_pk", lm, nb * c.L, s, (const int8_t *)sp, pk, ptb, pt_shared ? (u64)0 : PL, outb,
-                        (uint32_t)c.L, c.dmods(), hr > 0 ? c.dtw_f() : c.dtw(), stage);
-            });
-            continue;
+        const GroupDraws d(c, seeds + b0 * 32, variance, 3, 0, nb, whole, s);
+        if (whole) {
+            for (uint32_t stage = 0; stage < 3; stage++)
+                rows("encrypt_pk", nb * c.L, s,
+                     [](auto lm, auto nrw, auto h) { return kernel_c<k::encrypt_pk_kernel<lm(), nrw(), h()>>{}; },
+                     d.e(), pk, ptb, pts, outb, (uint32_t)c.L, c.dmods(), rows.tw(), stage);
+            return;
         }
-        WsGuard x(nb * 3 * PL * sizeof(u64), s, true);
         const u64 total = (u64)nb * PL;
-        small_lift(c, sp, x.u(), nb * 3, true, s);
         FHE_LAUNCH("encrypt_combine", k::encrypt_combine_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS),
-                   0, s, (const u64 *)x.u(), (const u64 *)nullptr, pk, ptb, pt_shared ? (u64)0 : PL, outb, (uint32_t)c.L,
-                   c.dmods(), (uint32_t)c.logn, 1u, total);
-    }
+                   0, s, d.x(), (const u64 *)nullptr, pk, ptb, pts, outb, (uint32_t)c.L, c.dmods(), (uint32_t)c.logn, 1u,
+                   total);
+    });
 }
 
 // ------------------------------------------------------------------ key generation ----
@@ -2977,49 +3009,36 @@ inline std::vector<std::unique_ptr<Ksk>> ksk_generate(const Ctx &ct, const Ctx &
     FHE_LAUNCH("ksk_consts", k::ksk_consts_kernel, dim3(blocks_for(nd * Lk, 64)), dim3(64), 0, s, kc.dmods(),
                (uint32_t)nd, (uint32_t)Lk, (uint32_t)lb, g, rq);
     const bool whole = kc.logn <= 14;
-    const bool f64_on = !f64_disabled();   // (read once per call: every transform of the call takes the same kind)
-    const int hr = kc.f64_rows(0, Lk, f64_on);
-    const u64 wpd = cbd_words_per_draw(variance, N);
+    const RowLaunch rows(kc, Lk, !f64_disabled());   // (read once per call: every transform of the call takes the same kind)
     // groups: at most KG_KEYS keys (the output table travels in the kernel arguments) and 1 GiB of c1 scratch (256 MiB
     // of c1 and transformed errors for larger rows), split into groups of equal size
     const size_t group = whole ? encrypt_group(kc, nd, nkeys, (size_t)1 << 30, k::KG_KEYS)
                                : encrypt_group(kc, 2 * nd, nkeys, (size_t)256 << 20, k::KG_KEYS);
     require(group * nd * Lk <= 0x7fffffffu, E_ARG, "ksk_generate: a launch group exceeds the grid limit");
-    for (size_t b0 = 0; b0 < nkeys; b0 += group) {
-        const size_t nb = std::min(group, nkeys - b0);
+    for_groups(nkeys, group, [&](size_t b0, size_t nb) {
         k::KskOutTable tab{};
         for (size_t b = 0; b < nb; b++) {
             const Ksk &kk = *keys[b0 + b];
             tab.k[b] = k::KskOut{kk.c0.p, kk.c0s.p, kk.c1.p, kk.c1s.p, kk.c0f.p, kk.c1f.p};
         }
         WsGuard ds(nb * nd * 32, s), c1(nb * PK * sizeof(u64), s);
-        WsGuard smp(small_bytes(nb * nd * N), s, true);   // the errors: secrets, cleared before they return to the pool
-        int8_t *sp = (int8_t *)smp.p;
         const uint8_t *sd = seeds + b0 * 32;
         FHE_LAUNCH("ksk_seeds", k::ksk_seeds_kernel, dim3(blocks_for(nb * nd, 64)), dim3(64), 0, s, sd,
                    seeds_out ? seeds_out + b0 * 32 : nullptr, (uint8_t *)ds.p, (uint32_t)nd, (uint32_t)(nb * nd));
-        const u64 ns = (u64)nd * N;
-        FHE_LAUNCH("cbd_sample_at", k::cbd_sample_at_kernel, dim3(blocks_for(ns, k::CBD_THREADS), (unsigned)nb),
-                   dim3(k::CBD_THREADS), k::CBD_AT_SMEM_BYTES, s, sd, sp, (uint32_t)variance, ns, (uint32_t)kc.logn, wpd,
-                   (u64)4);
+        const GroupDraws d(kc, sd, variance, nd, 4, nb, whole, s);   // the errors: nd draws per key, after K
         polys_from_seeds(kc, (const uint8_t *)ds.p, c1.u(), nb * nd, s);
         const u64 *fb = from_ntt + b0 * Lk * N;
-        if (whole) {
-            with_tile(kc.logn, ENC_TILE, kc.below_2p60(0, Lk), hr, [&](auto lm, auto nrw, auto h) {
-                launch_tile<k::ksk_gen_kernel<decltype(lm)::value, decltype(nrw)::value, decltype(h)::value>>(
-                    "ksk_gen", lm, nb * nd * Lk, s, (const int8_t *)sp, (const u64 *)c1.u(), s_ntt, fb, (const u64 *)g, (const
-                    k::u64x2 *)rq, tab, (uint32_t)nd, (uint32_t)Lk, (uint32_t)wf, kc.dmods(), hr > 0 ? kc.dtw_f() : kc.dtw());
-            });
-            continue;
-        }
-        // rows larger than one LDS tile: lift, launch_ntt, then the epilogue as a pass of its own
-        WsGuard x(nb * PK * sizeof(u64), s, true);
+        if (whole)
+            return rows("ksk_gen", nb * nd * Lk, s,
+                        [](auto lm, auto nrw, auto h) { return kernel_c<k::ksk_gen_kernel<lm(), nrw(), h()>>{}; },
+                        d.e(), (const u64 *)c1.u(), s_ntt, fb, (const u64 *)g, (const k::u64x2 *)rq, tab, (uint32_t)nd,
+                        (uint32_t)Lk, (uint32_t)wf, kc.dmods(), rows.tw());
+        // rows larger than one LDS tile: the epilogue as a pass of its own over the transformed errors
         const u64 total = (u64)nb * PK;
-        small_lift(kc, sp, x.u(), nb * nd, true, s);
         FHE_LAUNCH("ksk_combine", k::ksk_combine_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
-                   (const u64 *)x.u(), (const u64 *)c1.u(), s_ntt, fb, (const u64 *)g, (const k::u64x2 *)rq, tab,
-                   (uint32_t)nd, (uint32_t)Lk, (uint32_t)wf, kc.dmods(), (uint32_t)kc.logn, total);
-    }
+                   d.x(), (const u64 *)c1.u(), s_ntt, fb, (const u64 *)g, (const k::u64x2 *)rq, tab, (uint32_t)nd,
+                   (uint32_t)Lk, (uint32_t)wf, kc.dmods(), (uint32_t)kc.logn, total);
+    });
     return keys;
 }
 
@@ -3063,14 +3082,13 @@ inline void galois_from(const Ctx &ct, const Ctx &kc, const u64 *s_ntt, const si
     std::unique_ptr<WsGuard> t;   // (the substituted rows over the ciphertext context, when they still switch up)
     if (kc.L != ct.L) t = std::make_unique<WsGuard>(nkeys * pc * sizeof(u64), s, true);
     u64 *dst = t ? t->u() : out;
-    for (size_t b0 = 0; b0 < nkeys; b0 += k::KG_KEYS) {
-        const size_t nb = std::min<size_t>(k::KG_KEYS, nkeys - b0);
+    for_groups(nkeys, k::KG_KEYS, [&](size_t b0, size_t nb) {
         k::KgExps e{};
         for (size_t b = 0; b < nb; b++) e.e[b] = (uint32_t)(exponents[b0 + b] % (2 * ct.n));
         const u64 total = (u64)nb * pc;
         FHE_LAUNCH("galois_from", k::galois_from_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
                    s_ntt, dst + b0 * pc, e, (uint32_t)ct.L, (uint32_t)ct.logn, total);
-    }
+    });
     if (t) switch_up_ntt(ct, kc, t->u(), out, nkeys, s);
 }
 
@@ -3093,23 +3111,14 @@ inline void mbfv_shares(const Ctx &c, size_t variance, const uint8_t *seeds, siz
     if (!batch) return;
     require(batch * edraws * c.L <= 0x7fffffffu, E_ARG, "mbfv: batch exceeds the grid limit");
     const bool whole = c.logn <= 14;
-    const bool f64_on = !f64_disabled();   // (read once per call: every transform of the call takes the same kind)
-    const int hr = c.f64_rows(0, c.L, f64_on);
+    const RowLaunch rows(c, c.L, !f64_disabled());   // (read once per call: every transform of the call takes the same kind)
     const u64 PL = (u64)c.L * c.n;
     const size_t group = whole ? encrypt_group(c, 1, batch, ~(size_t)0 >> 1) : encrypt_group(c, edraws, batch, (size_t)256 << 20);
-    for (size_t b0 = 0; b0 < batch; b0 += group) {
-        const size_t nb = std::min(group, batch - b0);
-        WsGuard smp(small_bytes(nb * edraws * c.n), s, true);
-        int8_t *sp = (int8_t *)smp.p;
-        cbd_sample(seeds + b0 * 32, variance, c.logn, edraws, sp, nb, s);
-        std::unique_ptr<WsGuard> x;   // rows larger than one LDS tile: lift, launch_ntt, then the epilogues as passes
-        if (!whole) {
-            x = std::make_unique<WsGuard>(nb * edraws * PL * sizeof(u64), s, true);
-            small_lift(c, sp, x->u(), nb * edraws, true, s);
-        }
+    for_groups(batch, group, [&](size_t b0, size_t nb) {
+        const GroupDraws d(c, seeds + b0 * 32, variance, edraws, 0, nb, whole, s);
         for (const MbfvPart &pt : parts) {
             k::MbfvArgs g = pt.g;
-            g.e = sp;
+            g.e = d.e();
             g.edraws = (uint32_t)edraws;
             g.rows = (uint32_t)c.L;
             g.A += b0 * g.a_stride;
@@ -3118,20 +3127,21 @@ inline void mbfv_shares(const Ctx &c, size_t variance, const uint8_t *seeds, siz
             if (g.Y) g.Y += b0 * g.s_stride;
             u64 *outb = pt.out + b0 * g.k * PL;
             if (whole) {
-                with_tile(c.logn, ENC_TILE, c.below_2p60(0, c.L), hr, [&](auto lm, auto nrw, auto h) {
-                    with_int<0, 2>((size_t)pt.form, "unknown share form", [&](auto form) {
-                        launch_tile<k::mbfv_share_kernel<decltype(lm)::value, decltype(nrw)::value, decltype(h)::value,
-                                                         decltype(form)::value>>(
-                            "mbfv_share", lm, nb * g.k * c.L, s, g, outb, c.dmods(), hr > 0 ? c.dtw_f() : c.dtw());
-                    });
+                with_int<0, 2>((size_t)pt.form, "unknown share form", [&](auto form) {
+                    rows("mbfv_share", nb * g.k * c.L, s,
+                         [](auto lm, auto nrw, auto h) {
+                             return kernel_c<k::mbfv_share_kernel<lm(), nrw(), h(), decltype(form)::value>>{};
+                         },
+                         g, outb, c.dmods(), rows.tw());
                 });
                 continue;
             }
+            // rows larger than one LDS tile: the epilogues as passes over the transformed draws
             const u64 total = (u64)nb * g.k * PL;
             FHE_LAUNCH("mbfv_share", k::mbfv_share_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
-                       (const u64 *)x->u(), g, (uint32_t)pt.form, outb, c.dmods(), (uint32_t)c.logn, total);
+                       d.x(), g, (uint32_t)pt.form, outb, c.dmods(), (uint32_t)c.logn, total);
         }
-    }
+    });
 }
 
 // words between the secrets of consecutive items: none when one party serves the batch, else a level-0 secret (the
@@ -3230,12 +3240,11 @@ inline void mbfv_sum(const Ctx &c, const u64 *shares, size_t nshares, u64 share_
     if (!npolys) return;
     const u64 PL = (u64)c.L * c.n;
     require(PL / 2 <= 0x7fffffffu, E_ARG, "mbfv: polynomial exceeds the grid limit");
-    for (size_t j0 = 0; j0 < npolys; j0 += 65535) {   // (the polynomial is the grid's second dimension)
-        const size_t nj = std::min<size_t>(65535, npolys - j0);
+    for_groups(npolys, 65535, [&](size_t j0, size_t nj) {   // (the polynomial is the grid's second dimension)
         FHE_LAUNCH("mbfv_sum", k::mbfv_sum_kernel, dim3(blocks_for(PL / 2, EW_THREADS), (unsigned)nj), dim3(EW_THREADS), 0, s,
                    shares + j0 * PL, (uint32_t)nshares, share_stride, base ? base + j0 * base_stride : nullptr, base_stride,
                    out + j0 * PL, c.dmods(), (uint32_t)c.logn, (uint32_t)(PL / 2));
-    }
+    });
 }
 
 // Plaintext::from_shares (F/mbfv/secret_key_switch.rs:145-186): c0 + the sum of the decryption shares in one launch,
@@ -3315,22 +3324,18 @@ inline void launch_lift(const Ctx &c, const u64 *polys, const k::LiftSub &sub, u
     const dim3 grid((unsigned)(batch * nblk)), block(k::LIFT_THREADS);
     const size_t lds = BITS ? k::LIFT_SMEM_BYTES : 0;
     const char *name = BITS ? "centered_bits" : "lift";
-    if (c.L <= (size_t)LIFT_LC_MAX)
-        with_int<1, LIFT_LC_MAX>(c.L, "lift: no moduli", [&](auto lc) {
-            launch_k<k::lift_kernel<decltype(lc)::value, BITS>>(name, grid, block, lds, s, polys, tab, sub, out, partial,
-                                                                (uint32_t)c.L, (uint32_t)w, (uint32_t)c.logn, (uint32_t)nblk,
-                                                                (uint32_t)batch);
-        });
-    else
-        launch_k<k::lift_kernel<0, BITS>>(name, grid, block, lds, s, polys, tab, sub, out, partial, (uint32_t)c.L, (uint32_t)w,
-                                          (uint32_t)c.logn, (uint32_t)nblk, (uint32_t)batch);
+    with_int_or_generic<1, LIFT_LC_MAX>(c.L, "lift: no moduli", [&](auto lc) {
+        launch_k<k::lift_kernel<decltype(lc)::value, BITS>>(name, grid, block, lds, s, polys, tab, sub, out, partial,
+                                                            (uint32_t)c.L, (uint32_t)w, (uint32_t)c.logn, (uint32_t)nblk,
+                                                            (uint32_t)batch);
+    });
 }
 
 // RnsContext::lift per coefficient (M/rns/mod.rs:138-143): polys [batch][L][N] -> out [batch][N][W] limbs.
 inline void poly_lift(const Ctx &c, const u64 *polys, u64 *out, size_t batch, hipStream_t s) {
     c.need_device();
     if (!batch) return;
-    launch_lift<false>(c, polys, k::LiftSub{nullptr, nullptr, 0, k::u64x2{0, 0}}, out, nullptr, lift_limbs(c), batch, s);
+    launch_lift<false>(c, polys, k::lift_sub_none(), out, nullptr, lift_limbs(c), batch, s);
 }
 
 // max over the coefficients of min(bits(x), bits(q - x)) (secret_key.rs:88-95) of polys [batch][L][N] minus, when
@@ -3375,20 +3380,11 @@ inline std::unique_ptr<Encoder> encoder_create_big(const Ctx &top, const BigUint
     require(e->plain->lift_w <= 2 * e->wt && e->plain->L >= e->wt, E_INVALID_MODULUS,
             "the plaintext context is too long for the plaintext modulus");
     for (const Ctx *c = &top; c; c = c->next.get()) {
-        std::vector<k::u64x2> d(c->L);
-        for (size_t i = 0; i < c->L; i++) {
-            const u64 q = c->moduli[i];
-            const u64 neg_t = (q - t.mod_u64(q)) % q;
-            require(neg_t != 0, E_INVALID_MODULUS, "the plaintext modulus must be invertible modulo every q_i");
-            const u64 inv = powmod(neg_t, q - 2, q);
-            d[i] = k::u64x2{inv, shoup(inv, q)};
-        }
+        push_delta(*e, *c, [&](u64 q) { return t.mod_u64(q); });
         const BigUint qt = ctx_modulus(*c) % t;
         std::vector<u64> limbs(e->wt);
         for (size_t i = 0; i < e->wt; i++) limbs[i] = qt.limb(i);
         e->q_mod_t_big.push_back(limbs);
-        e->d_delta.push_back(std::make_unique<DevBuf<k::u64x2>>());
-        e->d_delta.back()->upload(d);
     }
     return e;
 }
@@ -3444,14 +3440,10 @@ inline void reduce_big(const Encoder &e, const u64 *polys, size_t rows, u64 *out
     with_int<2, k::BIGT_WMAX>(e.wt, "reduce: unsupported plaintext limbs", [&](auto w) {
         constexpr int WT = decltype(w)::value;
         const k::BigT<WT> bt = bigt_consts<WT>(e);
-        if (pc.L <= (size_t)BIGT_PC_MAX)
-            with_int<WT, BIGT_PC_MAX>(pc.L, "reduce: plaintext context shorter than the plaintext modulus", [&](auto p) {
-                launch_k<k::bigt_tail_kernel<decltype(p)::value, WT>>("bigt_tail", grid, block, 0, s, polys, tab, bt, out,
-                                                                      (uint32_t)pc.L, (uint32_t)pc.logn, (uint32_t)nblk);
-            });
-        else
-            launch_k<k::bigt_tail_kernel<0, WT>>("bigt_tail", grid, block, 0, s, polys, tab, bt, out, (uint32_t)pc.L,
-                                                 (uint32_t)pc.logn, (uint32_t)nblk);
+        with_int_or_generic<WT, BIGT_PC_MAX>(pc.L, "reduce: plaintext context shorter than the plaintext modulus", [&](auto p) {
+            launch_k<k::bigt_tail_kernel<decltype(p)::value, WT>>("bigt_tail", grid, block, 0, s, polys, tab, bt, out,
+                                                                  (uint32_t)pc.L, (uint32_t)pc.logn, (uint32_t)nblk);
+        });
     });
 }
 // Scaler::scale (t / Q_level) of the PowerBasis phase into the plaintext context, then the tail: out [batch][N][W_t]
@@ -3518,7 +3510,7 @@ inline void measure_noise_big(const Encoder &e, const Scaler &sc, size_t level, 
     encode_big(e, false, true, level, m, e.n, mp.u(), batch, s);
     ew_op(cc, ph.u(), mp.u(), batch, k::EW_SUB, s);
     launch_ntt(cc, true, ph.u(), ph.u(), full_map(cc, cc.L), batch, s);
-    centered_bits(cc, ph.u(), k::LiftSub{nullptr, nullptr, 0, k::u64x2{0, 0}}, noise_bits, batch, s);
+    centered_bits(cc, ph.u(), k::lift_sub_none(), noise_bits, batch, s);
 }
 
 // SecretKey::measure_noise (F/bfv/keys/secret_key.rs:55-98): the phase in PowerBasis minus Plaintext::to_poly of m --

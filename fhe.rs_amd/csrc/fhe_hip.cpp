@@ -1720,7 +1720,7 @@ fhe_status fhe_poly_centered_bits_dev(const fhe_ctx *ctx, const uint64_t *polys,
             need(out_bits, "out_bits");
         }
         set_device(c);
-        centered_bits(c, polys, k::LiftSub{nullptr, nullptr, 0, k::u64x2{0, 0}}, out_bits, batch, as_stream(stream));
+        centered_bits(c, polys, k::lift_sub_none(), out_bits, batch, as_stream(stream));
     });
 }
 fhe_status fhe_bfv_measure_noise_dev(const fhe_encoder *enc, const fhe_scaler *sc, const uint64_t *s_ntt, const uint64_t *ct,

@@ -147,36 +147,6 @@ __global__ void __launch_bounds__(BIGT_THREADS)
     }
 }
 
-// Garner's digits of the residues d[0 .. L) in place, then Horner's limbs x[0 .. L): lift_kernel's arithmetic on the
-// table kernels_noise.hpp describes.
-template <int LA, int UF>
-__device__ __forceinline__ void bigt_garner_horner(u64 (&d)[LA], u64 (&x)[LA], const u64 *__restrict__ tab, const int L) {
-#pragma unroll UF
-    for (int i = 1; i < L; i++) {
-        const u64 q = tab[i], mq = tab[L + i];
-        const u64 *pr = tab + lift_pairs_at(L) + (uint32_t)(i * (i - 1));
-        u64 t = d[i];
-#pragma unroll UF
-        for (int j = 0; j < i; j++) t = mul_shoup_lazy(t + mq - d[j], pr[2 * j], pr[2 * j + 1], q);
-        d[i] = csub(t, q);
-    }
-    x[0] = d[L - 1];
-#pragma unroll UF
-    for (int i = L - 2; i >= 0; i--) {
-        const u64 q = tab[i];
-        const int len = L - 1 - i;
-        u64 carry = d[i];
-#pragma unroll UF
-        for (int k = 0; k < len; k++) {
-            const u64 hi = mulhi64(x[k], q);
-            const u64 lo = x[k] * q + carry;
-            carry = hi + (lo < carry ? 1 : 0);
-            x[k] = lo;
-        }
-        x[len] = carry;
-    }
-}
-
 // One thread per coefficient: polys [batch][P][N] PowerBasis over the plaintext context (tab: its lift table) ->
 // out [batch][N][WT], ((x + t) mod Q_p) mod t.  Q_p has at most WT + 2 <= 2 WT limbs (bits(Q_p) < bits(t) + 122), so the
 // sum is within bigt_reduce's range.  PC = 0: run-time P up to LIFT_LMAX, arrays in scratch.
@@ -198,7 +168,7 @@ __global__ void __launch_bounds__(BIGT_THREADS)
     u64 d[LA], x[LA];
 #pragma unroll UF
     for (int i = 0; i < P; i++) d[i] = src[(u64)i << logn];
-    bigt_garner_horner<LA, UF>(d, x, tab, P);
+    garner_horner<LA, UF>(d, x, tab, P);   // (kernels_noise.hpp)
 
     // s = x + t (carry cs), df = s - Q_p (borrow); w = s >= Q_p ? df : s, kept in d
     const u64 *ql = tab + lift_q_at(P);

@@ -7,6 +7,8 @@
 //   encrypt_pk_kernel       u (.) pk0 + e1 + m, u (.) pk1 + e2 (three stages)          F/bfv/keys/public_key.rs:47-97
 //   small_lift_ew_kernel / encrypt_combine_ew_kernel   the element-wise forms, for rows larger than one LDS tile
 //                           (N >= 32768) and for PowerBasis samples, around launch_ntt
+//                           (both forms of an epilogue take their steps from encrypt_sk_combine / encrypt_pk_combine /
+//                           encrypt_plus)
 // The samples are secrets: every address and branch below depends on indices and parameters only, never on a sample,
 // a key or a plaintext word (the lift of a negative sample is a select, the products are the branch-free mul_mod).
 #pragma once
@@ -153,6 +155,20 @@ __global__ void __launch_bounds__(ntt_threads_c(LOGM), 4)
                                         [&](uint32_t i, u64 x, u64 y) { dst[i >> 1] = u64x2{x, y}; });
 }
 
+// The per-coefficient steps of the encryptions: the whole-row kernels call these on the .x and .y of a pair (the
+// plaintext addend under their uniform branch on its pointer), encrypt_combine_ew_kernel once per word.  For secret-key
+// encryption that is the epilogue but for the plaintext addend.  For public-key encryption only the single steps are
+// shared, not the epilogue: its composition c0 = u pk0 + e1 + m, c1 = u pk1 + e2 is spread over encrypt_pk_kernel's three
+// stages and written out in encrypt_combine_ew_kernel (one combine returning {c0, c1} cost that kernel a VGPR).
+// SecretKey::encrypt_poly: c0 = e - a s, before the plaintext
+__device__ __forceinline__ u64 encrypt_sk_combine(u64 e, u64 a, u64 s, const DevMod &md) {
+    return sub_mod(e, mul_mod(a, s, md), md.p);
+}
+// PublicKey::try_encrypt, stage 0: the partial u pk_j, before its error (and the plaintext)
+__device__ __forceinline__ u64 encrypt_pk_combine(u64 u, u64 key, const DevMod &md) { return mul_mod(u, key, md); }
+// a further addend of a ciphertext part: the plaintext word, or stage 1 / 2's error on the partial
+__device__ __forceinline__ u64 encrypt_plus(u64 c, u64 v, const DevMod &md) { return add_mod(c, v, md.p); }
+
 // SecretKey::encrypt_poly: one workgroup per (item, row).  e [batch][N] int8; a [batch][rows][N] (seed_expand_kernel's
 // rows); s_ntt [rows][N]; pt [batch][rows][N] (pt_stride 0: one for the batch; null: the zero plaintext).
 // out[b][0][r] = NTT(e) - a (.) s + pt, out[b][1][r] = a.
@@ -175,11 +191,10 @@ __global__ void __launch_bounds__(ntt_threads_c(LOGM), 4)
     u64x2 *o1 = o0 + (u64)rows * M / 2;
     small_row_ntt<LOGM, T, NARROW, F64>(lds, tw + (u64)r * M, md, tid, e + (u64)b * M, [&](uint32_t i, u64 x, u64 y) {
         const u64x2 av = ar[i >> 1], sv = sr[i >> 1];
-        u64x2 c{sub_mod(x, mul_mod(av.x, sv.x, md), md.p), sub_mod(y, mul_mod(av.y, sv.y, md), md.p)};
+        u64x2 c{encrypt_sk_combine(x, av.x, sv.x, md), encrypt_sk_combine(y, av.y, sv.y, md)};
         if (pr) {
             const u64x2 m = pr[i >> 1];
-            c.x = add_mod(c.x, m.x, md.p);
-            c.y = add_mod(c.y, m.y, md.p);
+            c = u64x2{encrypt_plus(c.x, m.x, md), encrypt_plus(c.y, m.y, md)};
         }
         o0[i >> 1] = c;
         o1[i >> 1] = av;
@@ -211,8 +226,8 @@ __global__ void __launch_bounds__(ntt_threads_c(LOGM), 4)
         const u64x2 *k1 = k0 + (u64)rows * M / 2;
         small_row_ntt<LOGM, T, NARROW, F64>(lds, tw + (u64)r * M, md, tid, src, [&](uint32_t i, u64 x, u64 y) {
             const u64x2 p0 = k0[i >> 1], p1 = k1[i >> 1];
-            o0[i >> 1] = u64x2{mul_mod(x, p0.x, md), mul_mod(y, p0.y, md)};
-            o1[i >> 1] = u64x2{mul_mod(x, p1.x, md), mul_mod(y, p1.y, md)};
+            o0[i >> 1] = u64x2{encrypt_pk_combine(x, p0.x, md), encrypt_pk_combine(y, p0.y, md)};
+            o1[i >> 1] = u64x2{encrypt_pk_combine(x, p1.x, md), encrypt_pk_combine(y, p1.y, md)};
         });
         return;
     }
@@ -220,12 +235,10 @@ __global__ void __launch_bounds__(ntt_threads_c(LOGM), 4)
     const u64x2 *pr = stage == 1 && pt ? reinterpret_cast<const u64x2 *>(pt + (u64)b * pt_stride + (u64)r * M) : nullptr;
     small_row_ntt<LOGM, T, NARROW, F64>(lds, tw + (u64)r * M, md, tid, src, [&](uint32_t i, u64 x, u64 y) {
         u64x2 c = o[i >> 1];
-        c.x = add_mod(c.x, x, md.p);
-        c.y = add_mod(c.y, y, md.p);
-        if (pr) {
+        c = u64x2{encrypt_plus(c.x, x, md), encrypt_plus(c.y, y, md)};
+        if (pr) {   // (stage 1 with a plaintext: the addend of c0)
             const u64x2 m = pr[i >> 1];
-            c.x = add_mod(c.x, m.x, md.p);
-            c.y = add_mod(c.y, m.y, md.p);
+            c = u64x2{encrypt_plus(c.x, m.x, md), encrypt_plus(c.y, m.y, md)};
         }
         o[i >> 1] = c;
     });
@@ -258,11 +271,11 @@ __global__ void encrypt_combine_ew_kernel(const u64 *__restrict__ x, const u64 *
     if (pk) {
         const u64 *xb = x + 3 * b * pl + off;
         const u64 u = xb[0];
-        o[0] = add_mod(add_mod(mul_mod(u, key[off], md), xb[pl], md.p), m, md.p);
-        o[pl] = add_mod(mul_mod(u, key[pl + off], md), xb[2 * pl], md.p);
+        o[0] = encrypt_plus(encrypt_plus(encrypt_pk_combine(u, key[off], md), xb[pl], md), m, md);
+        o[pl] = encrypt_plus(encrypt_pk_combine(u, key[pl + off], md), xb[2 * pl], md);
     } else {
         const u64 av = a[gid];
-        o[0] = add_mod(sub_mod(x[gid], mul_mod(av, key[off], md), md.p), m, md.p);
+        o[0] = encrypt_plus(encrypt_sk_combine(x[gid], av, key[off], md), m, md);
         o[pl] = av;
     }
 }
