@@ -1,7 +1,8 @@
 """One shape of tests/devop_shapes.py through the encode, encrypt and key-generation cases (encode_cases,
 encrypt_cases, keygen_cases), every item against the restatements bit for bit.  Shared by
 tests/test_devop_shapes_gpu.py (the HIP build), tests/test_devop_shapes_emu.py (kernel sources under host emulation)
-and the `devops` family of tests/random_sweep_gpu.py.  `dev`: as helpers.Xfer."""
+and the `devops` family of tests/random_sweep_gpu.py; the launch-group rule and the symbol parsers also serve
+tests/test_mbfv_shapes_gpu.py.  `dev`: as helpers.Xfer."""
 import re
 
 import devop_shapes as S
@@ -58,7 +59,9 @@ def launch_group(nmoduli, n, rows_per_item, batch, budget, cap=65535):
     polynomials of nmoduli x n words per item) stay within `budget` bytes and `cap` items, and the batch is split
     into groups of equal size.  Secret-key encryption: 1 row per item in 1 GiB for whole rows (N <= 16384), 2 in
     256 MiB above; public-key encryption: one group of up to 65535 for whole rows, 3 rows in 256 MiB above; key
-    generation: ndigits rows per key in 1 GiB for whole rows, 2 ndigits in 256 MiB above, at most 32 keys (KG_KEYS)."""
+    generation: ndigits rows per key in 1 GiB for whole rows, 2 ndigits in 256 MiB above, at most 32 keys (KG_KEYS);
+    the multiparty shares (mbfv_shares): 1 row per item and no byte budget for whole rows, so the cap of 65535 items
+    alone splits a batch, and `edraws` rows per item (the transformed draws) in 256 MiB above."""
     per = max(1, rows_per_item) * nmoduli * n * 8
     most = max(1, min(cap, budget // per))
     groups = -(-batch // most)
@@ -91,3 +94,29 @@ def cell_of_symbol(symbol):
     hr = int(m.group(4))
     kind = "f64_%d" % hr if hr else "narrow" if m.group(3) == "true" else "general"
     return m.group(1), int(m.group(2)), kind
+
+
+_MBFV_SYMBOL = re.compile(r"(mbfv_share_kernel)<(\d+), (true|false), (\d+), (\d+)>")
+
+
+def mbfv_cell_of_symbol(symbol):
+    """As cell_of_symbol for `...mbfv_share_kernel<LOGM, NARROW, F64, FORM>(...)`: a cell of
+    devop_shapes.mbfv_all_cells(); None for every other kernel."""
+    m = _MBFV_SYMBOL.search(symbol)
+    if not m:
+        return None
+    hr = int(m.group(4))
+    kind = "f64_%d" % hr if hr else "narrow" if m.group(3) == "true" else "general"
+    return m.group(1), int(m.group(2)), kind, int(m.group(5))
+
+
+def mbfv_f64_eligible(shp):
+    """One of the shape's share launches takes an F64 instance while the switch is on."""
+    return any(kind.startswith("f64") for _k, _lm, kind, _f in S.mbfv_cells(shp))
+
+
+def chunk_group(batch, cap=65535):
+    """Items per launch of the loops that cut a batch into chunks of `cap` with a tail (for_groups with a fixed size):
+    public-key encryption of whole rows -- and with it the public-key-switch share -- and the aggregator mbfv_sum,
+    whose polynomial index is the grid's second dimension."""
+    return min(batch, cap)

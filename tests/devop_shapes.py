@@ -10,6 +10,7 @@ That is 2 x 12 + 3 x 3 = 33 instances per kernel.  generate_prime(bits, ...) ret
 so a "50-bit" modulus is class 3, a "49-bit" one class 4, 48 bits and fewer class 5, 51 ... 60 bits narrow and 61 or
 62 bits general.  The rows of the ciphertext moduli take their kind from the moduli of the level they run at (level l
 keeps the first L - l moduli); the row mod t (encode_simd_t_kernel, decode_simd_kernel) takes it from t alone.
+The multiparty share kernel has the same 33 row kinds in each of its three forms (mbfv_all_cells, mbfv_cells).
 
 Nothing here imports the engine."""
 import random
@@ -102,6 +103,31 @@ def cells(shp):
     for rows in (q, q[:1]):
         out |= {(k, lm, row_kind(rows, lm)) for k in KERNELS if k not in T_KERNELS and k != "ksk_gen_kernel"}
     out.add(("ksk_gen_kernel", lm, row_kind(q, lm)))
+    return out
+
+
+# The multiparty share kernel, mbfv_share_kernel<LOGM, NARROW, F64, FORM>, goes through the same dispatcher: the same 33
+# row kinds, times its three forms (kernels_mbfv.hpp: MBFV_AX = 0, MBFV_AXX = 1, MBFV_AX_WY = 2).
+MBFV_KERNEL = "mbfv_share_kernel"
+MBFV_FORMS = (0, 1, 2)
+
+
+def mbfv_all_cells():
+    """Every (mbfv_share_kernel, LOGM, kind, form) instance: 33 x 3."""
+    return {(MBFV_KERNEL, lm, k, f) for kern, lm, k in all_cells() if kern == KERNELS[0] for f in MBFV_FORMS}
+
+
+def mbfv_cells(shp):
+    """The instances mbfv_shape_cases.case_shape launches for one shape: MBFV_AX (the public-key share at level 0, the
+    decryption share, round-1 h1, round-2 h0) and MBFV_AXX (the secret-key-switch share, round-2 h1) at the kind of
+    level 0 and at the kind of the deepest level; MBFV_AX_WY (round-1 h0) at the kind of level 0 alone, and only when
+    the relin rounds run (two moduli or more: they run over the level-0 context)."""
+    n, sizes, _t, _v, _b = shp
+    lm = n.bit_length() - 1
+    q = generate_moduli(sizes, n)
+    out = {(MBFV_KERNEL, lm, row_kind(rows, lm), f) for rows in (q, q[:1]) for f in MBFV_FORMS[:2]}
+    if len(q) >= 2:
+        out.add((MBFV_KERNEL, lm, row_kind(q, lm), MBFV_FORMS[2]))
     return out
 
 

@@ -1,6 +1,7 @@
 """The shape table of tests/devop_shapes.py: the oracle accepts every shape, and the matrix list reaches every
 (kernel, LOGM, kind) instance of the seven whole-row encode / encrypt / key-generation kernels -- 7 x 33 = 231 cells,
-derived here from the shapes' own moduli by the dispatch rules, restated below.  No engine, no GPU."""
+derived here from the shapes' own moduli by the dispatch rules, restated below; the same for the 33 x 3 = 99 instances of
+the multiparty share kernel.  No engine, no GPU."""
 import devop_shapes as S
 from fhe_oracle import bfv as obfv
 
@@ -39,9 +40,15 @@ def launched_cells(opar):
     return cells
 
 
+_built = {}
+
+
 def build(shp):
     n, sizes, t, variance, batch = shp
-    opar = obfv.BfvParameters(n, t, moduli_sizes=sizes, variance=variance)   # raises NonInvertible / NotEnoughPrimes
+    key = (n, tuple(sizes), t, variance)
+    if key not in _built:   # (seconds at n = 16384, and two tests walk the matrix)
+        _built[key] = obfv.BfvParameters(n, t, moduli_sizes=sizes, variance=variance)   # raises NonInvertible / NotEnoughPrimes
+    opar = _built[key]
     assert opar.moduli_sizes == sizes and t % (2 * n) == 1 and t not in opar.moduli
     assert 1 <= variance <= 32 and batch >= 1
     return opar
@@ -71,6 +78,31 @@ def test_matrix_shapes_cover_every_instance():
     # t as wide as the general instances take, the stock 20 bits, and one of each F64 class
     widths = {o.plaintext.bit_length() for os_ in by_logm.values() for o in os_}
     assert {20, 48, 49, 50, 61} <= widths and any(51 <= w <= 59 for w in widths)
+
+
+def test_mbfv_cells_cover_every_instance():
+    """mbfv_share_kernel<LOGM, NARROW, F64, FORM>: the matrix case (mbfv_shape_cases.case_shape) launches MBFV_AX (0) and
+    MBFV_AXX (1) over the moduli of level 0 and of the deepest level, MBFV_AX_WY (2, round-1 h0) over the level-0
+    moduli; the union over the matrix is every one of the 33 x 3 instances."""
+    need = {("mbfv_share_kernel", logm, k, form) for kern, logm, k in required_cells() if kern == "ksk_gen_kernel"
+            for form in (0, 1, 2)}
+    assert len(need) == 3 * 33 == 99 and S.MBFV_FORMS == (0, 1, 2)
+    got = set()
+    differ = 0
+    for shp in S.matrix_shapes():
+        opar = build(shp)
+        assert len(opar.moduli) >= 2   # (the relin rounds run on every matrix shape)
+        logm = opar.degree().bit_length() - 1
+        k0, kd = kind(opar.ctx[0].moduli, logm), kind(opar.ctx[opar.max_level()].moduli, logm)
+        differ += k0 != kd
+        mine = {("mbfv_share_kernel", logm, k, form) for k in (k0, kd) for form in (0, 1)}
+        mine.add(("mbfv_share_kernel", logm, k0, 2))
+        assert mine == S.mbfv_cells(shp), shp
+        got |= mine
+    assert got == need == S.mbfv_all_cells(), sorted(need - got)
+    assert differ   # (a deepest level of another kind than level 0's: [36, 62], [60, 52, 30], ...)
+    # a single-modulus shape of the sweep runs no relin round
+    assert {c[3] for c in S.mbfv_cells(S.shape(16, [62], 20, 10, 1))} == {0, 1}
 
 
 def test_roundtrip_shapes_leave_room_for_fresh_noise():
