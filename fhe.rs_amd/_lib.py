@@ -156,6 +156,8 @@ SIGNATURES = {
     "fhe_bfv_galois_keys_generate_dev": (i32, [vp, vp, sz, vp, vp, vp, sz, vp, vp, vp]),
     "fhe_ksk_export_dev": (i32, [vp, vp, vp, vp, vp, vp]),
     "fhe_ksk_ndigits": (sz, [vp]),
+    "fhe_ksk_load_wire_dev": (i32, [vp, vp, sz, vp, vp, vp, sz, vp, vp]),
+    "fhe_ksk_serialize_dev": (i32, [vp, vp, vp, vp]),
     "fhe_ctx_lift_limbs": (sz, [vp]),
     "fhe_poly_lift_dev": (i32, [vp, vp, vp, sz, vp]),
     "fhe_poly_centered_bits_dev": (i32, [vp, vp, vp, sz, vp]),

@@ -808,6 +808,63 @@ class KeySwitchingKey:
             _wipe(staged)
         return keys[0] if one else keys
 
+    @classmethod
+    def from_wire(cls, ctx_ciphertext, ctx_ksk, c0_bytes, c1_bytes=None, seeds=None, log_base=0):
+        """KeySwitchingKey::try_convert_from(&KeySwitchingKeyProto) (key_switching_key.rs:387-482) on the device
+        (fhe_ksk_load_wire_dev): c0_bytes uint8 [ndigits, ctx_ksk.serialized_size] -- `proto.c0[i].coefficients`
+        concatenated -- or [nkeys, ndigits, size] for a batch of keys of one geometry; exactly one of c1_bytes (same
+        shape) and seeds (`proto.seed`: 32 bytes per key, as `_seeds` takes them).  Device arrays are read in place, numpy
+        is staged.  A coefficient >= q_j -> FheError(-1).  Returns a list of keys, ready on any stream."""
+        L = _lib.lib()
+        if (c1_bytes is None) == (seeds is None):
+            raise FheError(-1, "exactly one of c1_bytes and seeds")
+        nd = -(-(ctx_ksk.moduli[0] - 1).bit_length() // log_base) if log_base else ctx_ciphertext.nmoduli
+        tail = (nd, ctx_ksk.serialized_size)
+        dev = max(ctx_ksk.device, 0)
+
+        def wire(b):
+            if tuple(b.shape[-2:]) != tail or len(b.shape) > 3:
+                raise FheError(-1, "wire bytes must be [ndigits, serialized_size] (%d, %d) per key" % tail)
+            if not _is_dev(b):
+                b = DeviceArray.from_numpy(np.ascontiguousarray(np.asarray(b, dtype=np.uint8)), dev)
+            return b
+        c0 = wire(c0_bytes)
+        count = 1 if len(c0.shape) == 2 else int(c0.shape[0])
+        c1 = sd = None
+        if c1_bytes is not None:
+            c1 = wire(c1_bytes)
+            if tuple(c1.shape) != tuple(c0.shape):
+                raise FheError(-1, "c0_bytes and c1_bytes differ in shape")
+        else:
+            sd, n, _own = _seeds(seeds, count, dev)   # (public seeds: kept with the keys, not wiped)
+            if n != count:
+                raise FheError(-1, "one seed per key: %d keys, %d seeds" % (count, n))
+        hs = (C.c_void_p * count)()
+        check(L.fhe_ksk_load_wire_dev(ctx_ciphertext._h, ctx_ksk._h, log_base, _dptr8(c0),
+                                      _dptr8(c1) if c1 is not None else None, _dptr8(sd) if sd is not None else None,
+                                      count, _stream(), hs))
+        keys = []
+        for i in range(count):
+            k = cls._adopt(ctx_ciphertext, ctx_ksk, hs[i], sd.reshape(count, 32) if sd is not None else None, i)
+            k.log_base = log_base
+            keys.append(k)
+        return keys
+
+    def to_wire(self, seeded=None):
+        """From<&KeySwitchingKey> for KeySwitchingKeyProto (key_switching_key.rs:365-385) on the device
+        (fhe_ksk_serialize_dev): (c0_bytes, seed) when the key carries its seed (keys from `.generate` and from a
+        seeded `from_wire`), else (c0_bytes, c1_bytes); the byte arrays are uint8 [ndigits, serialized_size] on the
+        device, one row per `proto.c0[i].coefficients`.  seeded = False forces the explicit c1."""
+        if seeded is None:
+            seeded = self.seed is not None
+        if seeded and self.seed is None:
+            raise FheError(-1, "the key carries no seed")
+        shape = (self.ndigits, self.ctx_ksk.serialized_size)
+        c0 = _alloc(shape, self.ctx_ksk.device, itemsize=1)
+        c1 = None if seeded else _alloc(shape, self.ctx_ksk.device, itemsize=1)
+        check(_lib.lib().fhe_ksk_serialize_dev(self._h, _dptr8(c0), _dptr8(c1) if c1 is not None else None, _stream()))
+        return c0, (self.seed if seeded else c1)
+
     def export(self):
         """(c0, c1, c0_shoup, c1_shoup), each [ndigits, Lk, N] on the device (fhe_ksk_export_dev): what a client sends
         to the server; `KeySwitchingKey(ctx_ct, ctx_ksk, c0, c1, ...)` of them is an equal key."""
@@ -866,6 +923,14 @@ class RelinearizationKey:
             L.fhe_bfv_relin_key_generate_dev(ct._h, kc._h, sk.params.variance, _dptr(sk.s_ntt), _dptr8(sd), _dptr8(ko),
                                              _stream(), hs)))[0])
 
+    @classmethod
+    def from_wire(cls, ctx_ciphertext, ctx_ksk, c0_bytes, c1_bytes=None, seed=None):
+        """RelinearizationKeyProto's one KeySwitchingKeyProto (relinearization_key.rs), as KeySwitchingKey.from_wire."""
+        return cls(KeySwitchingKey.from_wire(ctx_ciphertext, ctx_ksk, c0_bytes, c1_bytes, seed)[0])
+
+    def to_wire(self, seeded=None):
+        return self.ksk.to_wire(seeded)
+
     def relinearizes(self, ct3):
         """[..., 3, L, N] Ntt -> [..., 2, L, N] Ntt."""
         L = _lib.lib()
@@ -907,6 +972,24 @@ class GaloisKey:
             L.fhe_bfv_galois_keys_generate_dev(ct._h, kc._h, sk.params.variance, _dptr(sk.s_ntt), arr, _dptr8(sd),
                                                len(exps), _dptr8(ko), _stream(), hs)))
         return [cls(k, e) for k, e in zip(keys, exps)]
+
+    @classmethod
+    def from_wire(cls, exponents, ctx_ciphertext, ctx_ksk, c0_bytes, c1_bytes=None, seeds=None, log_base=0):
+        """One GaloisKeyProto per exponent (galois_key.rs): the keys' bytes batched as KeySwitchingKey.from_wire takes
+        them ([nkeys, ndigits, size]), one load call.  Returns a list of keys in the order of `exponents`."""
+        exps = [int(e) for e in exponents]
+        if not exps:
+            return []
+        n = ctx_ciphertext.degree
+        if any((e % (2 * n)) & 1 == 0 for e in exps):
+            raise FheError(-10, "InvalidSubstitutionExponent")
+        keys = KeySwitchingKey.from_wire(ctx_ciphertext, ctx_ksk, c0_bytes, c1_bytes, seeds, log_base)
+        if len(keys) != len(exps):
+            raise FheError(-1, "one key per exponent: %d exponents, %d keys" % (len(exps), len(keys)))
+        return [cls(k, e) for k, e in zip(keys, exps)]
+
+    def to_wire(self, seeded=None):
+        return self.ksk.to_wire(seeded)
 
     def relinearize(self, ct):
         """[..., 2, L, N] Ntt -> same shape."""
@@ -963,6 +1046,18 @@ class EvaluationKey:
         HashSet order; here each key has its own seed.)"""
         exps = cls.exponents(sk.params.degree, column_rotations, row_rotation, inner_sum, expansion_level)
         return cls(sk.params.degree, GaloisKey.generate(sk, exps, seeds, ciphertext_level, key_level))
+
+    @classmethod
+    def from_wire(cls, exponents, ctx_ciphertext, ctx_ksk, c0_bytes, c1_bytes=None, seeds=None, log_base=0):
+        """EvaluationKeyProto's Galois keys (evaluation_key.rs): `exponents` are the messages' exponents, the bytes
+        batched in the same order (GaloisKey.from_wire)."""
+        return cls(ctx_ciphertext.degree,
+                   GaloisKey.from_wire(exponents, ctx_ciphertext, ctx_ksk, c0_bytes, c1_bytes, seeds, log_base))
+
+    def to_wire(self, seeded=None):
+        """(exponents, [KeySwitchingKey.to_wire(seeded) per key]), exponents sorted."""
+        exps = sorted(self.gk)
+        return exps, [self.gk[e].to_wire(seeded) for e in exps]
 
     def rotates_rows(self, ct):
         e = 2 * self.degree - 1
@@ -1036,6 +1131,17 @@ class RGSWCiphertext:
 
     def __init__(self, ksk0: KeySwitchingKey, ksk1: KeySwitchingKey):
         self.ksk0, self.ksk1 = ksk0, ksk1
+
+    @classmethod
+    def from_wire(cls, ctx_ciphertext, ctx_ksk, c0_bytes, c1_bytes=None, seeds=None, log_base=0):
+        """RGSWCiphertextProto{ksk0, ksk1} (rgsw_ciphertext.rs): two keys in one load call, bytes [2, ndigits, size].
+        Both keys are at the ciphertext's level, else FheError(-1)."""
+        if list(ctx_ksk.moduli) != list(ctx_ciphertext.moduli) or len(c0_bytes.shape) != 3 or c0_bytes.shape[0] != 2:
+            raise FheError(-1, "an RGSW ciphertext is two keys at the ciphertext level")
+        return cls(*KeySwitchingKey.from_wire(ctx_ciphertext, ctx_ksk, c0_bytes, c1_bytes, seeds, log_base))
+
+    def to_wire(self, seeded=None):
+        return self.ksk0.to_wire(seeded), self.ksk1.to_wire(seeded)
 
     def external_product(self, ct):
         """`&Ciphertext * &RGSWCiphertext`: ct, result [..., 2, L, N] Ntt."""

@@ -3092,6 +3092,115 @@ inline void galois_from(const Ctx &ct, const Ctx &kc, const u64 *s_ntt, const si
     if (t) switch_up_ntt(ct, kc, t->u(), out, nkeys, s);
 }
 
+// --------------------------------------------------------------- keys on the wire ----
+// The digit count KeySwitchingKey::try_convert_from reads off a message (F/bfv/keys/key_switching_key.rs:394-412):
+// ceil(log_modulus / log_base) for a decomposition key, else the ciphertext context's moduli count.
+inline size_t ksk_wire_digits(const Ctx &ct, const Ctx &kc, size_t log_base) {
+    if (!log_base) return ct.L;
+    const size_t log_modulus = 64 - __builtin_clzll(kc.moduli[0] - 1);
+    return (log_modulus + log_base - 1) / log_base;
+}
+
+// KeySwitchingKey::try_convert_from(&KeySwitchingKeyProto) (:387-482) for `nkeys` keys of one geometry: c0b
+// [nkeys][ndigits][wire_poly_bytes(kc)] packed PowerBasis polynomials; c1b the same (explicit c1) or K [nkeys][32] the
+// messages' seeds -- exactly one of the two.  No unpacked copy and no key word passes through host memory: whole rows
+// (N <= 16384) go from the bytes through the transform into the handles in one launch per group of up to KG_KEYS keys
+// (ksk_generate's groups); larger rows through wire_deserialize into the handle, the element-wise compare, launch_ntt
+// and the element-wise twins.  A seeded
+// c1 is expanded by the unchanged seed_expand_kernel straight into each handle's c1 (it writes a key's digits back to
+// back, the handle's layout), one launch per key.  A word >= q_j anywhere raises the call's flag word: the call waits
+// for `s` once, after its last launch, reads it, and throws E_ARG -- the handles are freed with the vector.
+inline std::vector<std::unique_ptr<Ksk>> ksk_load_wire(const Ctx &ct, const Ctx &kc, size_t lb, const uint8_t *c0b,
+                                                       const uint8_t *c1b, const uint8_t *K, size_t nkeys, hipStream_t s) {
+    kc.need_device();
+    const size_t nd = ksk_wire_digits(ct, kc, lb), Lk = kc.L, N = kc.n;
+    ksk_validate(ct, kc, nd, lb);
+    std::vector<std::unique_ptr<Ksk>> keys;
+    if (!nkeys) return keys;
+    const u64 PK = (u64)nd * Lk * N;   // words of one key array
+    const u64 wb = wire_poly_bytes(kc);
+    const bool wf = ksk_f64_eligible(kc, lb);
+    for (size_t b = 0; b < nkeys; b++) {
+        auto k_ = make_ksk(ct, kc, nd, lb);
+        for (DevBuf<u64> *d : {&k_->c0, &k_->c0s, &k_->c1, &k_->c1s}) d->alloc(PK);
+        if (wf) {
+            k_->c0f.alloc(PK);
+            k_->c1f.alloc(PK);
+        }
+        keys.push_back(std::move(k_));
+    }
+    // rq [Lk] {2^64 mod q_j, q_j^-1} (ksk_consts_kernel's; its g [nd][Lk] is not read here), then the flag word
+    WsGuard cst((2 * Lk + nd * Lk + 1) * sizeof(u64), s);
+    k::u64x2 *rq = (k::u64x2 *)cst.p;
+    u64 *g = cst.u() + 2 * Lk;
+    uint32_t *flag = (uint32_t *)(g + nd * Lk);
+    FHE_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(u64), s));
+    FHE_LAUNCH("ksk_consts", k::ksk_consts_kernel, dim3(blocks_for(nd * Lk, 64)), dim3(64), 0, s, kc.dmods(),
+               (uint32_t)nd, (uint32_t)Lk, (uint32_t)lb, g, rq);
+    const bool whole = kc.logn <= 14;
+    const RowLaunch rows(kc, Lk, !f64_disabled());
+    // the word-granular loader: rows of >= 128 coefficients and 16-byte aligned byte pointers (see ksk_load_kernel)
+    const bool words = N >= 128 && ((uintptr_t)c0b & 15) == 0 && ((uintptr_t)c1b & 15) == 0;
+    const size_t group = whole ? encrypt_group(kc, nd, nkeys, (size_t)1 << 30, k::KG_KEYS)
+                               : encrypt_group(kc, 2 * nd, nkeys, (size_t)256 << 20, k::KG_KEYS);
+    require(2 * group * nd * Lk <= 0x7fffffffu, E_ARG, "ksk_load_wire: a launch group exceeds the grid limit");
+    for_groups(nkeys, group, [&](size_t b0, size_t nb) {
+        k::KskOutTable tab{};
+        for (size_t b = 0; b < nb; b++) {
+            const Ksk &kk = *keys[b0 + b];
+            tab.k[b] = k::KskOut{kk.c0.p, kk.c0s.p, kk.c1.p, kk.c1s.p, kk.c0f.p, kk.c1f.p};
+        }
+        const uint8_t *b0p = c0b + b0 * nd * wb, *b1p = c1b ? c1b + b0 * nd * wb : nullptr;
+        uint32_t ew_parts = whole ? 0u : 3u;   // what ksk_twin_ew_kernel still has to do for this group
+        if (K) {
+            WsGuard ds(nb * nd * 32, s);
+            FHE_LAUNCH("ksk_dseeds", k::ksk_dseeds_kernel, dim3(blocks_for(nb * nd, 64)), dim3(64), 0, s, K + b0 * 32,
+                       (uint8_t *)ds.p, (uint32_t)nd, (uint32_t)(nb * nd));
+            for (size_t b = 0; b < nb; b++)
+                polys_from_seeds(kc, (const uint8_t *)ds.p + b * nd * 32, keys[b0 + b]->c1.p, nd, s);
+            ew_parts |= 2u;
+        }
+        if (whole) {
+            rows("ksk_load", (b1p ? 2 : 1) * nb * nd * Lk, s,
+                 [](auto lm, auto nrw, auto h) { return kernel_c<k::ksk_load_kernel<lm(), nrw(), h()>>{}; }, b0p, b1p, wb,
+                 (uint32_t)words, (const k::u64x2 *)rq, tab, (uint32_t)nd, (uint32_t)Lk, (uint32_t)(nb * nd), (uint32_t)wf,
+                 kc.dmods(), rows.tw(), flag);
+        }
+        const u64 pairs = (u64)nb * PK / 2;
+        auto twins = [&](uint32_t parts, uint32_t check_only) {
+            FHE_LAUNCH("ksk_twin", k::ksk_twin_ew_kernel, dim3(blocks_for(pairs, EW_THREADS)), dim3(EW_THREADS), 0, s, tab,
+                       parts, check_only, (const k::u64x2 *)rq, (uint32_t)nd, (uint32_t)Lk, (uint32_t)wf, kc.dmods(),
+                       (uint32_t)kc.logn, pairs, flag);
+        };
+        if (!whole) {
+            // unpack into the handles, compare the PowerBasis words with their moduli, then transform in place
+            for (size_t b = 0; b < nb; b++) {
+                wire_deserialize(kc, b0p + b * nd * wb, keys[b0 + b]->c0.p, nd, false, s);
+                if (b1p) wire_deserialize(kc, b1p + b * nd * wb, keys[b0 + b]->c1.p, nd, false, s);
+            }
+            twins(b1p ? 3u : 1u, 1u);
+            for (size_t b = 0; b < nb; b++) {
+                launch_ntt(kc, false, keys[b0 + b]->c0.p, keys[b0 + b]->c0.p, full_map(kc, Lk), nd, s);
+                if (b1p) launch_ntt(kc, false, keys[b0 + b]->c1.p, keys[b0 + b]->c1.p, full_map(kc, Lk), nd, s);
+            }
+        }
+        if (ew_parts) twins(ew_parts, 0u);
+    });
+    uint32_t bad = 0;
+    FHE_HIP_CHECK(hipMemcpyAsync(&bad, flag, sizeof(bad), hipMemcpyDeviceToHost, s));
+    FHE_HIP_CHECK(hipStreamSynchronize(s));
+    require(!bad, E_ARG, "key coefficient not reduced");
+    return keys;
+}
+
+// From<&KeySwitchingKey> for KeySwitchingKeyProto (:365-385): c0 (and c1 when c1b is given) taken to PowerBasis and
+// packed, straight from the handle's arrays.
+inline void ksk_serialize_wire(const Ksk &k_, uint8_t *c0b, uint8_t *c1b, hipStream_t s) {
+    const Ctx &kc = *k_.ksk_ctx;
+    wire_serialize(kc, k_.c0.p, c0b, k_.ndigits, true, s);
+    if (c1b) wire_serialize(kc, k_.c1.p, c1b, k_.ndigits, true, s);
+}
+
 // ------------------------------------------------------------------ multiparty BFV ----
 // The shares of F/mbfv/ (kernels_mbfv.hpp).  One part of a call: the form, the operands (e, edraws filled in by
 // mbfv_shares) and out [batch][k][L][N].

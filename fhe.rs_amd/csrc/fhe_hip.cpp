@@ -1961,6 +1961,35 @@ fhe_status fhe_ksk_export_dev(const fhe_ksk *ksk, uint64_t *c0, uint64_t *c1, ui
     });
 }
 
+// ------------------------------------------------------------------- keys on the wire ----
+// Device-pointer forms only.  The load call checks its handles, the device and the key's geometry before it looks at a
+// buffer; nkeys == 0 is a no-op.  The handles are made all or none, like the generation calls'.
+fhe_status fhe_ksk_load_wire_dev(const fhe_ctx *ct_ctx, const fhe_ctx *ksk_ctx, size_t log_base, const uint8_t *c0_bytes,
+                                 const uint8_t *c1_bytes, const uint8_t *seeds, size_t nkeys, void *stream, fhe_ksk **out) {
+    return guard([&] {
+        need(ct_ctx, "ct_ctx");
+        need(ksk_ctx, "ksk_ctx");
+        const Ctx &ct = *ct_ctx->c, &kc = *ksk_ctx->c;
+        kc.need_device();
+        ksk_validate(ct, kc, ksk_wire_digits(ct, kc, log_base), log_base);
+        if (!nkeys) return;
+        need(out, "out");
+        for (size_t i = 0; i < nkeys; i++) out[i] = nullptr;
+        need(c0_bytes, "c0_bytes");
+        require((c1_bytes != nullptr) != (seeds != nullptr), E_ARG, "exactly one of c1_bytes and seeds");
+        set_device(kc);
+        keygen_out(ksk_load_wire(ct, kc, log_base, c0_bytes, c1_bytes, seeds, nkeys, as_stream(stream)), out);
+    });
+}
+fhe_status fhe_ksk_serialize_dev(const fhe_ksk *ksk, uint8_t *c0_bytes, uint8_t *c1_bytes, void *stream) {
+    return guard([&] {
+        need(ksk, "ksk");
+        need(c0_bytes, "c0_bytes");
+        set_device(*ksk->k->ksk_ctx);
+        ksk_serialize_wire(*ksk->k, c0_bytes, c1_bytes, as_stream(stream));
+    });
+}
+
 // --------------------------------------------------------------------- multiparty BFV ----
 // Device-pointer forms only, like encryption.  Each checks its handle, the device and the variance before it looks at a
 // buffer; batch == 0 is a no-op.

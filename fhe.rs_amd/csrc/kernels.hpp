@@ -30,6 +30,8 @@
 //                           PublicKey::try_encrypt   M/rq/mod.rs:298-330, F/bfv/keys/secret_key.rs:100-134, public_key.rs:47-97
 //   ksk_seeds_kernel, cbd_sample_at_kernel, ksk_consts_kernel, ksk_gen_kernel, galois_from_kernel   KeySwitchingKey::new,
 //                           RelinearizationKey / GaloisKey::new   F/bfv/keys/key_switching_key.rs:71-236, galois_key.rs:26-58
+//   ksk_dseeds_kernel, ksk_load_kernel, ksk_twin_ew_kernel   KeySwitchingKey::try_convert_from(&KeySwitchingKeyProto): the
+//                           wire bytes to a handle's arrays, twins and F64 words   F/bfv/keys/key_switching_key.rs:387-482
 //   lift_kernel, noise_max_kernel       RnsContext::lift, SecretKey::measure_noise   M/rns/mod.rs:138-143, F/bfv/keys/secret_key.rs:55-98
 //   mbfv_share_kernel, mbfv_sum_kernel  the shares of the multiparty protocols and their aggregation   F/mbfv/*.rs
 //   bigt_project_kernel, bigt_tail_kernel   plaintext moduli above 64 bits: Vec<BigUint> encoding and the Large branch of
@@ -45,6 +47,7 @@
 #include "kernels_encode.hpp"
 #include "kernels_encrypt.hpp"
 #include "kernels_keygen.hpp"
+#include "kernels_keyload.hpp"
 #include "kernels_noise.hpp"
 #include "kernels_mbfv.hpp"
 #include "kernels_bigt.hpp"

@@ -572,6 +572,39 @@ fhe_status fhe_ksk_export_dev(const fhe_ksk *ksk, uint64_t *c0, uint64_t *c1, ui
 /* A key's digit count: each of fhe_ksk_export_dev's arrays holds ndigits * Lk * N words (0 for NULL). */
 size_t fhe_ksk_ndigits(const fhe_ksk *ksk);
 
+/* --------------------------------------------------------- keys on the wire ---- */
+/* Key-switching keys to and from the payloads of their KeySwitchingKeyProto messages, on the device.  Device-pointer
+ * forms only, with no host-pointer twin.  RelinearizationKey, GaloisKey, EvaluationKey and RGSWCiphertext are one or
+ * more such messages.  The envelope checks (representation tag, degree, polynomial counts, seed length) stay with the
+ * host that parses the protobuf; these calls move the `coefficients` payloads and the seed.
+ *
+ * KeySwitchingKey::try_convert_from(&KeySwitchingKeyProto) (F/bfv/keys/key_switching_key.rs:387-482) for nkeys
+ * keys of one geometry: c0_bytes [nkeys][ndigits][fhe_poly_serialized_size(ksk_ctx)], the `coefficients` payloads
+ * of the c0 Rq messages; exactly one of c1_bytes (same shape) and seeds [nkeys][32] (the message's `seed`) non-NULL.
+ * ndigits follows from the contexts and log_base as in the reference (:394-412): ceil(log_modulus / log_base) with
+ * log_modulus = q.next_power_of_two().ilog2() for a decomposition key, else the ciphertext context's moduli count.
+ * With a seed, c1[i] = Poly::random_from_seed(ksk_ctx, bytes [32 i, 32 i + 32) of ChaCha8Rng::from_seed(seed))
+ * (generate_c1; the layout of fhe_ksk_generate_dev, PARITY UNPINNED like it).  The byte pointers need no alignment
+ * (16-byte aligned ones take a faster loader from N = 128 on).
+ * A handle made here is indistinguishable from fhe_ksk_create of the same words: c0, c1, both Shoup twin arrays, the
+ * F64 words when the key is eligible, mode FHE_KS_AUTO.
+ * Range check: a coefficient >= q_j anywhere in c0 or an explicit c1 -> FHE_E_ARG ("key coefficient not reduced"),
+ * no handle is returned (out[] all NULL) and every buffer is freed, exactly as fhe_ksk_create refuses such a word.
+ * The reference takes such words verbatim (Poly::from_bytes does not reduce them, convert.rs:148-160) and would compute
+ * with a non-canonical key; here the Shoup quotient of an unreduced word does not fit 64 bits, so the key is refused.
+ * Stream: the bytes are untrusted input, so the call waits for `stream` once, after its last launch, to read the
+ * check's flag word (fhe_ksk_create_dev waits too).  Keys it returns are therefore ready on any stream.
+ * Statuses: the geometry as fhe_ksk_create (FHE_E_DEGREE_MISMATCH, FHE_E_CONTEXT_NOT_REACHABLE,
+ * FHE_E_PARAMETER_MISMATCH, FHE_E_KEYSWITCH_UNSUPPORTED, FHE_E_ARG for a bad log_base); both or neither of c1_bytes /
+ * seeds, or a NULL handle or buffer with nkeys > 0 -> FHE_E_ARG; nkeys == 0 is a no-op. */
+fhe_status fhe_ksk_load_wire_dev(const fhe_ctx *ct_ctx, const fhe_ctx *ksk_ctx, size_t log_base,
+                                 const uint8_t *c0_bytes, const uint8_t *c1_bytes, const uint8_t *seeds,
+                                 size_t nkeys, void *stream, fhe_ksk **out);
+/* The reverse (:365-385): c0 (and c1 when c1_bytes != NULL) taken to PowerBasis and packed, straight from the
+ * handle's arrays (no export copy): c0_bytes, c1_bytes [ndigits][fhe_poly_serialized_size(ksk_ctx)].  A seeded message
+ * carries c0_bytes and the key's seed instead of c1_bytes.  Asynchronous on `stream`. */
+fhe_status fhe_ksk_serialize_dev(const fhe_ksk *ksk, uint8_t *c0_bytes, uint8_t *c1_bytes, void *stream);
+
 /* ------------------------------------------------------------ lift and noise ---- */
 /* Residues to integers, and the noise of a ciphertext.  Device-pointer forms only, with no host-pointer twin: the phase
  * and the error polynomial are secret-dependent and are never staged through host memory by the engine.  batch == 0 is

@@ -227,6 +227,8 @@ impl CtxView<'_> {
     pub fn device(&self) -> i32 { unsafe { ffi::fhe_ctx_device(self.ptr) as i32 } }
     /// u64 words of one polynomial, `L * N`.
     pub fn poly_words(&self) -> usize { self.nmoduli() * self.degree() }
+    /// Bytes of one polynomial's `coefficients` payload on the wire (`fhe_poly_serialized_size`).
+    pub fn serialized_size(&self) -> usize { unsafe { ffi::fhe_poly_serialized_size(self.ptr) } }
     /// `Poly::ntt_forward` (rq/mod.rs:335-343) on `polys.len() / (L*N)` polynomials, in place.
     pub fn ntt_forward(&self, polys: &mut [u64]) -> Result<()> {
         let b = whole_batch("ntt_forward", polys.len(), self.poly_words())?;
@@ -998,6 +1000,15 @@ impl DeviceBuffer {
         check(unsafe { ffi::fhe_buf_upload(self.ptr as *mut c_void, src.as_ptr() as *const c_void, self.len * 8, stream.as_ptr()) })
     }
     /// Device -> host after everything enqueued on `stream` so far (waits for the stream).
+    /// Host bytes (wire payloads) as a device buffer of little-endian u64 words, the last one zero-padded.
+    pub fn upload_bytes(device: i32, bytes: &[u8], stream: &Stream) -> Result<Self> {
+        let mut padded = bytes.to_vec();
+        padded.resize(((bytes.len() + 7) / 8).max(1) * 8, 0);
+        let words: Vec<u64> = padded.chunks_exact(8).map(|c| u64::from_le_bytes(c.try_into().unwrap())).collect();
+        let buf = Self::alloc_on(device, words.len(), stream)?;
+        buf.upload(&words, stream)?;
+        Ok(buf)
+    }
     pub fn download(&self, dst: &mut [u64], stream: &Stream) -> Result<()> {
         expect_len("download", dst.len(), self.len)?;
         check(unsafe { ffi::fhe_buf_download(dst.as_mut_ptr() as *mut c_void, self.ptr as *const c_void, self.len * 8, stream.as_ptr()) })
@@ -1105,6 +1116,65 @@ impl HipKsk {
                                     out[3].as_mut_ptr(), stream.as_ptr())
         })?;
         Ok(out)
+    }
+}
+
+/// The `c1` half of a `KeySwitchingKeyProto`: the packed polynomials, or the 32-byte seeds they expand from.
+pub enum WireC1<'a> {
+    Bytes(&'a DeviceBuffer),
+    Seeds(&'a DeviceSeeds),
+}
+
+/// Keys to and from the payloads of their `KeySwitchingKeyProto` messages on the device
+/// (F/bfv/keys/key_switching_key.rs:365-482).  Wire bytes travel in `DeviceBuffer`s (u64 words, the last one padded).
+impl HipKsk {
+    /// u64 words that hold `nkeys` keys' `c0` (or `c1`) payloads: `nkeys * ndigits * serialized_size` bytes, rounded up.
+    pub fn wire_words(ksk_ctx: &Arc<HipCtx>, ndigits: usize, nkeys: usize) -> usize {
+        (nkeys * ndigits * ksk_ctx.serialized_size() + 7) / 8
+    }
+    /// `KeySwitchingKey::try_convert_from(&KeySwitchingKeyProto)` for `nkeys` keys of one geometry: `c0_bytes` holds
+    /// `proto.c0[i].coefficients` concatenated, key after key; `c1` the same for `proto.c1`, or `proto.seed` per key.
+    /// `ndigits` is the messages' polynomial count (the engine derives its own from the contexts and `log_base`, and
+    /// the lengths are checked against the caller's).  A coefficient >= q_j -> `status::ARG`, no key is made.  The
+    /// call waits for `stream` once; the keys are ready on any stream.
+    pub fn from_wire_dev(ct_ctx: &Arc<HipCtx>, ksk_ctx: &Arc<HipCtx>, log_base: usize, ndigits: usize,
+                         c0_bytes: &DeviceBuffer, c1: WireC1<'_>, nkeys: usize, stream: &Stream) -> Result<Vec<Self>> {
+        let words = Self::wire_words(ksk_ctx, ndigits, nkeys);
+        expect_len("from_wire_dev c0_bytes", c0_bytes.len(), words.max(1))?;
+        let (c1_ptr, seed_ptr) = match c1 {
+            WireC1::Bytes(b) => {
+                expect_len("from_wire_dev c1_bytes", b.len(), words.max(1))?;
+                (b.as_ptr() as *const u8, ptr::null())
+            }
+            WireC1::Seeds(sd) => {
+                expect_len("from_wire_dev seeds", sd.batch, nkeys)?;
+                (ptr::null(), sd.as_ptr())
+            }
+        };
+        let mut out = vec![ptr::null_mut(); nkeys];
+        check(unsafe {
+            ffi::fhe_ksk_load_wire_dev(ct_ctx.as_ptr(), ksk_ctx.as_ptr(), log_base, c0_bytes.as_ptr() as *const u8, c1_ptr,
+                                       seed_ptr, nkeys, stream.as_ptr(), out.as_mut_ptr())
+        })?;
+        let keys = Self::adopt(out, ct_ctx, ksk_ctx);
+        for k in keys.iter() {
+            expect_len("from_wire_dev ndigits", k.ndigits(), ndigits)?;
+        }
+        Ok(keys)
+    }
+    /// `From<&KeySwitchingKey> for KeySwitchingKeyProto`: (`c0` payloads, `c1` payloads when `with_c1`), packed from the
+    /// handle's arrays on `stream`; a seeded message sends `c0` and the key's seed.
+    pub fn to_wire_dev(&self, with_c1: bool, stream: &Stream) -> Result<(DeviceBuffer, Option<DeviceBuffer>)> {
+        let words = Self::wire_words(&self.ksk_ctx, self.ndigits(), 1).max(1);
+        let dev = self.ksk_ctx.device();
+        let c0 = DeviceBuffer::alloc_on(dev, words, stream)?;
+        let c1 = if with_c1 { Some(DeviceBuffer::alloc_on(dev, words, stream)?) } else { None };
+        expect_len("to_wire_dev c0_bytes", c0.len(), words)?;
+        check(unsafe {
+            ffi::fhe_ksk_serialize_dev(self.ptr, c0.as_mut_ptr() as *mut u8,
+                                       c1.as_ref().map_or(ptr::null_mut(), |b| b.as_mut_ptr() as *mut u8), stream.as_ptr())
+        })?;
+        Ok((c0, c1))
     }
 }
 
