@@ -1449,7 +1449,7 @@ struct Ksk {
     uint32_t digit_arg() const { return (uint32_t)log_base | (lift_mode() << 8); }
     DevBuf<u64> c0, c0s, c1, c1s;  // [ndigits][Lk][N]
     // Round 6: the key words as doubles (bit patterns) when every key modulus is below 2^50 and the digits are RNS rows
-    // (ksk_fill_f64; empty otherwise): what ks_fused_kernel's F64 instances read in place of (c0, c0s, c1, c1s) -- 16 bytes
+    // (ksk_f64_eligible; empty otherwise): what ks_fused_kernel's F64 instances read in place of (c0, c0s, c1, c1s) -- 16 bytes
     // per coefficient and digit instead of 32: their accumulate takes its quotient from h / p, so no k / q_j twin exists.
     DevBuf<u64> c0f, c1f;
     // Execution options of this handle (fhe_ksk_set_mode; read once per call, like Mul's):
@@ -1465,30 +1465,13 @@ struct Ksk {
 enum : int { KS_AUTO = 0, KS_FUSED = 1, KS_UNFUSED = 2, KS_UNFUSED_SUB = 3, KS_FUSED_SUB = 4 };
 
 // Does a key over `kc` with these digits carry the F64 words (c0f, c1f)?  RNS digits, the device's F64 tables, and every
-// key modulus below 2^50 (so that a canonical key word is an exact double).  Used by the host path (ksk_fill_f64) and
-// by device generation (ksk_generate) alike.
+// key modulus below 2^50 (so that a canonical key word is an exact double).  Every route asks here: generation
+// (ksk_generate), the wire loader (ksk_load_wire) and creation from given words (ksk_finish).
 inline bool ksk_f64_eligible(const Ctx &kc, size_t log_base) {
     if (log_base != 0 || kc.device < 0 || !kc.root->d_tw_f.p) return false;
     for (u64 q : kc.moduli)
         if (q >> 50) return false;
     return true;
-}
-
-// host key words [ndigits][Lk][N] (canonical, checked by the caller) -> the F64 twins on the device
-inline void ksk_fill_f64(Ksk &k_, const u64 *h0, const u64 *h1) {
-    const Ctx &kc = *k_.ksk_ctx;
-    if (!ksk_f64_eligible(kc, k_.log_base)) return;
-    const size_t count = k_.ndigits * kc.L * kc.n;
-    std::vector<u64> f(count);
-    auto fill = [&](const u64 *h, DevBuf<u64> &df) {
-        for (size_t x = 0; x < count; x++) {
-            const double kd = (double)h[x];     // exact: canonical key words are below 2^50 here
-            std::memcpy(&f[x], &kd, 8);
-        }
-        df.upload(f);
-    };
-    fill(h0, k_.c0f);
-    fill(h1, k_.c1f);
 }
 
 inline void ksk_validate(const Ctx &ct_ctx, const Ctx &ksk_ctx, size_t ndigits, size_t log_base) {
@@ -1510,8 +1493,7 @@ inline void ksk_validate(const Ctx &ct_ctx, const Ctx &ksk_ctx, size_t ndigits, 
     }
 }
 
-// A key handle with its geometry checked and no arrays yet (fhe_ksk_create fills them from the host, ksk_generate on
-// the device).
+// A key handle with its geometry checked and no arrays yet (ksk_alloc adds them).
 inline std::unique_ptr<Ksk> make_ksk(const Ctx &ct, const Ctx &kc, size_t ndigits, size_t log_base) {
     ksk_validate(ct, kc, ndigits, log_base);
     kc.need_device();
@@ -1521,6 +1503,17 @@ inline std::unique_ptr<Ksk> make_ksk(const Ctx &ct, const Ctx &kc, size_t ndigit
     k_->ndigits = ndigits;
     k_->log_base = log_base;
     return k_;
+}
+
+// The handle's arrays: c0, c1 and their Shoup twins, and the F64 words when the key is eligible.
+inline void ksk_alloc(Ksk &k_) {
+    const Ctx &kc = *k_.ksk_ctx;
+    const size_t count = k_.ndigits * kc.L * kc.n;
+    for (DevBuf<u64> *d : {&k_.c0, &k_.c0s, &k_.c1, &k_.c1s}) d->alloc(count);
+    if (ksk_f64_eligible(kc, k_.log_base)) {
+        k_.c0f.alloc(count);
+        k_.c1f.alloc(count);
+    }
 }
 
 template <int LOGN>
@@ -2974,6 +2967,68 @@ inline std::pair<size_t, size_t> ksk_digits(const Ctx &ct, const Ctx &kc) {
     return {ct.L, 0};
 }
 
+// `nkeys` handles of one geometry with their arrays allocated.
+inline std::vector<std::unique_ptr<Ksk>> ksk_new_keys(const Ctx &ct, const Ctx &kc, size_t nd, size_t lb, size_t nkeys) {
+    std::vector<std::unique_ptr<Ksk>> keys;
+    for (size_t b = 0; b < nkeys; b++) {
+        keys.push_back(make_ksk(ct, kc, nd, lb));
+        ksk_alloc(*keys.back());
+    }
+    return keys;
+}
+
+// What the launches of one key call share, stated once for ksk_generate, ksk_load_wire and ksk_finish: the public
+// constants of ksk_consts_kernel in scratch -- rq [Lk] {2^64 mod q_j, q_j^-1}, then g [nd][Lk] -- the group rule, a
+// group's output table, and the element-wise pass over words already in the handles.  `checked`: a route that reads
+// untrusted words also gets the zeroed flag word of the range check behind g (ksk_generate has none: its stream holds
+// no memset).
+struct KskCall {
+    const Ctx &kc;
+    const size_t nd, Lk;
+    const u64 PK;   // words of one key array
+    const bool wf, whole;
+    hipStream_t s;
+    WsGuard cst;
+    KskCall(const Ctx &kc_, size_t nd_, size_t lb, bool checked, hipStream_t s_)
+        : kc(kc_), nd(nd_), Lk(kc_.L), PK((u64)nd_ * kc_.L * kc_.n), wf(ksk_f64_eligible(kc_, lb)), whole(kc_.logn <= 14),
+          s(s_), cst((2 * Lk + nd * Lk + (checked ? 1 : 0)) * sizeof(u64), s_) {
+        if (checked) FHE_HIP_CHECK(hipMemsetAsync(flag(), 0, sizeof(u64), s));
+        FHE_LAUNCH("ksk_consts", k::ksk_consts_kernel, dim3(blocks_for(nd * Lk, 64)), dim3(64), 0, s, kc.dmods(),
+                   (uint32_t)nd, (uint32_t)Lk, (uint32_t)lb, cst.u() + 2 * Lk, (k::u64x2 *)cst.p);
+    }
+    const k::u64x2 *rq() const { return (const k::u64x2 *)cst.p; }
+    const u64 *g() const { return cst.u() + 2 * Lk; }
+    uint32_t *flag() const { return (uint32_t *)(cst.u() + 2 * Lk + nd * Lk); }
+    // groups: at most KG_KEYS keys (the output table travels in the kernel arguments) and 1 GiB of scratch rows, nd per
+    // key (256 MiB at 2 nd per key for rows larger than one LDS tile), split into groups of equal size
+    size_t group(size_t nkeys) const {
+        return whole ? encrypt_group(kc, nd, nkeys, (size_t)1 << 30, k::KG_KEYS)
+                     : encrypt_group(kc, 2 * nd, nkeys, (size_t)256 << 20, k::KG_KEYS);
+    }
+    static k::KskOut out(const Ksk &kk) { return k::KskOut{kk.c0.p, kk.c0s.p, kk.c1.p, kk.c1s.p, kk.c0f.p, kk.c1f.p}; }
+    static k::KskOutTable table(const std::unique_ptr<Ksk> *keys, size_t nb) {
+        k::KskOutTable tab{};
+        for (size_t b = 0; b < nb; b++) tab.k[b] = out(*keys[b]);
+        return tab;
+    }
+    // ksk_twin_ew_kernel over c0 (parts & 1) and c1 (parts & 2) of a group's nb keys: the range check into the flag word
+    // and, unless check_only, the Shoup twins and F64 words.  Without check_only every word must be below its modulus.
+    void twins(const k::KskOutTable &tab, size_t nb, uint32_t parts, uint32_t check_only) const {
+        const u64 pairs = (u64)nb * PK / 2;
+        FHE_LAUNCH("ksk_twin", k::ksk_twin_ew_kernel, dim3(blocks_for(pairs, EW_THREADS)), dim3(EW_THREADS), 0, s, tab,
+                   parts, check_only, rq(), (uint32_t)nd, (uint32_t)Lk, (uint32_t)wf, kc.dmods(), (uint32_t)kc.logn, pairs,
+                   flag());
+    }
+    // reads the flag word, waiting for `s`: a word >= q_j anywhere raised it (ksk_load_wire's one wait; ksk_finish's
+    // callers wait once more before they return)
+    void check() const {
+        uint32_t bad = 0;
+        FHE_HIP_CHECK(hipMemcpyAsync(&bad, flag(), sizeof(bad), hipMemcpyDeviceToHost, s));
+        FHE_HIP_CHECK(hipStreamSynchronize(s));
+        require(!bad, E_ARG, "key coefficient not reduced");
+    }
+};
+
 // KeySwitchingKey::new (F/bfv/keys/key_switching_key.rs:71-236) for `nkeys` keys, key b with
 // rng = ChaCha8Rng::from_seed(seeds[b]): K = the rng's first 32 bytes (written to seeds_out[b] when given),
 // c1[i] = Poly::random_from_seed(ctx_ksk, bytes [32 i, 32 i + 32) of ChaCha8Rng::from_seed(K)), e_i = the rng's i-th
@@ -2989,38 +3044,16 @@ inline std::vector<std::unique_ptr<Ksk>> ksk_generate(const Ctx &ct, const Ctx &
     const auto dg = ksk_digits(ct, kc);
     const size_t nd = dg.first, lb = dg.second, Lk = kc.L, N = kc.n;
     ksk_validate(ct, kc, nd, lb);
-    std::vector<std::unique_ptr<Ksk>> keys;
+    auto keys = ksk_new_keys(ct, kc, nd, lb, nkeys);
     if (!nkeys) return keys;
-    const u64 PK = (u64)nd * Lk * N;   // words of one key array
-    const bool wf = ksk_f64_eligible(kc, lb);
-    for (size_t b = 0; b < nkeys; b++) {
-        auto k_ = make_ksk(ct, kc, nd, lb);
-        for (DevBuf<u64> *d : {&k_->c0, &k_->c0s, &k_->c1, &k_->c1s}) d->alloc(PK);
-        if (wf) {
-            k_->c0f.alloc(PK);
-            k_->c1f.alloc(PK);
-        }
-        keys.push_back(std::move(k_));
-    }
-    // the public constants: rq [Lk] {2^64 mod q_j, q_j^-1}, then g [nd][Lk]
-    WsGuard cst((2 * Lk + nd * Lk) * sizeof(u64), s);
-    k::u64x2 *rq = (k::u64x2 *)cst.p;
-    u64 *g = cst.u() + 2 * Lk;
-    FHE_LAUNCH("ksk_consts", k::ksk_consts_kernel, dim3(blocks_for(nd * Lk, 64)), dim3(64), 0, s, kc.dmods(),
-               (uint32_t)nd, (uint32_t)Lk, (uint32_t)lb, g, rq);
-    const bool whole = kc.logn <= 14;
+    const KskCall kk(kc, nd, lb, false, s);
+    const u64 PK = kk.PK;
+    const bool whole = kk.whole;
     const RowLaunch rows(kc, Lk, !f64_disabled());   // (read once per call: every transform of the call takes the same kind)
-    // groups: at most KG_KEYS keys (the output table travels in the kernel arguments) and 1 GiB of c1 scratch (256 MiB
-    // of c1 and transformed errors for larger rows), split into groups of equal size
-    const size_t group = whole ? encrypt_group(kc, nd, nkeys, (size_t)1 << 30, k::KG_KEYS)
-                               : encrypt_group(kc, 2 * nd, nkeys, (size_t)256 << 20, k::KG_KEYS);
+    const size_t group = kk.group(nkeys);   // (the c1 scratch, and the transformed errors of larger rows)
     require(group * nd * Lk <= 0x7fffffffu, E_ARG, "ksk_generate: a launch group exceeds the grid limit");
     for_groups(nkeys, group, [&](size_t b0, size_t nb) {
-        k::KskOutTable tab{};
-        for (size_t b = 0; b < nb; b++) {
-            const Ksk &kk = *keys[b0 + b];
-            tab.k[b] = k::KskOut{kk.c0.p, kk.c0s.p, kk.c1.p, kk.c1s.p, kk.c0f.p, kk.c1f.p};
-        }
+        const k::KskOutTable tab = KskCall::table(&keys[b0], nb);
         WsGuard ds(nb * nd * 32, s), c1(nb * PK * sizeof(u64), s);
         const uint8_t *sd = seeds + b0 * 32;
         FHE_LAUNCH("ksk_seeds", k::ksk_seeds_kernel, dim3(blocks_for(nb * nd, 64)), dim3(64), 0, s, sd,
@@ -3031,13 +3064,13 @@ inline std::vector<std::unique_ptr<Ksk>> ksk_generate(const Ctx &ct, const Ctx &
         if (whole)
             return rows("ksk_gen", nb * nd * Lk, s,
                         [](auto lm, auto nrw, auto h) { return kernel_c<k::ksk_gen_kernel<lm(), nrw(), h()>>{}; },
-                        d.e(), (const u64 *)c1.u(), s_ntt, fb, (const u64 *)g, (const k::u64x2 *)rq, tab, (uint32_t)nd,
-                        (uint32_t)Lk, (uint32_t)wf, kc.dmods(), rows.tw());
+                        d.e(), (const u64 *)c1.u(), s_ntt, fb, kk.g(), kk.rq(), tab, (uint32_t)nd, (uint32_t)Lk,
+                        (uint32_t)kk.wf, kc.dmods(), rows.tw());
         // rows larger than one LDS tile: the epilogue as a pass of its own over the transformed errors
         const u64 total = (u64)nb * PK;
         FHE_LAUNCH("ksk_combine", k::ksk_combine_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
-                   d.x(), (const u64 *)c1.u(), s_ntt, fb, (const u64 *)g, (const k::u64x2 *)rq, tab, (uint32_t)nd,
-                   (uint32_t)Lk, (uint32_t)wf, kc.dmods(), (uint32_t)kc.logn, total);
+                   d.x(), (const u64 *)c1.u(), s_ntt, fb, kk.g(), kk.rq(), tab, (uint32_t)nd, (uint32_t)Lk, (uint32_t)kk.wf,
+                   kc.dmods(), (uint32_t)kc.logn, total);
     });
     return keys;
 }
@@ -3115,41 +3148,18 @@ inline std::vector<std::unique_ptr<Ksk>> ksk_load_wire(const Ctx &ct, const Ctx 
     kc.need_device();
     const size_t nd = ksk_wire_digits(ct, kc, lb), Lk = kc.L, N = kc.n;
     ksk_validate(ct, kc, nd, lb);
-    std::vector<std::unique_ptr<Ksk>> keys;
+    auto keys = ksk_new_keys(ct, kc, nd, lb, nkeys);
     if (!nkeys) return keys;
-    const u64 PK = (u64)nd * Lk * N;   // words of one key array
+    const KskCall kk(kc, nd, lb, true, s);   // (ksk_consts_kernel's g is not read here)
     const u64 wb = wire_poly_bytes(kc);
-    const bool wf = ksk_f64_eligible(kc, lb);
-    for (size_t b = 0; b < nkeys; b++) {
-        auto k_ = make_ksk(ct, kc, nd, lb);
-        for (DevBuf<u64> *d : {&k_->c0, &k_->c0s, &k_->c1, &k_->c1s}) d->alloc(PK);
-        if (wf) {
-            k_->c0f.alloc(PK);
-            k_->c1f.alloc(PK);
-        }
-        keys.push_back(std::move(k_));
-    }
-    // rq [Lk] {2^64 mod q_j, q_j^-1} (ksk_consts_kernel's; its g [nd][Lk] is not read here), then the flag word
-    WsGuard cst((2 * Lk + nd * Lk + 1) * sizeof(u64), s);
-    k::u64x2 *rq = (k::u64x2 *)cst.p;
-    u64 *g = cst.u() + 2 * Lk;
-    uint32_t *flag = (uint32_t *)(g + nd * Lk);
-    FHE_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(u64), s));
-    FHE_LAUNCH("ksk_consts", k::ksk_consts_kernel, dim3(blocks_for(nd * Lk, 64)), dim3(64), 0, s, kc.dmods(),
-               (uint32_t)nd, (uint32_t)Lk, (uint32_t)lb, g, rq);
-    const bool whole = kc.logn <= 14;
+    const bool whole = kk.whole;
     const RowLaunch rows(kc, Lk, !f64_disabled());
     // the word-granular loader: rows of >= 128 coefficients and 16-byte aligned byte pointers (see ksk_load_kernel)
     const bool words = N >= 128 && ((uintptr_t)c0b & 15) == 0 && ((uintptr_t)c1b & 15) == 0;
-    const size_t group = whole ? encrypt_group(kc, nd, nkeys, (size_t)1 << 30, k::KG_KEYS)
-                               : encrypt_group(kc, 2 * nd, nkeys, (size_t)256 << 20, k::KG_KEYS);
+    const size_t group = kk.group(nkeys);
     require(2 * group * nd * Lk <= 0x7fffffffu, E_ARG, "ksk_load_wire: a launch group exceeds the grid limit");
     for_groups(nkeys, group, [&](size_t b0, size_t nb) {
-        k::KskOutTable tab{};
-        for (size_t b = 0; b < nb; b++) {
-            const Ksk &kk = *keys[b0 + b];
-            tab.k[b] = k::KskOut{kk.c0.p, kk.c0s.p, kk.c1.p, kk.c1s.p, kk.c0f.p, kk.c1f.p};
-        }
+        const k::KskOutTable tab = KskCall::table(&keys[b0], nb);
         const uint8_t *b0p = c0b + b0 * nd * wb, *b1p = c1b ? c1b + b0 * nd * wb : nullptr;
         uint32_t ew_parts = whole ? 0u : 3u;   // what ksk_twin_ew_kernel still has to do for this group
         if (K) {
@@ -3163,34 +3173,38 @@ inline std::vector<std::unique_ptr<Ksk>> ksk_load_wire(const Ctx &ct, const Ctx 
         if (whole) {
             rows("ksk_load", (b1p ? 2 : 1) * nb * nd * Lk, s,
                  [](auto lm, auto nrw, auto h) { return kernel_c<k::ksk_load_kernel<lm(), nrw(), h()>>{}; }, b0p, b1p, wb,
-                 (uint32_t)words, (const k::u64x2 *)rq, tab, (uint32_t)nd, (uint32_t)Lk, (uint32_t)(nb * nd), (uint32_t)wf,
-                 kc.dmods(), rows.tw(), flag);
+                 (uint32_t)words, kk.rq(), tab, (uint32_t)nd, (uint32_t)Lk, (uint32_t)(nb * nd), (uint32_t)kk.wf, kc.dmods(),
+                 rows.tw(), kk.flag());
         }
-        const u64 pairs = (u64)nb * PK / 2;
-        auto twins = [&](uint32_t parts, uint32_t check_only) {
-            FHE_LAUNCH("ksk_twin", k::ksk_twin_ew_kernel, dim3(blocks_for(pairs, EW_THREADS)), dim3(EW_THREADS), 0, s, tab,
-                       parts, check_only, (const k::u64x2 *)rq, (uint32_t)nd, (uint32_t)Lk, (uint32_t)wf, kc.dmods(),
-                       (uint32_t)kc.logn, pairs, flag);
-        };
         if (!whole) {
             // unpack into the handles, compare the PowerBasis words with their moduli, then transform in place
             for (size_t b = 0; b < nb; b++) {
                 wire_deserialize(kc, b0p + b * nd * wb, keys[b0 + b]->c0.p, nd, false, s);
                 if (b1p) wire_deserialize(kc, b1p + b * nd * wb, keys[b0 + b]->c1.p, nd, false, s);
             }
-            twins(b1p ? 3u : 1u, 1u);
+            kk.twins(tab, nb, b1p ? 3u : 1u, 1u);
             for (size_t b = 0; b < nb; b++) {
                 launch_ntt(kc, false, keys[b0 + b]->c0.p, keys[b0 + b]->c0.p, full_map(kc, Lk), nd, s);
                 if (b1p) launch_ntt(kc, false, keys[b0 + b]->c1.p, keys[b0 + b]->c1.p, full_map(kc, Lk), nd, s);
             }
         }
-        if (ew_parts) twins(ew_parts, 0u);
+        if (ew_parts) kk.twins(tab, nb, ew_parts, 0u);
     });
-    uint32_t bad = 0;
-    FHE_HIP_CHECK(hipMemcpyAsync(&bad, flag, sizeof(bad), hipMemcpyDeviceToHost, s));
-    FHE_HIP_CHECK(hipStreamSynchronize(s));
-    require(!bad, E_ARG, "key coefficient not reduced");
+    kk.check();
     return keys;
+}
+
+// The one way to finish a handle whose c0 and c1 already hold Ntt words on `s` (fhe_ksk_create(_dev), the multiparty
+// relinearization key).  The words are untrusted: the range check runs as a pass of its own and the call waits for `s`
+// to read its flag -- the twin pass must never see a word >= q_j -- then come the Shoup twins and, when eligible, the
+// F64 words.
+inline void ksk_finish(const Ksk &k_, hipStream_t s) {
+    const KskCall kk(*k_.ksk_ctx, k_.ndigits, k_.log_base, true, s);
+    k::KskOutTable tab{};
+    tab.k[0] = KskCall::out(k_);
+    kk.twins(tab, 1, 3u, 1u);
+    kk.check();
+    kk.twins(tab, 1, 3u, 0u);
 }
 
 // From<&KeySwitchingKey> for KeySwitchingKeyProto (:365-385): c0 (and c1 when c1b is given) taken to PowerBasis and

@@ -910,47 +910,31 @@ static std::unique_ptr<fhe_ksk> ksk_new(const fhe_ctx *ct_ctx, const fhe_ctx *ks
     need(c1, "c1");
     return h;
 }
-// Uploads the key from HOST arrays.  Every coefficient must be a canonical residue (the Shoup quotient of an unreduced
-// value does not fit 64 bits and the key would silently give wrong results); supplied twins must be the twins, missing
-// ones are computed.
-static void ksk_upload(Ksk &k_, const u64 *c0, const u64 *c0_shoup, const u64 *c1, const u64 *c1_shoup) {
-    const Ctx &kc = *k_.ksk_ctx;
-    const size_t count = k_.ndigits * kc.L * kc.n;
-    auto up = [&](DevBuf<u64> &d, const u64 *src) {
-        d.alloc(count);
-        FHE_HIP_CHECK(hipMemcpy(d.p, src, count * sizeof(u64), hipMemcpyHostToDevice));
-    };
-    auto shoup_of = [&](const u64 *src, const u64 *given) {
-        std::vector<u64> v(count);
-        for (size_t i = 0; i < k_.ndigits; i++)
-            for (size_t r = 0; r < kc.L; r++)
-                for (size_t j = 0; j < kc.n; j++) {
-                    const size_t x = (i * kc.L + r) * kc.n + j;
-                    if (src[x] >= kc.moduli[r]) throw StatusError(FHE_E_ARG, "key coefficient not reduced");
-                    v[x] = shoup(src[x], kc.moduli[r]);
-                    if (given && given[x] != v[x])
-                        throw StatusError(FHE_E_ARG, "Shoup twin is not floor(c * 2^64 / q)");
-                }
-        return v;
-    };
-    up(k_.c0, c0);
-    up(k_.c1, c1);
-    {
-        auto v = shoup_of(c0, c0_shoup);
-        up(k_.c0s, v.data());
+// The handle's arrays from its key words: c0 and c1 (host or device arrays, by `kind`) copied into it on `s`, then
+// ksk_finish.  Every coefficient must be a canonical residue (the Shoup quotient of an unreduced value does not fit 64
+// bits and the key would silently give wrong results); supplied twins (host arrays) must be the twins the device
+// wrote.  Waits for `s`: the key is usable from any stream afterwards.
+static void ksk_fill(Ksk &k_, const u64 *c0, const u64 *c0_shoup, const u64 *c1, const u64 *c1_shoup, hipMemcpyKind kind,
+                     hipStream_t s) {
+    const size_t bytes = k_.ndigits * k_.ksk_ctx->L * k_.ksk_ctx->n * sizeof(u64);
+    ksk_alloc(k_);
+    FHE_HIP_CHECK(hipMemcpyAsync(k_.c0.p, c0, bytes, kind, s));
+    FHE_HIP_CHECK(hipMemcpyAsync(k_.c1.p, c1, bytes, kind, s));
+    ksk_finish(k_, s);
+    FHE_HIP_CHECK(hipStreamSynchronize(s));
+    for (auto given : {std::make_pair(c0_shoup, k_.c0s.p), std::make_pair(c1_shoup, k_.c1s.p)}) {
+        if (!given.first) continue;
+        std::vector<u64> v(bytes / sizeof(u64));
+        FHE_HIP_CHECK(hipMemcpy(v.data(), given.second, bytes, hipMemcpyDeviceToHost));
+        require(std::memcmp(v.data(), given.first, bytes) == 0, E_ARG, "Shoup twin is not floor(c * 2^64 / q)");
     }
-    {
-        auto v = shoup_of(c1, c1_shoup);
-        up(k_.c1s, v.data());
-    }
-    ksk_fill_f64(k_, c0, c1);
 }
 fhe_status fhe_ksk_create(const fhe_ctx *ct_ctx, const fhe_ctx *ksk_ctx, size_t ndigits, const uint64_t *c0,
                           const uint64_t *c0_shoup, const uint64_t *c1, const uint64_t *c1_shoup, size_t log_base,
                           fhe_ksk **out) {
     return guard([&] {
         auto h = ksk_new(ct_ctx, ksk_ctx, ndigits, c0, c1, log_base, out);
-        ksk_upload(*h->k, c0, c0_shoup, c1, c1_shoup);
+        ksk_fill(*h->k, c0, c0_shoup, c1, c1_shoup, hipMemcpyHostToDevice, nullptr);
         *out = h.release();
     });
 }
@@ -958,13 +942,7 @@ fhe_status fhe_ksk_create_dev(const fhe_ctx *ct_ctx, const fhe_ctx *ksk_ctx, siz
                               const uint64_t *c1, size_t log_base, void *stream, fhe_ksk **out) {
     return guard([&] {
         auto h = ksk_new(ct_ctx, ksk_ctx, ndigits, c0, c1, log_base, out);
-        // the device arrays come down once and take the host path (the checks and twins are host computations)
-        const size_t count = ndigits * ksk_ctx->c->L * ksk_ctx->c->n;
-        FHE_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
-        std::vector<u64> h0(count), h1(count);
-        FHE_HIP_CHECK(hipMemcpy(h0.data(), c0, count * sizeof(u64), hipMemcpyDeviceToHost));
-        FHE_HIP_CHECK(hipMemcpy(h1.data(), c1, count * sizeof(u64), hipMemcpyDeviceToHost));
-        ksk_upload(*h->k, h0.data(), nullptr, h1.data(), nullptr);
+        ksk_fill(*h->k, c0, nullptr, c1, nullptr, hipMemcpyDeviceToDevice, as_stream(stream));
         *out = h.release();
     });
 }
@@ -2112,19 +2090,16 @@ fhe_status fhe_mbfv_relin_key_aggregate_dev(const fhe_ctx *ctx, const uint64_t *
         need(r1_h1, "r1_h1");
         set_device(c);
         hipStream_t s = as_stream(stream);
-        const size_t L = c.L, count = L * L * c.n;
+        const size_t L = c.L;
         auto h = ksk_new(ctx, ctx, L, r2_h0, r1_h1, 0, out);
-        std::vector<u64> h0(count), h1(count);
-        {
-            WsGuard c0(count * sizeof(u64), s);
-            mbfv_sum(c, r2_h0, nshares, (u64)share_stride, L, nullptr, 0, c0.u(), s);
-            mbfv_sum(c, r2_h1, nshares, (u64)share_stride, L, c0.u(), (u64)L * c.n, c0.u(), s);
-            // the key words come down once and take the host path, as in fhe_ksk_create_dev
-            FHE_HIP_CHECK(hipStreamSynchronize(s));
-            FHE_HIP_CHECK(hipMemcpy(h0.data(), c0.p, count * sizeof(u64), hipMemcpyDeviceToHost));
-            FHE_HIP_CHECK(hipMemcpy(h1.data(), r1_h1, count * sizeof(u64), hipMemcpyDeviceToHost));
-        }
-        ksk_upload(*h->k, h0.data(), nullptr, h1.data(), nullptr);
+        Ksk &k_ = *h->k;
+        ksk_alloc(k_);
+        u64 *c0 = k_.c0.p;   // the sums go straight into the handle
+        mbfv_sum(c, r2_h0, nshares, (u64)share_stride, L, nullptr, 0, c0, s);
+        mbfv_sum(c, r2_h1, nshares, (u64)share_stride, L, c0, (u64)L * c.n, c0, s);
+        FHE_HIP_CHECK(hipMemcpyAsync(k_.c1.p, r1_h1, L * L * c.n * sizeof(u64), hipMemcpyDeviceToDevice, s));
+        ksk_finish(k_, s);
+        FHE_HIP_CHECK(hipStreamSynchronize(s));   // (the call waits for `stream`, as fhe_ksk_create_dev does)
         *out = h.release();
     });
 }

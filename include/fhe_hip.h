@@ -241,7 +241,11 @@ fhe_status fhe_poly_scale_dev(const fhe_scaler *s, const uint64_t *in, uint64_t 
 fhe_status fhe_ksk_create(const fhe_ctx *ct_ctx, const fhe_ctx *ksk_ctx, size_t ndigits, const uint64_t *c0,
                           const uint64_t *c0_shoup, const uint64_t *c1, const uint64_t *c1_shoup,
                           size_t log_base, fhe_ksk **out);
-/* Same with key polynomials already resident on the device (copied device-to-device). */
+/* Same with key polynomials already resident on the device: copied device-to-device on `stream`, checked and twinned
+ * there by the pass every other route uses (no key word passes through host memory).  The words are untrusted input:
+ * the call waits for `stream` to read the range check's flag word and once more before it returns, so the key is
+ * usable from any stream afterwards.  fhe_ksk_create is the host form of this call: its arrays are uploaded and finished
+ * the same way, and a supplied twin array is compared with the twins the device wrote. */
 fhe_status fhe_ksk_create_dev(const fhe_ctx *ct_ctx, const fhe_ctx *ksk_ctx, size_t ndigits, const uint64_t *c0,
                               const uint64_t *c1, size_t log_base, void *stream, fhe_ksk **out);
 void fhe_ksk_destroy(fhe_ksk *k);
@@ -547,8 +551,8 @@ fhe_status fhe_bfv_encrypt_pk_dev(const fhe_ctx *ctx, size_t variance, const uin
 /* KeySwitchingKey::new for nkeys keys: from_ntt [nkeys][Lk][N] Ntt over ksk_ctx (the reference's `from` after the
  * forward transform), seeds [nkeys][32] -> out[nkeys] handles, seeds_out [nkeys][32] (may be NULL).  from_ntt must
  * hold canonical residues (row j below q_j), as every Ntt-form output of this library does: the words are not checked
- * on the device (fhe_ksk_create's host check would need a copy of them), and a word >= q_j gives a key whose c0 words
- * and Shoup twins are not canonical. */
+ * (fhe_ksk_create_dev's range check waits for the stream; generation never does), and a word >= q_j gives a key whose
+ * c0 words and Shoup twins are not canonical. */
 fhe_status fhe_ksk_generate_dev(const fhe_ctx *ct_ctx, const fhe_ctx *ksk_ctx, size_t variance, const uint64_t *s_ntt,
                                 const uint64_t *from_ntt, const uint8_t *seeds, size_t nkeys, uint8_t *seeds_out,
                                 void *stream, fhe_ksk **out);
@@ -593,7 +597,8 @@ size_t fhe_ksk_ndigits(const fhe_ksk *ksk);
  * The reference takes such words verbatim (Poly::from_bytes does not reduce them, convert.rs:148-160) and would compute
  * with a non-canonical key; here the Shoup quotient of an unreduced word does not fit 64 bits, so the key is refused.
  * Stream: the bytes are untrusted input, so the call waits for `stream` once, after its last launch, to read the
- * check's flag word (fhe_ksk_create_dev waits too).  Keys it returns are therefore ready on any stream.
+ * check's flag word (fhe_ksk_create_dev waits too: for the same flag word before its twin pass, and before it returns).
+ * Keys it returns are therefore ready on any stream.
  * Statuses: the geometry as fhe_ksk_create (FHE_E_DEGREE_MISMATCH, FHE_E_CONTEXT_NOT_REACHABLE,
  * FHE_E_PARAMETER_MISMATCH, FHE_E_KEYSWITCH_UNSUPPORTED, FHE_E_ARG for a bad log_base); both or neither of c1_bytes /
  * seeds, or a NULL handle or buffer with nkeys > 0 -> FHE_E_ARG; nkeys == 0 is a no-op. */
@@ -697,9 +702,10 @@ fhe_status fhe_mbfv_aggregate_dev(const fhe_ctx *ctx, const uint64_t *shares, si
                                   size_t npolys, const uint64_t *base_or_null, uint64_t *out, void *stream);
 /* RelinearizationKey::from_shares (mbfv/relin_key_gen.rs:299-351): c0[i] = sum_p r2_h0[p][i] + sum_p r2_h1[p][i],
  * c1[i] = r1_h1[i] (the aggregated round-1 h1), log_base 0, ciphertext and key level 0 (ctx).  r2_h0, r2_h1: nshares
- * arrays [L][L][N] at share_stride words; r1_h1 [L][L][N].  The handle is made as fhe_ksk_create_dev makes it (the
- * public key words come down once for the checks and Shoup twins; the call waits for `stream`).  nshares == 0 ->
- * FHE_E_ARG; a single-modulus context -> FHE_E_KEYSWITCH_UNSUPPORTED.  No draws, no secrets. */
+ * arrays [L][L][N] at share_stride words; r1_h1 [L][L][N].  The sums are written straight into the new handle's c0,
+ * r1_h1 is copied into its c1, and the handle is finished as fhe_ksk_create_dev finishes it (range check, Shoup twins
+ * and F64 words on the device; a word >= q_j -> FHE_E_ARG; the call waits for `stream`).  nshares == 0 -> FHE_E_ARG; a
+ * single-modulus context -> FHE_E_KEYSWITCH_UNSUPPORTED.  No draws, no secrets. */
 fhe_status fhe_mbfv_relin_key_aggregate_dev(const fhe_ctx *ctx, const uint64_t *r2_h0, const uint64_t *r2_h1,
                                             size_t nshares, size_t share_stride, const uint64_t *r1_h1, void *stream,
                                             fhe_ksk **out);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Key generation on the device against today's path, on the reference's stock sets n = 4096 / 8192 / 16384
+"""Key generation on the device against creation from host arrays, on the reference's stock sets n = 4096 / 8192 / 16384
 (tests/ref_params.py), the FP64 kernels on and off:
   relin_key       one RelinearizationKey.generate (fhe_bfv_relin_key_generate_dev), ms per key
   ek_pir          one EvaluationKey.generate of the PIR set (expansion level log2 N, inner sum, row rotation: one batched
@@ -8,8 +8,9 @@
 Two yardsticks from the same process ride on every record:
   sk_encrypt_per_s_over_ndigits   secret-key encryptions of a batch of 1,024 per second divided by ndigits (a key is
                                   ndigits encryptions over the key context)
-  ksk_create_host_ms              fhe_ksk_create of the same relinearization key from host arrays (the floor of today's
-                                  path: host Shoup twins, host F64 words, synchronous uploads), ms per key
+  ksk_create_host_ms              fhe_ksk_create of the same relinearization key from host arrays (what a host that
+                                  generates keys itself pays: two uploads, then the device's range check, Shoup twins
+                                  and F64 words), ms per key
 Timing: wall clock around `--reps` calls after one warm-up call, the stream synchronised before and after, median of
 three windows (key generation allocates each key's buffers on the host side, so device-event timing would miss it).
 One JSON line per record on stdout (and to --out).  Kernel times: run it under `rocprofv3 --kernel-trace --stats`."""
@@ -68,7 +69,7 @@ def main():
         pts = enc.encode(torch.from_numpy(rng.integers(0, t, size=(1024, n), dtype=np.uint64).view(np.int64)).cuda(),
                          "simd", 0, True)
         ea, ee = dev(1024, 32), dev(1024, 32)
-        # the host-path yardstick: the same key's arrays on the host, made into a handle by fhe_ksk_create
+        # the host-array yardstick: the same key's arrays on the host, made into a handle by fhe_ksk_create
         host = [x.cpu().numpy().view(np.uint64) for x in fhe.RelinearizationKey.generate(sk, s1).ksk.export()[:2]]
         for f64 in (True, False):
             fhe.set_f64(f64)

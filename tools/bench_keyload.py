@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""Loading key-switching keys from their wire bytes on the device against today's route, on the reference's stock sets
+"""Loading key-switching keys from their wire bytes on the device against the piecewise route, on the reference's stock sets
 n = 4096 / 8192 / 16384 (tests/ref_params.py), for one relinearization key and for a 22-key evaluation key, seeded (c0
 bytes + the 32-byte seed) and unseeded (c0 and c1 bytes):
   load_wire       KeySwitchingKey.from_wire (one fhe_ksk_load_wire_dev for all keys), keys per second
-  today           per key: Context.deserialize(to_ntt=True) of c0 (fhe_poly_deserialize_dev), Context.random_from_seed of
-                  the digit seeds (fhe_poly_from_seed_dev; the digit seeds themselves, a host ChaCha8 restatement in
-                  today's route, are prepared OUTSIDE the timed window, which flatters this route) or deserialize of c1,
-                  then KeySwitchingKey(c0, c1) (fhe_ksk_create_dev), keys per second
+  today           the piecewise route (the record keeps its name, so that runs stay comparable), per key:
+                  Context.deserialize(to_ntt=True) of c0 (fhe_poly_deserialize_dev), Context.random_from_seed of the
+                  digit seeds (fhe_poly_from_seed_dev; the digit seeds themselves, a host ChaCha8 restatement in this
+                  route, are prepared OUTSIDE the timed window, which flatters it) or deserialize of c1, then
+                  KeySwitchingKey(c0, c1) (fhe_ksk_create_dev: device copies, range check and twins), keys per second
 Both routes are timed in the same process, their windows alternating.  Two more figures ride on every record:
   ntt_rows_yardstick_keys_per_s   rows per second of one batched forward transform of 1,024 polynomials, divided by the
                                   rows a key transforms (ndigits x Lk, twice that with an explicit c1): what the transform
@@ -86,7 +87,7 @@ def main():
         c0b, c1b = torch.stack([w[0] for w in wire]), torch.stack([w[1] for w in wire])   # [keys, ndigits, size]
         K = [k.seed for k in gen]
         Kd = torch.from_numpy(np.frombuffer(b"".join(K), dtype=np.uint8).reshape(EK_KEYS, 32).copy()).cuda()
-        # today's route restates generate_c1 on the host: the digit seeds, prepared once, outside the timed windows
+        # the piecewise route restates generate_c1 on the host: the digit seeds, prepared once, outside the timed windows
         dseeds = [torch.from_numpy(np.frombuffer(b"".join(keygen_ref.digit_seeds(k, L)), dtype=np.uint8)
                                    .reshape(L, 32).copy()).cuda() for k in K]
         # the loaded keys are the generated ones (results must not change): checked once per set
