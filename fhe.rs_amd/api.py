@@ -1059,6 +1059,12 @@ class EvaluationKey:
         exps = sorted(self.gk)
         return exps, [self.gk[e].to_wire(seeded) for e in exps]
 
+    @staticmethod
+    def batched(eks):
+        """The evaluation keys of many clients as one `EvaluationKeySet` (keyed batches: one set per exponent); refuses
+        clients whose exponent lists differ."""
+        return EvaluationKeySet(eks)
+
     def rotates_rows(self, ct):
         e = 2 * self.degree - 1
         if e not in self.gk:
@@ -1124,6 +1130,160 @@ class EvaluationKey:
         if e not in self.gk:
             raise FheError(-11, "EvaluationKeyError::Unsupported(ColumnRotation)")
         return self.gk[e].relinearize(ct)
+
+
+class KeySet:
+    """Keyed batches (fhe_kskset): the keys of many clients for ONE operation -- every client's relinearization key, or
+    every client's Galois key of one exponent -- as `KeySwitchingKey`, `RelinearizationKey` or `GaloisKey` objects (kept
+    alive here).  A call takes a batch whose leading dimension is a multiple of len(keys): items [c * m, (c + 1) * m)
+    belong to keys[c], and the result is what one single-key call per client gives.  numpy in -> numpy out (staged
+    through the device); torch tensors and DeviceArrays are read in place."""
+
+    def __init__(self, keys):
+        self.keys = list(keys)
+        ksks = [getattr(k, "ksk", k) for k in self.keys]
+        exps = {getattr(k, "exponent", None) for k in self.keys}
+        if len(exps) > 1:
+            raise FheError(-1, "a key set holds the clients' keys of one exponent")
+        self.exponent = exps.pop() if exps else None
+        h = C.c_void_p()
+        arr = (C.c_void_p * max(len(ksks), 1))(*[k._h.value if k is not None else None for k in ksks])
+        check(_lib.lib().fhe_kskset_create(arr, len(ksks), C.byref(h)))
+        self._h = h
+        self.ctx_ciphertext, self.ctx_ksk = ksks[0].ctx_ciphertext, ksks[0].ctx_ksk
+
+    def __del__(self):
+        if getattr(self, "_h", None) is not None and _lib._lib is not None:
+            _lib._lib.fhe_kskset_destroy(self._h)
+
+    def __len__(self):
+        return int(_lib.lib().fhe_kskset_size(self._h))
+
+    def set_w_budget(self, nbytes=0):
+        """Bytes of transformed digit rows per launch pair (fhe_kskset_set_w_budget; 0 = default)."""
+        check(_lib.lib().fhe_kskset_set_w_budget(self._h, int(nbytes)))
+        return self
+
+    def w_budget(self):
+        w = C.c_size_t()
+        check(_lib.lib().fhe_kskset_get_w_budget(self._h, C.byref(w)))
+        return w.value
+
+    def _run(self, x, oshapes, call):
+        """Stages `x`, allocates one output per shape, runs call(x, outs) and hands the outputs back in x's kind."""
+        host = not _is_dev(x)
+        d = DeviceArray.from_numpy(_np(x), max(self.ctx_ksk.device, 0)) if host else x
+        outs = [DeviceArray(sh, d.device) if host else _empty_dev(d, sh) for sh in oshapes]
+        check(call(d, outs))
+        return [o.download() if host else o for o in outs]
+
+    def key_switch(self, p):
+        """KeySwitchingKey::key_switch per client: p [batch, L, N] PowerBasis -> (c0, c1) [batch, Lk, N] Ntt."""
+        L = _lib.lib()
+        b = self.ctx_ciphertext._batch(p)
+        oshape = tuple(p.shape[:-2]) + (self.ctx_ksk.nmoduli, self.ctx_ksk.degree)
+        o0, o1 = self._run(p, [oshape, oshape], lambda d, o: L.fhe_key_switch_keyed_dev(
+            self._h, _dptr(d), _dptr(o[0]), _dptr(o[1]), b, _stream()))
+        return o0, o1
+
+    def relinearizes(self, ct3):
+        """RelinearizationKey::relinearizes per client: [batch, 3, L, N] Ntt -> [batch, 2, L, N] Ntt."""
+        L = _lib.lib()
+        ctx = self.ctx_ciphertext
+        if ct3.shape[-3] != 3:
+            raise FheError(-13, "InvalidPolynomialCount: relinearization expects 3 parts")
+        b = ctx._batch(ct3) // 3
+        oshape = tuple(ct3.shape[:-3]) + (2, ctx.nmoduli, ctx.degree)
+        return self._run(ct3, [oshape], lambda d, o: L.fhe_bfv_relinearize_keyed_dev(
+            self._h, _dptr(d), _dptr(o[0]), b, _stream()))[0]
+
+    def relinearize(self, exponent, ct, out=None):
+        """GaloisKey::relinearize per client with the clients' keys of `exponent`: [batch, 2, L, N] Ntt -> same shape.
+        out (device arrays only): where to write; `out is ct` rotates in place."""
+        L = _lib.lib()
+        ctx = self.ctx_ciphertext
+        if ct.shape[-3] != 2:
+            raise FheError(-13, "InvalidPolynomialCount: rotation expects 2 parts")
+        e = int(exponent) % (2 * ctx.degree)
+        if e & 1 == 0:
+            raise FheError(-10, "InvalidSubstitutionExponent")
+        if self.exponent is not None and self.exponent != e:
+            raise FheError(-1, "the set holds the Galois keys of exponent %d, not %d" % (self.exponent, e))
+        b = ctx._batch(ct) // 2
+        if out is not None:
+            check(L.fhe_bfv_galois_keyed_dev(self._h, e, _dptr(ct), _dptr(out), b, _stream()))
+            return out
+        return self._run(ct, [tuple(ct.shape)], lambda d, o: L.fhe_bfv_galois_keyed_dev(
+            self._h, e, _dptr(d), _dptr(o[0]), b, _stream()))[0]
+
+
+class EvaluationKeySet:
+    """`EvaluationKey.batched(eks)`: the rotation keys of many clients, one `KeySet` per Galois exponent.  Each method
+    is the `EvaluationKey` method of the same name applied client by client to a batch whose leading dimension is a
+    multiple of the client count (items [c * m, (c + 1) * m) belong to client c)."""
+
+    def __init__(self, eks):
+        eks = list(eks)
+        if not eks:
+            raise FheError(-1, "a key set needs at least one key")
+        exps = sorted(eks[0].gk)
+        if any(sorted(ek.gk) != exps or ek.degree != eks[0].degree for ek in eks):
+            raise FheError(-1, "the clients' evaluation keys differ in their Galois exponents")
+        self.degree, self.nclients = eks[0].degree, len(eks)
+        self.sets = {e: KeySet([ek.gk[e] for ek in eks]) for e in exps}
+
+    def _need(self, exps, what):
+        if any(e not in self.sets for e in exps):
+            raise FheError(-11, "EvaluationKeyError::Unsupported(%s)" % what)
+
+    def rotates_rows(self, ct):
+        e = 2 * self.degree - 1
+        self._need([e], "RowRotation")
+        return self.sets[e].relinearize(e, ct)
+
+    def rotates_columns_by(self, ct, i):
+        if not (1 <= i < self.degree // 2):
+            raise FheError(-1, "InvalidRotationStep")
+        e = pow(3, i, 2 * self.degree)
+        self._need([e], "ColumnRotation")
+        return self.sets[e].relinearize(e, ct)
+
+    def computes_inner_sum(self, ct):
+        """EvaluationKey::computes_inner_sum (evaluation_key.rs:56-100) per client."""
+        n = self.degree
+        seq, i = [], 1
+        while i < n // 2:
+            seq.append(pow(3, i, 2 * n))
+            i *= 2
+        seq.append(2 * n - 1)
+        self._need(seq, "InnerSum")
+        L = _lib.lib()
+        handles = (C.c_void_p * len(seq))(*[self.sets[e]._h.value for e in seq])
+        exps = (C.c_size_t * len(seq))(*seq)
+        first = self.sets[seq[0]]
+        b = first.ctx_ciphertext._batch(ct) // 2
+        return first._run(ct, [tuple(ct.shape)], lambda d, o: L.fhe_bfv_inner_sum_keyed_dev(
+            handles, exps, len(seq), _dptr(d), _dptr(o[0]), b, _stream()))[0]
+
+    def supports_expansion(self, level):
+        return level <= self.degree.bit_length() - 1 and all((self.degree >> l) + 1 in self.sets for l in range(level))
+
+    def expands(self, ct, size):
+        """EvaluationKey::expands (evaluation_key.rs:192-256) per client: ct [batch, 2, L, N] ->
+        [size, batch, 2, L, N]."""
+        if size == 0 or size > self.degree:
+            raise FheError(-20, "InvalidExpansionSize")
+        level = (size - 1).bit_length()
+        if not self.supports_expansion(level):
+            raise FheError(-21, "EvaluationKeyError::Unsupported(Expansion)")
+        if level == 0:
+            return (ct.clone() if _is_dev(ct) else _np(ct).copy())[None]
+        L = _lib.lib()
+        handles = (C.c_void_p * level)(*[self.sets[(self.degree >> l) + 1]._h.value for l in range(level)])
+        first = self.sets[self.degree + 1]
+        b = first.ctx_ciphertext._batch(ct) // 2
+        return first._run(ct, [(size,) + tuple(ct.shape)], lambda d, o: L.fhe_bfv_expand_keyed_dev(
+            handles, level, _dptr(d), _dptr(o[0]), size, b, _stream()))[0]
 
 
 class RGSWCiphertext:

@@ -1464,6 +1464,48 @@ struct Ksk {
 };
 enum : int { KS_AUTO = 0, KS_FUSED = 1, KS_UNFUSED = 2, KS_UNFUSED_SUB = 3, KS_FUSED_SUB = 4 };
 
+// Keyed batches: the keys of many clients for ONE operation (every client's relinearization key, or every client's
+// Galois key of one exponent), applied to a batch in which items [c * m, (c + 1) * m) belong to key c.  The keys are
+// borrowed (they outlive the set); `table` holds their (c0, c1) pointers on the device, built once at creation (one
+// upload, one wait), which is what ks_mac_keyed_kernel indexes.  The keyed key switch rests on the unfused form, whose
+// stage A reads no key: only RNS-digit keys of one geometry can share its launches.
+struct KskSet {
+    std::vector<const Ksk *> keys;
+    DevBuf<k::KsKeyPtr> table;   // [nkeys]
+    const Ctx *ct_ctx = nullptr, *ksk_ctx = nullptr;
+    size_t ndigits = 0;
+    std::atomic<size_t> w_budget{0};   // as Ksk::w_budget; 0 = default
+};
+// The trailing optional argument of key_switch_polys / key_switch_add / galois_apply (one), inner_sum (one per rotation)
+// and expand (one per level): polynomial b of the call takes key (b / per_key) % nkeys of `set`.
+struct KsKeyed {
+    const KskSet *set = nullptr;
+    size_t per_key = 0;
+};
+inline std::unique_ptr<KskSet> kskset_create(const Ksk *const *keys, size_t nkeys) {
+    require(keys != nullptr && nkeys > 0, E_ARG, "a key set needs at least one key");
+    for (size_t i = 0; i < nkeys; i++) require(keys[i] != nullptr, E_ARG, "null argument: keys[i]");
+    const Ksk &k0 = *keys[0];
+    auto set = std::make_unique<KskSet>();
+    std::vector<k::KsKeyPtr> tab(nkeys);
+    for (size_t i = 0; i < nkeys; i++) {
+        const Ksk &ki = *keys[i];
+        require(ki.log_base == 0, E_ARG, "keyed batches take RNS-digit keys");
+        // (one parameter set, one (ciphertext level, key level) pair: stage A and the moduli tables are the first key's)
+        require(ki.ct_ctx->same_ring(*k0.ct_ctx) && ki.ksk_ctx->same_ring(*k0.ksk_ctx) && ki.ndigits == k0.ndigits &&
+                    ki.ksk_ctx->device == k0.ksk_ctx->device && ki.ksk_ctx->same_tables(*k0.ksk_ctx, k0.ksk_ctx->L),
+                E_PARAMETER_MISMATCH, "keyed batches: the keys differ in parameters, levels or digit count");
+        tab[i] = k::KsKeyPtr{ki.c0.p, ki.c1.p};
+        set->keys.push_back(&ki);
+    }
+    k0.ksk_ctx->need_device();
+    set->ct_ctx = k0.ct_ctx;
+    set->ksk_ctx = k0.ksk_ctx;
+    set->ndigits = k0.ndigits;
+    set->table.upload(tab);
+    return set;
+}
+
 // Does a key over `kc` with these digits carry the F64 words (c0f, c1f)?  RNS digits, the device's F64 tables, and every
 // key modulus below 2^50 (so that a canonical key word is an exact double).  Every route asks here: generation
 // (ksk_generate), the wire loader (ksk_load_wire) and creation from given words (ksk_finish).
@@ -1813,6 +1855,65 @@ inline void key_switch_polys_unfused(const Ksk &k_, int mode, const u64 *p, u64 
     }
 }
 
+// The keyed form (KskSet, kernels_kskeyed.hpp): key_switch_polys_unfused with ks_mac_keyed_kernel as its stage B.  The
+// geometry is that function's, unchanged -- tile choice (no extra rows here), `narrow`, `rns`, the W budget rule with equal
+// chunks and equal key-modulus groups -- and stage A is launch_ks_ntt, which reads only the key-independent fields of the
+// first key.  Each stage-B launch is told the index of its first polynomial within the call, so a chunk of polynomials
+// need not end on a key boundary.
+inline void key_switch_polys_keyed(const KskSet &set, size_t per_key, const u64 *p, u64 p_stride, u64 *o0, u64 *o1,
+                                   u64 out_stride, const u64 *a0, const u64 *a1, u64 a_stride, size_t npolys,
+                                   hipStream_t s, const u64 *xhat, u64 xhat_stride, uint32_t gal) {
+    const Ksk &k_ = *set.keys[0];
+    const Ctx &kc = *set.ksk_ctx;
+    kc.need_device();
+    require(per_key > 0, E_ARG, "keyed batches: at least one polynomial per key");
+    if (!npolys) return;
+    const size_t N = kc.n, nd = set.ndigits, Lk = kc.L, nkeys = set.keys.size();
+    const uint32_t logn = (uint32_t)kc.logn;
+    const bool sub14 = logn == 14 && 2 * npolys * nd * Lk <= (size_t)device_cus(kc.device);
+    const uint32_t logm = logn > 14 ? 13 : sub14 ? 13 : logn;
+    const uint32_t g0 = logn - logm;
+    const bool narrow = !FHE_LAB_FLAG("NO_NARROW") && kc.below_2p60(0, kc.L);
+    const bool rns = k_.digit_arg() == (1u << 8);
+    size_t budget = set.w_budget.load(std::memory_order_relaxed);
+    if (!budget) budget = KS_W_BUDGET_DEFAULT;
+    const size_t row_bytes = N * sizeof(u64);
+    size_t pc = npolys, jg = Lk;
+    if (pc * nd * jg * row_bytes > budget) {
+        jg = std::max<size_t>(1, budget / (pc * nd * row_bytes));
+        if (jg > Lk) jg = Lk;
+        if (pc * nd * jg * row_bytes > budget) pc = std::max<size_t>(1, budget / (nd * jg * row_bytes));
+    }
+    jg = (Lk + ((Lk + jg - 1) / jg) - 1) / ((Lk + jg - 1) / jg);
+    pc = (npolys + ((npolys + pc - 1) / pc) - 1) / ((npolys + pc - 1) / pc);
+    WsGuard w(pc * nd * jg * row_bytes, s);
+    const uint32_t skip_own = xhat != nullptr ? 1u : 0u;
+    for (size_t b0 = 0; b0 < npolys; b0 += pc) {
+        const size_t nb = std::min(pc, npolys - b0);
+        for (size_t j0 = 0; j0 < Lk; j0 += jg) {
+            const size_t njg = std::min(jg, Lk - j0);
+            const unsigned grid_a = (unsigned)((nb * nd * njg) << g0);
+            const u64 *pp = p + b0 * p_stride;
+            auto stage_a = [&](auto lm, auto g) {
+                launch_ks_ntt<decltype(lm)::value, decltype(g)::value>(k_, narrow, rns, grid_a, s, pp, p_stride, w.u(), (uint32_t)j0,
+                                                                       (uint32_t)njg, skip_own, nullptr);
+            };
+            if (g0 == 0)
+                with_logn<3, 14>(logm, "unsupported key-switch row size", [&](auto lm) { stage_a(lm, int_c<0>{}); });
+            else if (g0 == 1) stage_a(int_c<13>{}, int_c<1>{});
+            else if (g0 == 2) stage_a(int_c<13>{}, int_c<2>{});
+            else stage_a(int_c<13>{}, int_c<3>{});
+            const uint32_t cpr = N >= 512 ? (uint32_t)(N / 512) : 1u;
+            const unsigned grid_b = (unsigned)((((njg * cpr) + 7) / 8) * nb * 8);
+            FHE_LAUNCH("ks_mac_keyed", k::ks_mac_keyed_kernel, dim3(grid_b), dim3(256), 0, s, w.u(), o0 + b0 * out_stride,
+                       o1 + b0 * out_stride, out_stride, a0 ? a0 + b0 * a_stride : nullptr, a1 ? a1 + b0 * a_stride : nullptr,
+                       a_stride, set.table.p, (uint32_t)nkeys, (uint32_t)per_key, (uint32_t)b0, kc.dmods(), (uint32_t)nd,
+                       (uint32_t)Lk, (uint32_t)j0, (uint32_t)njg, logn, xhat ? xhat + b0 * xhat_stride : nullptr, xhat_stride,
+                       (uint32_t)nb, gal);
+        }
+    }
+}
+
 // KeySwitchingKey::key_switch (:241-320): p [npolys][L][N] PowerBasis (poly stride p_stride) ->
 // o0,o1 [npolys][Lk][N] Ntt over ksk_ctx (poly stride out_stride).  If a0/a1 are given (and the
 // key lives at the ciphertext level) the result is added to them on the fly.
@@ -1827,9 +1928,15 @@ inline void key_switch_polys_unfused(const Ksk &k_, int mode, const u64 *p, u64 
 inline void key_switch_polys(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0, u64 *o1, u64 out_stride,
                              const u64 *a0, const u64 *a1, u64 a_stride, size_t npolys, hipStream_t s,
                              const u64 *xhat = nullptr, u64 xhat_stride = 0, uint32_t gal = 0,
-                             const KsExtraFwd *extra = nullptr) {
+                             const KsExtraFwd *extra = nullptr, const KsKeyed *keyed = nullptr) {
     if (FHE_LAB_FLAG("NO_KS_XHAT") && !gal) xhat = nullptr;
     require(!gal || (xhat != nullptr && a1 == nullptr), E_ARG, "galois key switch: needs the Ntt rows, adds to c0 only");
+    if (keyed != nullptr) {   // one key per group of polynomials: `k_` is the set's first key
+        require(extra == nullptr, E_ARG, "keyed batches take no extra rows");
+        key_switch_polys_keyed(*keyed->set, keyed->per_key, p, p_stride, o0, o1, out_stride, a0, a1, a_stride, npolys, s, xhat,
+                               xhat_stride, gal);
+        return;
+    }
     const Ctx &kc = *k_.ksk_ctx;
     kc.need_device();
     if (!npolys) return;
@@ -1961,11 +2068,12 @@ inline void switch_down_to_ntt(const Ctx &from, size_t iters, const u64 *in, u64
 inline void key_switch_add(const Ksk &k_, const u64 *p, u64 p_stride, const u64 *a0, const u64 *a1, u64 a_stride,
                            u64 *out0, u64 *out1, u64 out_stride, size_t npolys, hipStream_t s,
                            const u64 *xhat = nullptr, u64 xhat_stride = 0, uint32_t gal = 0,
-                           const KsExtraFwd *extra = nullptr) {
+                           const KsExtraFwd *extra = nullptr, const KsKeyed *keyed = nullptr) {
     const Ctx &kc = *k_.ksk_ctx, &cc = *k_.ct_ctx;
     const long iters = kc.niterations_to(cc);
     if (iters == 0) {
-        key_switch_polys(k_, p, p_stride, out0, out1, out_stride, a0, a1, a_stride, npolys, s, xhat, xhat_stride, gal, extra);
+        key_switch_polys(k_, p, p_stride, out0, out1, out_stride, a0, a1, a_stride, npolys, s, xhat, xhat_stride, gal, extra,
+                         keyed);
         return;
     }
     require(extra == nullptr, E_ARG, "extra rows ride only on a key switch at the ciphertext's level");
@@ -1973,7 +2081,8 @@ inline void key_switch_add(const Ksk &k_, const u64 *p, u64 p_stride, const u64 
     const u64 kstride = (u64)kc.L * kc.n, cstride = (u64)cc.L * cc.n;
     WsGuard r0(npolys * kstride * sizeof(u64), s), r1(npolys * kstride * sizeof(u64), s);
     WsGuard d0(npolys * cstride * sizeof(u64), s), d1(npolys * cstride * sizeof(u64), s);
-    key_switch_polys(k_, p, p_stride, r0.u(), r1.u(), kstride, nullptr, nullptr, 0, npolys, s, xhat, xhat_stride);
+    key_switch_polys(k_, p, p_stride, r0.u(), r1.u(), kstride, nullptr, nullptr, 0, npolys, s, xhat, xhat_stride, 0, nullptr,
+                     keyed);
     switch_down_to_ntt(kc, (size_t)iters, r0.u(), d0.u(), npolys, s);
     switch_down_to_ntt(kc, (size_t)iters, r1.u(), d1.u(), npolys, s);
     // out = a + d  (strided copy of a -- or of d when there is no addend -- then add)
@@ -2033,7 +2142,9 @@ inline void mul_plain(const Ctx &c, size_t nparts, const u64 *ct, const u64 *pt,
 }
 
 // GaloisKey::relinearize (F/bfv/keys/galois_key.rs:63-86): ct, out [batch][2][L][N] Ntt
-inline void galois_apply(const Ksk &ks, size_t exponent, const u64 *ct, u64 *out, size_t batch, hipStream_t s) {
+// keyed (optional): ciphertext b under key (b / per_key) % nkeys of the set; `ks` is then the set's first key
+inline void galois_apply(const Ksk &ks, size_t exponent, const u64 *ct, u64 *out, size_t batch, hipStream_t s,
+                         const KsKeyed *keyed = nullptr) {
     const Ctx &cc = *ks.ct_ctx;
     const u64 PL = (u64)cc.L * cc.n;
     if (!batch) return;
@@ -2054,7 +2165,8 @@ inline void galois_apply(const Ksk &ks, size_t exponent, const u64 *ct, u64 *out
         m.dst_poly_stride = PL;
         m.subst_exp = (uint32_t)e;
         launch_ntt(cc, true, ct + PL, c2.u(), m, batch, s);
-        key_switch_add(ks, c2.u(), PL, ct, nullptr, 2 * PL, out, out + PL, 2 * PL, batch, s, ct + PL, 2 * PL, (uint32_t)e);
+        key_switch_add(ks, c2.u(), PL, ct, nullptr, 2 * PL, out, out + PL, 2 * PL, batch, s, ct + PL, 2 * PL, (uint32_t)e,
+                       nullptr, keyed);
         return;
     }
     // substitute both parts at once: sub [b][2][L][N]; c2 = PowerBasis(substitute(c1))
@@ -2066,7 +2178,8 @@ inline void galois_apply(const Ksk &ks, size_t exponent, const u64 *ct, u64 *out
     launch_ntt(cc, true, sub.u() + PL, c2.u(), m, batch, s);
     // out0 = key_switch0 + substitute(c0) ; out1 = key_switch1   (galois_key.rs:66-79)
     // (substitute(c1) in Ntt form doubles as the transforms of digit j under key modulus j)
-    key_switch_add(ks, c2.u(), PL, sub.u(), nullptr, 2 * PL, out, out + PL, 2 * PL, batch, s, sub.u() + PL, 2 * PL);
+    key_switch_add(ks, c2.u(), PL, sub.u(), nullptr, 2 * PL, out, out + PL, 2 * PL, batch, s, sub.u() + PL, 2 * PL, 0,
+                   nullptr, keyed);
 }
 
 // `&Ciphertext * &RGSWCiphertext` (F/bfv/rgsw_ciphertext.rs:122-156)
@@ -2087,8 +2200,9 @@ inline void rgsw_mul(const Ksk &k0, const Ksk &k1, const u64 *ct, u64 *out, size
 }
 
 // EvaluationKey::computes_inner_sum (F/bfv/keys/evaluation_key.rs:56-100)
+// keyed (optional): one set per rotation, keyed[i] next to gks[i] (the set's first key)
 inline void inner_sum(const Ksk *const *gks, const size_t *exps, size_t ngk, const u64 *ct, u64 *out, size_t batch,
-                      hipStream_t s) {
+                      hipStream_t s, const KsKeyed *keyed = nullptr) {
     require(ngk > 0, E_ARG, "inner sum needs at least one Galois key");
     const Ctx &cc = *gks[0]->ct_ctx;
     cc.need_device();
@@ -2098,7 +2212,7 @@ inline void inner_sum(const Ksk *const *gks, const size_t *exps, size_t ngk, con
     FHE_HIP_CHECK(hipMemcpyAsync(out, ct, total * sizeof(u64), hipMemcpyDeviceToDevice, s));
     for (size_t i = 0; i < ngk; i++) {
         require(gks[i]->ct_ctx->same_ring(cc), E_PARAMETER_MISMATCH, "inner sum: Galois keys of different levels");
-        galois_apply(*gks[i], exps[i], out, tmp.u(), batch, s);
+        galois_apply(*gks[i], exps[i], out, tmp.u(), batch, s, keyed ? keyed + i : nullptr);
         ew_op(cc, out, tmp.u(), batch * 2, k::EW_ADD, s);
     }
 }
@@ -2150,8 +2264,10 @@ inline void decrypt(const Scaler &sc, u64 t, const u64 *s_ntt, const u64 *ct, si
 // EvaluationKey::expands (F/bfv/keys/evaluation_key.rs:192-256): ct [batch][2][L][N] ->
 // out [size][batch][2][L][N] (slot-major, so that the 2^l * batch ciphertexts a level works on
 // are contiguous and go through one batched Galois key switch).
+// keyed (optional): one set per level, keyed[l] next to gks[l] (the set's first key), each with batch == nkeys * per_key:
+// level l works on 2^l * batch slot-major items, and (item / per_key) % nkeys maps each back to its client.
 inline void expand(const Ksk *const *gks, size_t nlevels, const u64 *ct, u64 *out, size_t size, size_t batch,
-                   hipStream_t s) {
+                   hipStream_t s, const KsKeyed *keyed = nullptr) {
     require(nlevels > 0, E_ARG, "expansion needs at least one Galois key");
     const Ctx &cc = *gks[0]->ct_ctx;
     cc.need_device();
@@ -2178,7 +2294,7 @@ inline void expand(const Ksk *const *gks, size_t nlevels, const u64 *ct, u64 *ou
     for (size_t l = 0; l < level; l++) {
         const size_t step = (size_t)1 << l, cnt = step * batch;
         const size_t nhigh = std::min(step, size - step) * batch;
-        galois_apply(*gks[l], (cc.n >> l) + 1, out, sub.u(), cnt, s);
+        galois_apply(*gks[l], (cc.n >> l) + 1, out, sub.u(), cnt, s, keyed ? keyed + l : nullptr);
         FHE_LAUNCH("expand_step", k::expand_step_kernel, dim3(blocks_for(PL, EW_THREADS), (unsigned)(cnt * 2)),
                    dim3(EW_THREADS), 0, s, out, sub.u(), out + step * batch * CT, mono.u() + l * PL, cc.dmods(),
                    (uint32_t)cc.logn, PL, (uint32_t)(nhigh * 2));

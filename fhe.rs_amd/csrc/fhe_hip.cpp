@@ -28,6 +28,9 @@ struct fhe_scaler {
 struct fhe_ksk {
     std::unique_ptr<Ksk> k;
 };
+struct fhe_kskset {
+    std::unique_ptr<KskSet> s;
+};
 struct fhe_mul {
     std::unique_ptr<Mul> m;
     // scalers created by fhe_mul_create_default are owned here
@@ -991,6 +994,20 @@ fhe_status fhe_key_switch_dev(const fhe_ksk *k_, const uint64_t *p, uint64_t *c0
     return dev_call<KeySwitch>(stream, k_, p, c0_out, c1_out, batch);
 }
 
+// RelinearizationKey::relinearizes on device arrays; keyed (optional): ciphertext b under key (b / per_key) % nkeys of the
+// set, `ks` then being the set's first key
+static void relinearize_polys(const Ksk &ks, const u64 *ct3, u64 *out, size_t n, hipStream_t s, const KsKeyed *keyed = nullptr) {
+    const Ctx &cc = *ks.ct_ctx;
+    const u64 PL = (u64)cc.L * cc.n;
+    if (!n) return;
+    WsGuard c2(n * PL * sizeof(u64), s);
+    k::RowMap m = full_map(cc, cc.L);
+    m.src_poly_stride = 3 * PL;
+    m.dst_poly_stride = PL;
+    launch_ntt(cc, true, ct3 + 2 * PL, c2.u(), m, n, s);
+    // (c2 in Ntt form doubles as the transforms of digit j under key modulus j)
+    key_switch_add(ks, c2.u(), PL, ct3, ct3 + PL, 3 * PL, out, out + PL, 2 * PL, n, s, ct3 + 2 * PL, 3 * PL, 0, nullptr, keyed);
+}
 struct Relinearize : Paired {   // RelinearizationKey::relinearizes: ct3 [b][3][L][N] -> out [b][2][L][N]
     static constexpr bool sliced = true;
     const Ksk *ks;
@@ -1006,19 +1023,7 @@ struct Relinearize : Paired {   // RelinearizationKey::relinearizes: ct3 [b][3][
         const size_t pe = ks->ct_ctx->L * ks->ct_ctx->n;
         io = {Io::in(ct3, batch, 3 * pe), Io::out(out, batch, 2 * pe)};
     }
-    void run(const Ptrs<2> &d, size_t n, hipStream_t s) const {
-        const Ctx &cc = *ks->ct_ctx;
-        const u64 PL = (u64)cc.L * cc.n;
-        const u64 *ct3 = d[0];
-        if (!n) return;
-        WsGuard c2(n * PL * sizeof(u64), s);
-        k::RowMap m = full_map(cc, cc.L);
-        m.src_poly_stride = 3 * PL;
-        m.dst_poly_stride = PL;
-        launch_ntt(cc, true, ct3 + 2 * PL, c2.u(), m, n, s);
-        // (c2 in Ntt form doubles as the transforms of digit j under key modulus j)
-        key_switch_add(*ks, c2.u(), PL, ct3, ct3 + PL, 3 * PL, d[1], d[1] + PL, 2 * PL, n, s, ct3 + 2 * PL, 3 * PL);
-    }
+    void run(const Ptrs<2> &d, size_t n, hipStream_t s) const { relinearize_polys(*ks, d[0], d[1], n, s); }
 };
 fhe_status fhe_bfv_relinearize(const fhe_ksk *rk, const uint64_t *ct3, uint64_t *out, size_t batch) {
     return host_call<Relinearize>(rk, ct3, out, batch);
@@ -1311,6 +1316,135 @@ fhe_status fhe_bfv_expand(const fhe_ksk *const *gks, size_t nlevels, const uint6
 fhe_status fhe_bfv_expand_dev(const fhe_ksk *const *gks, size_t nlevels, const uint64_t *ct, uint64_t *out, size_t size,
                               size_t batch, void *stream) {
     return dev_call<Expand>(stream, gks, nlevels, ct, out, size, batch);
+}
+
+// ------------------------------------------------------------------- keyed batches ----
+// One key per client (KskSet): device-pointer forms only.  Checks in the order of the paired calls: handles, the batch
+// against the set's size, then the buffers; an empty batch is a no-op.
+fhe_status fhe_kskset_create(const fhe_ksk *const *keys, size_t nkeys, fhe_kskset **out) {
+    return guard([&] {
+        need(out, "out");
+        *out = nullptr;
+        if (nkeys == 0) throw StatusError(FHE_E_ARG, "a key set needs at least one key");
+        need(keys, "keys");
+        std::vector<const Ksk *> v;
+        for (size_t i = 0; i < nkeys; i++) {
+            need(keys[i], "keys[i]");
+            v.push_back(keys[i]->k.get());
+        }
+        set_device(*v[0]->ksk_ctx);
+        auto h = std::make_unique<fhe_kskset>();
+        h->s = kskset_create(v.data(), v.size());
+        *out = h.release();
+    });
+}
+void fhe_kskset_destroy(fhe_kskset *s) { delete s; }
+size_t fhe_kskset_size(const fhe_kskset *s) { return s ? s->s->keys.size() : 0; }
+fhe_status fhe_kskset_set_w_budget(fhe_kskset *s, size_t bytes) {
+    return guard([&] {
+        need(s, "set");
+        s->s->w_budget.store(bytes, std::memory_order_relaxed);
+    });
+}
+fhe_status fhe_kskset_get_w_budget(const fhe_kskset *s, size_t *bytes) {
+    return guard([&] {
+        need(s, "set");
+        need(bytes, "bytes");
+        *bytes = s->s->w_budget.load(std::memory_order_relaxed);
+    });
+}
+// The checks every keyed call shares; returns items per key (0: nothing to do).
+static size_t keyed_per_key(const KskSet &set, size_t batch) {
+    set.ksk_ctx->need_device();
+    const size_t nkeys = set.keys.size();
+    if (batch % nkeys != 0)
+        throw StatusError(FHE_E_ARG, "keyed batches: batch " + std::to_string(batch) + " is not a multiple of the set's " +
+                                         std::to_string(nkeys) + " keys");
+    set_device(*set.ksk_ctx);
+    return batch / nkeys;
+}
+// A list of sets (one per rotation / level) of one size; returns their first keys next to the KsKeyed entries.
+static void keyed_list(const fhe_kskset *const *gks, size_t n, const char *empty, size_t batch, std::vector<const Ksk *> &first,
+                       std::vector<KsKeyed> &keyed) {
+    need(gks, "gks");
+    if (n == 0) throw StatusError(FHE_E_ARG, empty);
+    for (size_t i = 0; i < n; i++) need(gks[i], "gks[i]");
+    for (size_t i = 0; i < n; i++) {
+        const KskSet &set = *gks[i]->s;
+        if (set.keys.size() != gks[0]->s->keys.size())
+            throw StatusError(FHE_E_PARAMETER_MISMATCH, "keyed batches: the sets of one call must have the same size");
+        first.push_back(set.keys[0]);
+        keyed.push_back(KsKeyed{&set, 0});
+    }
+    const size_t m = keyed_per_key(*gks[0]->s, batch);
+    for (KsKeyed &kd : keyed) kd.per_key = m;
+}
+fhe_status fhe_key_switch_keyed_dev(const fhe_kskset *s, const uint64_t *p, uint64_t *c0_out, uint64_t *c1_out, size_t batch,
+                                    void *stream) {
+    return guard([&] {
+        need(s, "set");
+        const KskSet &set = *s->s;
+        const size_t m = keyed_per_key(set, batch);
+        if (!batch) return;
+        need(p, "p");
+        need(c0_out, "c0_out");
+        need(c1_out, "c1_out");
+        const KsKeyed kd{&set, m};
+        key_switch_polys(*set.keys[0], p, (u64)set.ct_ctx->L * set.ct_ctx->n, c0_out, c1_out, (u64)set.ksk_ctx->L * set.ksk_ctx->n,
+                         nullptr, nullptr, 0, batch, as_stream(stream), nullptr, 0, 0, nullptr, &kd);
+    });
+}
+fhe_status fhe_bfv_relinearize_keyed_dev(const fhe_kskset *rks, const uint64_t *ct3, uint64_t *out, size_t batch,
+                                         void *stream) {
+    return guard([&] {
+        need(rks, "rks");
+        const KskSet &set = *rks->s;
+        const size_t m = keyed_per_key(set, batch);
+        if (!batch) return;
+        need(ct3, "ct3");
+        need(out, "out");
+        const KsKeyed kd{&set, m};
+        relinearize_polys(*set.keys[0], ct3, out, batch, as_stream(stream), &kd);
+    });
+}
+fhe_status fhe_bfv_galois_keyed_dev(const fhe_kskset *gks, size_t exponent, const uint64_t *ct, uint64_t *out, size_t batch,
+                                    void *stream) {
+    return guard([&] {
+        need(gks, "gks");
+        const KskSet &set = *gks->s;
+        const size_t m = keyed_per_key(set, batch);
+        if (!batch) return;
+        need(ct, "ct");
+        need(out, "out");
+        const KsKeyed kd{&set, m};
+        galois_apply(*set.keys[0], exponent, ct, out, batch, as_stream(stream), &kd);
+    });
+}
+fhe_status fhe_bfv_inner_sum_keyed_dev(const fhe_kskset *const *gks, const size_t *exponents, size_t ngk, const uint64_t *ct,
+                                       uint64_t *out, size_t batch, void *stream) {
+    return guard([&] {
+        need(exponents, "exponents");
+        std::vector<const Ksk *> first;
+        std::vector<KsKeyed> keyed;
+        keyed_list(gks, ngk, "inner sum needs at least one Galois key", batch, first, keyed);
+        if (!batch) return;
+        need(ct, "ct");
+        need(out, "out");
+        inner_sum(first.data(), exponents, ngk, ct, out, batch, as_stream(stream), keyed.data());
+    });
+}
+fhe_status fhe_bfv_expand_keyed_dev(const fhe_kskset *const *gks, size_t nlevels, const uint64_t *ct, uint64_t *out, size_t size,
+                                    size_t batch, void *stream) {
+    return guard([&] {
+        std::vector<const Ksk *> first;
+        std::vector<KsKeyed> keyed;
+        keyed_list(gks, nlevels, "expansion needs at least one Galois key", batch, first, keyed);
+        if (batch && size) {
+            need(ct, "ct");
+            need(out, "out");
+        }
+        expand(first.data(), nlevels, ct, out, size, batch, as_stream(stream), keyed.data());
+    });
 }
 
 // ----------------------------------------------------------------------------- mul ----

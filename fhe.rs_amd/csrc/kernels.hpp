@@ -12,6 +12,8 @@
 //   ks_fused_kernel         KeySwitchingKey::key_switch             F/bfv/keys/key_switching_key.rs:241-320
 //                           (+ lazy lift M/rq/mod.rs:563-586 + Shoup MAC M/rq/ops.rs:208-245)
 //   ks_fused_split_kernel   the same for N >= 32768: per 8192-point sub-block, first stages in the loader
+//   ks_mac_keyed_kernel     stage B of the unfused key switch with one key per group of polynomials (keyed batches:
+//                           KeySwitchingKey::key_switch client by client)   F/bfv/keys/key_switching_key.rs:241-320
 //   scale_kernel            RnsScaler::scale per column             M/rns/scaler.rs:249-352, M/rq/scaler.rs:85-94
 //   switch_down_kernel      Poly::switch_down                       M/rq/mod.rs:433-492
 //   substitute_kernel       Poly::substitute                        M/rq/mod.rs:360-412
@@ -42,6 +44,7 @@
 #include "kernels_passes.hpp"
 #include "kernels_ntt.hpp"
 #include "kernels_ks.hpp"
+#include "kernels_kskeyed.hpp"
 #include "kernels_scaler.hpp"
 #include "kernels_misc.hpp"
 #include "kernels_encode.hpp"

@@ -65,6 +65,7 @@ enum {
 typedef struct fhe_ctx fhe_ctx;       /* == rq::Context on one device   (M/rq/context.rs:9-19)        */
 typedef struct fhe_scaler fhe_scaler; /* == rq::scaler::Scaler          (M/rq/scaler.rs:18-23)        */
 typedef struct fhe_ksk fhe_ksk;       /* == bfv::KeySwitchingKey        (F/bfv/keys/key_switching_key.rs:22-46) */
+typedef struct fhe_kskset fhe_kskset; /* the KeySwitchingKeys of many clients for one operation (keyed batches) */
 typedef struct fhe_mul fhe_mul;       /* == bfv::Multiplicator          (F/bfv/ops/mul.rs:21-32)      */
 typedef struct fhe_params fhe_params; /* == bfv::BfvParameters' level tables (F/bfv/parameters.rs:83-117) */
 typedef struct fhe_encoder fhe_encoder; /* == BfvParameters' encoding tables (F/bfv/parameters.rs:598, 607-633, 711-725) */
@@ -373,6 +374,54 @@ fhe_status fhe_bfv_expand(const fhe_ksk *const *gks, size_t nlevels, const uint6
                           size_t batch);
 fhe_status fhe_bfv_expand_dev(const fhe_ksk *const *gks, size_t nlevels, const uint64_t *ct, uint64_t *out, size_t size,
                               size_t batch, void *stream);
+
+/* ------------------------------------------------- keyed batches: one key per client ---- */
+/* A server holds one ciphertext, or a few, from each of many clients, and every client has its own relinearization and
+ * Galois keys.  The calls above take one key for the whole batch; the calls below take a SET of keys and a batch in which
+ * items [c * m, (c + 1) * m), m = batch / nkeys, belong to key c -- the same values as one single-key call per client
+ * (KeySwitchingKey::key_switch, F/bfv/keys/key_switching_key.rs:241-320, client by client), in the launches of one batch.
+ * They rest on the unfused key switch: its digit transforms read no key, so one launch serves every client, and the
+ * multiply-accumulate takes each polynomial's key words from a table on the device (ks_mac_keyed_kernel).
+ * Device-pointer forms only.  For every keyed call: `batch` must be a multiple of the set's size (else FHE_E_ARG);
+ * batch == 0 is a no-op (NULL buffers allowed); a NULL buffer with batch > 0 -> FHE_E_ARG; the layouts are those of
+ * the single-key calls.
+ * fhe_kskset_create: `keys` [nkeys] are BORROWED -- they outlive the set -- and must be RNS-digit keys (log_base == 0)
+ * of one parameter set, one (ciphertext level, key level) pair and one digit count.  The set's device table is built
+ * here (one upload, one wait).  An empty list or a NULL key -> FHE_E_ARG; a decomposition key -> FHE_E_ARG ("keyed
+ * batches take RNS-digit keys"); keys that differ in contexts, levels or digits -> FHE_E_PARAMETER_MISMATCH; a
+ * host-only context -> FHE_E_NO_DEVICE.  The keys' own modes (fhe_ksk_set_mode) do not apply to keyed calls.
+ * fhe_kskset_set_w_budget: bytes of transformed digit rows one launch pair may have in flight (0 = default), as
+ * fhe_ksk_set_mode's; launches cut by it need not end on a client boundary.
+ * Not offered: an automatic choice between a keyed call and a loop of single-key calls (with many ciphertexts per client
+ * the fused kernels of the single-key calls fill the device; tools/bench_keyed.py measures both), per-item exponents,
+ * one RGSW ciphertext per item, and a Multiplicator with a key set.  To multiply and relinearize with one key per
+ * client, in the order of Multiplicator::multiply (F/bfv/ops/mul.rs:165-243): fhe_bfv_mul_dev on a fhe_mul created
+ * WITHOUT a relinearization key and without mod_switch (three parts out), then fhe_bfv_relinearize_keyed_dev, then
+ * fhe_bfv_switch_down_dev (nparts = 2) where the modulus switch is wanted. */
+fhe_status fhe_kskset_create(const fhe_ksk *const *keys, size_t nkeys, fhe_kskset **out);
+void fhe_kskset_destroy(fhe_kskset *s);
+size_t fhe_kskset_size(const fhe_kskset *s);
+fhe_status fhe_kskset_set_w_budget(fhe_kskset *s, size_t bytes);
+fhe_status fhe_kskset_get_w_budget(const fhe_kskset *s, size_t *bytes);
+/* KeySwitchingKey::key_switch (:241-320) per client: p [batch][L][N] PowerBasis -> c0_out, c1_out [batch][Lk][N] Ntt. */
+fhe_status fhe_key_switch_keyed_dev(const fhe_kskset *s, const uint64_t *p, uint64_t *c0_out, uint64_t *c1_out,
+                                    size_t batch, void *stream);
+/* RelinearizationKey::relinearizes (F/bfv/keys/relinearization_key.rs:69-102) per client:
+ * ct3 [batch][3][L][N] Ntt -> out [batch][2][L][N] Ntt. */
+fhe_status fhe_bfv_relinearize_keyed_dev(const fhe_kskset *rks, const uint64_t *ct3, uint64_t *out, size_t batch,
+                                         void *stream);
+/* GaloisKey::relinearize (F/bfv/keys/galois_key.rs:63-123) per client, one exponent for the batch: the set holds every
+ * client's key of that exponent.  ct, out [batch][2][L][N] Ntt; `out` may be `ct` (the copying path, as fhe_bfv_galois_dev). */
+fhe_status fhe_bfv_galois_keyed_dev(const fhe_kskset *gks, size_t exponent, const uint64_t *ct, uint64_t *out,
+                                    size_t batch, void *stream);
+/* EvaluationKey::computes_inner_sum (F/bfv/keys/evaluation_key.rs:56-100) per client: one set per rotation, in the
+ * order of fhe_bfv_inner_sum_dev.  Sets of different sizes -> FHE_E_PARAMETER_MISMATCH. */
+fhe_status fhe_bfv_inner_sum_keyed_dev(const fhe_kskset *const *gks, const size_t *exponents, size_t ngk,
+                                       const uint64_t *ct, uint64_t *out, size_t batch, void *stream);
+/* EvaluationKey::expands (F/bfv/keys/evaluation_key.rs:192-256) per client: gks[l] holds every client's key of element
+ * (N >> l) + 1.  ct [batch][2][L][N] -> out [size][batch][2][L][N].  Sets of different sizes -> FHE_E_PARAMETER_MISMATCH. */
+fhe_status fhe_bfv_expand_keyed_dev(const fhe_kskset *const *gks, size_t nlevels, const uint64_t *ct, uint64_t *out,
+                                    size_t size, size_t batch, void *stream);
 
 /* ------------------------------------------------------------- Multiplicator ---- */
 /* Multiplicator::new_leveled_internal + enable_relinearization + enable_mod_switching

@@ -7,6 +7,7 @@
 //! | [`HipCtx`]         | `fhe_ctx`                | `fhe_math::rq::Context`            (rq/context.rs:9-19)    |
 //! | [`HipScaler`]      | `fhe_scaler`             | `fhe_math::rq::scaler::Scaler`     (rq/scaler.rs:18-23)    |
 //! | [`HipKsk`]         | `fhe_ksk`                | `fhe::bfv::KeySwitchingKey`        (keys/key_switching_key.rs:22-46) |
+//! | [`HipKskSet`]      | `fhe_kskset`             | the `KeySwitchingKey`s of many clients for one operation (keyed batches) |
 //! | [`HipMul`]         | `fhe_mul`                | `fhe::bfv::Multiplicator`          (ops/mul.rs:21-32)      |
 //! | [`HipParams`]      | `fhe_params`             | level tables of `BfvParameters`    (parameters.rs:83-117)  |
 //! | [`HipEncoder`]     | `fhe_encoder`            | encoding tables of `BfvParameters` (parameters.rs:598, 711-725) |
@@ -605,6 +606,113 @@ pub enum KsMode {
 }
 impl Drop for HipKsk {
     fn drop(&mut self) { unsafe { ffi::fhe_ksk_destroy(self.ptr) } }
+}
+
+// ------------------------------------------------------------------------------------------ keyed batches
+/// The keys of many clients for ONE operation (`fhe_kskset`): every client's relinearization key, or every client's
+/// Galois key of one exponent.  A keyed call takes a batch whose size is a multiple of `len()`; ciphertexts
+/// `[c * m, (c + 1) * m)` belong to key `c`, and the result is what one single-key call per client gives
+/// (`KeySwitchingKey::key_switch`, keys/key_switching_key.rs:241-320, client by client) in the launches of one batch.
+/// The C object borrows the keys: the lifetime `'k` keeps them alive for as long as the set exists.
+pub struct HipKskSet<'k> {
+    ptr: *mut ffi::FheKskSet,
+    first: &'k HipKsk,
+    len: usize,
+    _keys: PhantomData<&'k [HipKsk]>,
+}
+unsafe impl Send for HipKskSet<'_> {}
+unsafe impl Sync for HipKskSet<'_> {}
+impl<'k> HipKskSet<'k> {
+    /// RNS-digit keys (`log_base == 0`) of one parameter set, one level pair and one digit count; builds the set's device
+    /// table (one upload, one wait).
+    pub fn new(keys: &[&'k HipKsk]) -> Result<Self> {
+        let first = *keys.first().ok_or_else(|| shape_error("HipKskSet::new: no keys"))?;
+        let ptrs: Vec<*const ffi::FheKsk> = keys.iter().map(|k| k.as_ptr()).collect();
+        let mut out: *mut ffi::FheKskSet = ptr::null_mut();
+        check(unsafe { ffi::fhe_kskset_create(ptrs.as_ptr(), ptrs.len(), &mut out) })?;
+        Ok(Self { ptr: out, first, len: keys.len(), _keys: PhantomData })
+    }
+    pub fn as_ptr(&self) -> *const ffi::FheKskSet { self.ptr }
+    pub fn len(&self) -> usize { self.len }
+    pub fn is_empty(&self) -> bool { self.len == 0 }
+    /// Bytes of transformed digit rows one launch pair may have in flight (`fhe_kskset_set_w_budget`; 0 = default).
+    pub fn set_w_budget(&self, bytes: usize) -> Result<()> {
+        check(unsafe { ffi::fhe_kskset_set_w_budget(self.ptr, bytes) })
+    }
+    pub fn w_budget(&self) -> Result<usize> {
+        let mut bytes = 0usize;
+        check(unsafe { ffi::fhe_kskset_get_w_budget(self.ptr, &mut bytes) })?;
+        Ok(bytes)
+    }
+    fn check_keyed(&self, what: &str, ct: &DeviceCiphertexts, parts: usize) -> Result<()> {
+        self.first.check_resident(what, ct, parts)?;
+        if ct.batch % self.len != 0 {
+            return Err(shape_error(&format!("{what}: the batch must be a multiple of the set's {} keys", self.len)));
+        }
+        Ok(())
+    }
+    /// `KeySwitchingKey::key_switch` per client (`fhe_key_switch_keyed_dev`): `p` `[batch][L][N]` PowerBasis ->
+    /// `c0`, `c1` `[batch][Lk][N]` Ntt.
+    pub fn key_switch_dev(&self, p: &DeviceBuffer, c0: &DeviceBuffer, c1: &DeviceBuffer, stream: &Stream) -> Result<()> {
+        let b = whole_batch("key_switch_dev input", p.len(), self.first.ct_ctx().poly_words())?;
+        expect_len("key_switch_dev c0", c0.len(), b * self.first.ksk_ctx().poly_words())?;
+        expect_len("key_switch_dev c1", c1.len(), b * self.first.ksk_ctx().poly_words())?;
+        check(unsafe { ffi::fhe_key_switch_keyed_dev(self.ptr, p.as_ptr(), c0.as_mut_ptr(), c1.as_mut_ptr(), b, stream.as_ptr()) })
+    }
+    /// `RelinearizationKey::relinearizes` per client (`fhe_bfv_relinearize_keyed_dev`).  After a `HipMul` made without a
+    /// relinearization key this is `Multiplicator::multiply` with one key per client (ops/mul.rs:165-243).
+    pub fn relinearize_dev(&self, ct3: &DeviceCiphertexts, stream: &Stream) -> Result<DeviceCiphertexts> {
+        self.check_keyed("relinearize_dev", ct3, 3)?;
+        let out = DeviceCiphertexts::alloc_on(self.first.ct_ctx().device(), ct3.batch, 2, ct3.rows, ct3.degree, ct3.level, stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_relinearize_keyed_dev(self.ptr, ct3.buf.as_ptr(), out.buf.as_mut_ptr(), ct3.batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+    /// `GaloisKey::relinearize` per client with the clients' keys of `exponent` (`fhe_bfv_galois_keyed_dev`).
+    pub fn galois_dev(&self, exponent: usize, ct: &DeviceCiphertexts, stream: &Stream) -> Result<DeviceCiphertexts> {
+        self.check_keyed("galois_dev", ct, 2)?;
+        let out = DeviceCiphertexts::alloc_on(self.first.ct_ctx().device(), ct.batch, 2, ct.rows, ct.degree, ct.level, stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_galois_keyed_dev(self.ptr, exponent, ct.buf.as_ptr(), out.buf.as_mut_ptr(), ct.batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+    /// `EvaluationKey::computes_inner_sum` per client (`fhe_bfv_inner_sum_keyed_dev`): `sets[i]` holds every client's
+    /// Galois key of element `exponents[i]`, in the reference's order (evaluation_key.rs:56-100).
+    pub fn inner_sum_dev(sets: &[&HipKskSet<'k>], exponents: &[usize], ct: &DeviceCiphertexts, stream: &Stream) -> Result<DeviceCiphertexts> {
+        let first = *sets.first().ok_or_else(|| shape_error("inner_sum_dev: no key sets"))?;
+        if sets.len() != exponents.len() {
+            return Err(shape_error("inner_sum_dev: one exponent per key set"));
+        }
+        first.check_keyed("inner_sum_dev", ct, 2)?;
+        let ptrs: Vec<*const ffi::FheKskSet> = sets.iter().map(|s| s.as_ptr()).collect();
+        let out = DeviceCiphertexts::alloc_on(first.first.ct_ctx().device(), ct.batch, 2, ct.rows, ct.degree, ct.level, stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_inner_sum_keyed_dev(ptrs.as_ptr(), exponents.as_ptr(), sets.len(), ct.buf.as_ptr(), out.buf.as_mut_ptr(),
+                                             ct.batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+    /// `EvaluationKey::expands` per client (`fhe_bfv_expand_keyed_dev`): `sets[l]` holds every client's Galois key of
+    /// element `(N >> l) + 1`.  The result has `size * ct.batch` ciphertexts laid out `[size][batch]`.
+    pub fn expand_dev(sets: &[&HipKskSet<'k>], size: usize, ct: &DeviceCiphertexts, stream: &Stream) -> Result<DeviceCiphertexts> {
+        if size == 0 || size > ct.degree {
+            return Err(HipError { status: status::INVALID_EXPANSION_SIZE, message: format!("expand_dev: size {size}, degree {}", ct.degree) });
+        }
+        let first = *sets.first()
+            .ok_or_else(|| HipError { status: status::EXPANSION_UNSUPPORTED, message: "expand_dev: no key sets".into() })?;
+        first.check_keyed("expand_dev", ct, 2)?;
+        let ptrs: Vec<*const ffi::FheKskSet> = sets.iter().map(|s| s.as_ptr()).collect();
+        let out = DeviceCiphertexts::alloc_on(first.first.ct_ctx().device(), size * ct.batch, 2, ct.rows, ct.degree, ct.level, stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_expand_keyed_dev(ptrs.as_ptr(), sets.len(), ct.buf.as_ptr(), out.buf.as_mut_ptr(), size, ct.batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+}
+impl Drop for HipKskSet<'_> {
+    fn drop(&mut self) { unsafe { ffi::fhe_kskset_destroy(self.ptr) } }
 }
 
 // ----------------------------------------------------------------------------------------- Multiplicator
