@@ -184,6 +184,11 @@ SIGNATURES = {
     "fhe_params_create_big_with_tables": (i32, [i32, sz, sz, u64p, u64p, sz, NTT_TABLES_FN, vp, C.POINTER(vp)]),
     "fhe_params_plaintext_limbs": (sz, [vp]),
     "fhe_bfv_encode_big_dev": (i32, [vp, i32, i32, sz, vp, sz, vp, sz, vp]),
+    "fhe_bfv_encode_bytes_dev": (i32, [vp, i32, sz, vp, sz, sz, sz, vp, sz, vp]),
+    "fhe_bfv_encode_words_count": (sz, [vp, sz, sz, sz, sz]),
+    "fhe_bfv_encode_words_dev": (i32, [vp, i32, sz, vp, sz, sz, sz, sz, vp, sz, vp]),
+    "fhe_transcode_count": (sz, [sz, sz, sz]),
+    "fhe_transcode_dev": (i32, [vp, i32, sz, sz, vp, i32, sz, sz, vp]),
     "fhe_bfv_reduce_big_dev": (i32, [vp, vp, sz, vp, sz, vp]),
     "fhe_encoder_plain_rows": (sz, [vp]),
     "fhe_bfv_decrypt_big_dev": (i32, [vp, vp, vp, vp, sz, vp, sz, vp]),

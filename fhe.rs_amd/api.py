@@ -1404,6 +1404,58 @@ class Encoder:
                                    _stream()))
         return out.download()
 
+    def _stream_args(self, nbits, level):
+        nbits = (int(self.plaintext).bit_length() - 1) if nbits is None else int(nbits)
+        nmod = len(self._params.moduli) - level if 0 <= level < len(self._params.moduli) else 1
+        return nbits, nmod
+
+    def encode_bytes(self, data, item_bytes, nbits=None, level=0, scaled=False, batch=None):
+        """encode_database (crates/fhe/examples/util.rs:97-145): item b is bytes [b item_bytes, (b + 1) item_bytes) of
+        `data` (`bytes`, a numpy uint8 array or a device uint8 array; what lies past its end reads as zero), its
+        transcode_from_bytes(item, nbits) values the coefficients of one plaintext -> poly_ntt [batch, L_level, N]
+        (scaled=True: Plaintext::to_poly).  nbits defaults to ilog2(t); batch to ceil(len(data) / item_bytes) -- a larger
+        one appends all-zero plaintexts, the padding rows up to dim1 * dim2."""
+        L = _lib.lib()
+        nbits, nmod = self._stream_args(nbits, level)
+        item_bytes = int(item_bytes)
+        host = not _is_dev(data)
+        if host:
+            a = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) \
+                else np.ascontiguousarray(np.asarray(data, dtype=np.uint8)).reshape(-1)
+            nbytes = int(a.size)
+            x = DeviceArray.from_numpy(a, max(self._params.device, 0)) if nbytes else None
+        else:
+            x, nbytes = data, int(data.numel())
+        if batch is None:
+            batch = -(-nbytes // item_bytes) if item_bytes else 0
+        oshape = (int(batch), nmod, self.degree)
+        out = DeviceArray(oshape, max(self._params.device, 0)) if host else _empty_dev(data, oshape)
+        check(L.fhe_bfv_encode_bytes_dev(self._h, 1 if scaled else 0, level, _dptr8(x) if nbytes else None, nbytes,
+                                         item_bytes, nbits, _dptr(out), batch, _stream()))
+        return out.download() if host else out
+
+    def encode_words(self, words, in_bits, nbits=None, level=0, scaled=False):
+        """The SealPIR fold (crates/fhe/examples/sealpir.rs:176-200): words [..., nseg, seg_len] carrying in_bits each;
+        every segment through transcode_bidirectional(segment, in_bits, nbits), an item's value lists appended and cut
+        into plaintexts of N values -> poly_ntt [..., nplain, L_level, N].  nbits defaults to ilog2(t)."""
+        L = _lib.lib()
+        nbits, nmod = self._stream_args(nbits, level)
+        if len(words.shape) < 2:
+            raise FheError(-1, "words: expected [..., nseg, seg_len]")
+        lead, nseg, seg_len = tuple(int(d) for d in words.shape[:-2]), int(words.shape[-2]), int(words.shape[-1])
+        batch = int(np.prod(lead)) if lead else 1
+        nplain = int(L.fhe_bfv_encode_words_count(self._h, int(in_bits), nseg, seg_len, nbits))
+        oshape = lead + (nplain, nmod, self.degree)
+        host = not _is_dev(words)
+        x = DeviceArray.from_numpy(_np(words), max(self._params.device, 0)) if host else words
+        out = DeviceArray(oshape, x.device) if host else _empty_dev(words, oshape)
+        try:
+            check(L.fhe_bfv_encode_words_dev(self._h, 1 if scaled else 0, level, _dptr(x), int(in_bits), nseg, seg_len,
+                                             nbits, _dptr(out), batch, _stream()))
+            return out.download() if host else out
+        finally:
+            _wipe([x] if host else [])
+
     def reduce(self, polys):
         """The tail of SecretKey::try_decrypt's Large branch alone (secret_key.rs:238-250, fhe_bfv_reduce_big_dev):
         PowerBasis residues over the plaintext context [..., P, N] -> ((x + t) mod Q_p) mod t of each lifted column,
@@ -1445,6 +1497,47 @@ class Encoder:
         out = DeviceArray(x.shape, x.device)
         check(L.fhe_bfv_decode_dev(self._h, enc, _dptr(x), _dptr(out), batch, _stream()))
         return out.download()
+
+
+def number_elements_per_plaintext(degree, nbits, element_size):
+    """crates/fhe/examples/util.rs:86-92: database elements of element_size bytes per plaintext of `degree` values of
+    `nbits` bits."""
+    return (nbits * degree) // (element_size * 8)
+
+
+def transcode(a, in_bits, out_bits, out_bytes=False, device=0):
+    """fhe_util::transcode_bidirectional / transcode_to_bytes / transcode_from_bytes (fhe-util/src/lib.rs:71-190) on the
+    device: rows [..., nin] of elements carrying in_bits each -> [..., ceil(nin in_bits / out_bits)] elements of out_bits
+    bits.  `a` is uint64 or -- `bytes`, a numpy uint8 array, a device uint8 array -- bytes; the result is uint8 when
+    out_bytes, else uint64.  numpy / bytes in -> numpy out (staged on `device`); a device array in -> a device array out,
+    on the current stream."""
+    L = _lib.lib()
+    host = not _is_dev(a)
+    if host:
+        if isinstance(a, (bytes, bytearray, memoryview)):
+            a = np.frombuffer(bytes(a), dtype=np.uint8)
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a if a.dtype == np.uint8 else np.asarray(a, dtype=np.uint64))
+        in_bytes = a.dtype == np.uint8
+    else:
+        in_bytes = a.element_size() == 1
+    if len(a.shape) < 1:
+        raise FheError(-1, "transcode: expected [..., nin]")
+    lead, nin = tuple(int(d) for d in a.shape[:-1]), int(a.shape[-1])
+    batch = int(np.prod(lead)) if lead else 1
+    in_bits, out_bits = int(in_bits), int(out_bits)
+    if not (1 <= in_bits <= (8 if in_bytes else 64) and 1 <= out_bits <= (8 if out_bytes else 64)):
+        raise FheError(-1, "transcode: widths must be in [1, 64] ([1, 8] on a byte side)")
+    nout = int(L.fhe_transcode_count(in_bits, nin, out_bits))
+    oshape, osize = lead + (nout,), 1 if out_bytes else 8
+    x = DeviceArray.from_numpy(a, device) if host else a
+    out = DeviceArray(oshape, x.device, osize) if host else _empty_dev(a, oshape, osize)
+    try:
+        check(L.fhe_transcode_dev((_dptr8 if in_bytes else _dptr)(x), 1 if in_bytes else 0, in_bits, nin,
+                                  (_dptr8 if out_bytes else _dptr)(out), 1 if out_bytes else 0, out_bits, batch, _stream()))
+        return out.download() if host else out
+    finally:
+        _wipe([x, out] if host else [])
 
 
 def _alloc(shape, device, itemsize=8):

@@ -2924,6 +2924,91 @@ inline void decode(const Encoder &e, bool simd, const u64 *coeffs, u64 *out, siz
                (const u64 *)tmp.u(), (u64)e.n, (u64)e.n, (const uint32_t *)e.d_map.p, out, e.tm, (uint32_t)e.logn, total);
 }
 
+// ------------------------------------------------------- plaintexts from packed bits ----
+// fhe_util::transcode_* (fhe-util/src/lib.rs:71-190): ceil(nin in_bits / out_bits) output elements, the last one partial.
+constexpr size_t TRANSCODE_MAX_ELEMS = (size_t)1 << 56;   // (keeps nin * in_bits below 2^63)
+inline bool transcode_bits_ok(size_t bits, bool bytes) { return bits >= 1 && bits <= (bytes ? 8u : 64u); }
+inline u64 transcode_count(size_t in_bits, size_t nin, size_t out_bits) {
+    return ((u64)nin * in_bits + out_bits - 1) / out_bits;
+}
+
+// One launch of transcode_ew_kernel: `rows` rows of nin elements, row i at i * in_stride of `in` (bounded by total_in),
+// written at (i / grp) * out_stride + (i % grp) * nout of `out`.
+inline void launch_transcode(const void *in, bool in_bytes, size_t in_bits, u64 total_in, u64 in_stride, u64 nin, void *out,
+                             bool out_bytes, size_t out_bits, u64 grp, u64 out_stride, size_t rows, hipStream_t s) {
+    const u64 nout = transcode_count(in_bits, nin, out_bits);
+    if (!rows || !nout) return;
+    const u64 bpr = (nout + EW_THREADS - 1) / EW_THREADS;
+    require(rows <= 0x7fffffffu && bpr * rows <= 0x7fffffffu, E_ARG, "transcode: batch exceeds the grid limit");
+    k::TranscodeIo io{in, out, total_in, in_stride, nin, nout, grp, out_stride, in_bytes ? 1u : 0u, (uint32_t)in_bits,
+                      out_bytes ? 1u : 0u, (uint32_t)out_bits, (uint32_t)bpr};
+    FHE_LAUNCH("transcode", k::transcode_ew_kernel, dim3((unsigned)(bpr * rows)), dim3(EW_THREADS), 0, s, io);
+}
+
+// fhe_util::transcode_from_bytes / transcode_to_bytes / transcode_bidirectional: rows [batch][nin] -> [batch][nout].
+inline void transcode(const void *in, bool in_bytes, size_t in_bits, size_t nin, void *out, bool out_bytes, size_t out_bits,
+                      size_t batch, hipStream_t s) {
+    require(transcode_bits_ok(in_bits, in_bytes), E_ARG, "transcode: in_bits must be in [1, 64] ([1, 8] for bytes)");
+    require(transcode_bits_ok(out_bits, out_bytes), E_ARG, "transcode: out_bits must be in [1, 64] ([1, 8] for bytes)");
+    require(nin <= TRANSCODE_MAX_ELEMS && (!nin || batch <= ((size_t)1 << 62) / nin), E_ARG, "transcode: too many elements");
+    const u64 nout = transcode_count(in_bits, nin, out_bits);
+    launch_transcode(in, in_bytes, in_bits, (u64)batch * nin, nin, nin, out, out_bytes, out_bits, 1, nout, batch, s);
+}
+
+// Plaintexts per item of encode_stream: ceil(nseg * M / N), M = ceil(seg_len * in_bits / nbits).
+// (0 for widths or lengths encode_stream refuses)
+inline u64 stream_plaintexts(const Encoder &e, size_t in_bits, size_t nseg, size_t seg_len, size_t nbits) {
+    if (!transcode_bits_ok(in_bits, false) || !transcode_bits_ok(nbits, false) || seg_len > TRANSCODE_MAX_ELEMS) return 0;
+    u64 nv;
+    if (__builtin_mul_overflow((u64)nseg, transcode_count(in_bits, seg_len, nbits), &nv) || nv >> 62) return 0;
+    return (nv + e.n - 1) / e.n;
+}
+
+// Plaintext::try_encode(Encoding::poly_at_level) (or, scaled, Plaintext::to_poly) of the transcoded values of a packed
+// source (k::StreamSrc): per item nseg segments of seg_len elements, `total` elements in all (what lies beyond reads as
+// zero) -> out [batch][nplain][L_level][N] Ntt.
+inline void encode_stream(const Encoder &e, bool scaled, size_t level, const void *src, bool bytes, u64 total, size_t in_bits,
+                          size_t nseg, size_t seg_len, size_t nbits, u64 *out, size_t batch, hipStream_t s) {
+    require(!e.big(), E_PARAMETER_MISMATCH, "the plaintext modulus exceeds 64 bits: use fhe_bfv_encode_big_dev");
+    const Ctx *qc = e.top->at_level(level);
+    if (!qc) throw StatusError(E_INVALID_LEVEL, "InvalidLevel");
+    require(nbits >= 1 && nbits <= 64, E_ARG, "encode: nbits must be in [1, 64]");
+    require(transcode_bits_ok(in_bits, bytes), E_ARG, "encode: in_bits must be in [1, 64]");
+    require(seg_len <= TRANSCODE_MAX_ELEMS, E_ARG, "encode: too many elements");
+    const u64 M = transcode_count(in_bits, seg_len, nbits);
+    u64 nv;
+    require(!__builtin_mul_overflow((u64)nseg, M, &nv) && !(nv >> 62), E_ARG, "encode: too many elements");
+    if (bytes && (u64)seg_len * 8 > (u64)e.n * nbits)
+        throw StatusError(E_TOO_MANY_VALUES, "TooManyValues: more bits than a plaintext of the degree holds");
+    const u64 nplain = bytes ? 1 : stream_plaintexts(e, in_bits, nseg, seg_len, nbits);
+    if (!batch || !nplain) return;
+    const u64 items = (u64)batch * nplain;
+    require(items * qc->L <= 0x7fffffffu, E_ARG, "encode: batch exceeds the grid limit");
+    const u64 qmt = e.q_mod_t[level];
+    const k::u64x2 qm{qmt, shoup(qmt, e.t)};
+    const k::u64x2 *delta = scaled ? e.d_delta[level]->p : nullptr;
+    if (qc->logn <= 14) {
+        k::StreamSrc ss{src, total, M ? (u64)nseg : 0, (u64)seg_len, (u64)seg_len, M ? M : 1, bytes ? 1u : 0u,
+                        (uint32_t)in_bits, (uint32_t)nbits, (uint32_t)nplain, e.tm, qm, scaled ? 1u : 0u, delta};
+        const RowLaunch rows(*qc, qc->L, !f64_disabled());
+        rows("encode_stream", items * qc->L, s,
+             [](auto lm, auto nrw, auto h) { return kernel_c<k::encode_stream_kernel<lm(), nrw(), h()>>{}; },
+             ss, out, (uint32_t)qc->L, qc->dmods(), rows.tw());
+        return;
+    }
+    // rows larger than one LDS tile: the values as a pass of their own into scratch that is cleared before it is reused
+    // (plaintext coefficients: the reference zeroizes them, plaintext.rs:104, 178), then the element-wise lift and launch_ntt
+    const u64 per_item = nplain * e.n;
+    WsGuard vals(items * e.n * sizeof(u64), s, true);
+    if ((u64)nseg * M < per_item) FHE_HIP_CHECK(hipMemsetAsync(vals.p, 0, vals.bytes, s));
+    launch_transcode(src, bytes, in_bits, total, seg_len, seg_len, vals.p, false, nbits, nseg, per_item, batch * nseg, s);
+    k::LiftSrc ls{vals.u(), e.n, e.n, e.tm, qm, scaled ? 1u : 0u, delta};
+    const u64 all = items * qc->L * e.n;
+    FHE_LAUNCH("encode_lift", k::encode_lift_ew_kernel, dim3(blocks_for(all, EW_THREADS)), dim3(EW_THREADS), 0, s, ls, out,
+               (uint32_t)qc->L, qc->dmods(), (uint32_t)e.logn, all);
+    launch_ntt(*qc, false, out, out, full_map(*qc, qc->L), items, s);
+}
+
 // ------------------------------------------------------------------------ encryption ----
 // Poly::small (M/rq/mod.rs:298-330) and sample_vec_cbd (fhe-util/src/lib.rs:22-66).
 inline void check_variance(size_t variance) {

@@ -1789,6 +1789,49 @@ fhe_status fhe_bfv_decode_dev(const fhe_encoder *enc, int encoding, const uint64
         decode(*enc->e, encoding == FHE_ENCODING_SIMD, coeffs, out, batch, as_stream(stream));
     });
 }
+fhe_status fhe_bfv_encode_bytes_dev(const fhe_encoder *enc, int scaled, size_t level, const uint8_t *bytes, size_t nbytes,
+                                    size_t item_bytes, size_t nbits, uint64_t *out, size_t batch, void *stream) {
+    return guard([&] {
+        need(enc, "encoder");
+        if (batch) {
+            if (nbytes) need(bytes, "bytes");
+            need(out, "out");
+        }
+        set_device(*enc->e->top);
+        encode_stream(*enc->e, scaled != 0, level, bytes, true, nbytes, 8, 1, item_bytes, nbits, out, batch, as_stream(stream));
+    });
+}
+size_t fhe_bfv_encode_words_count(const fhe_encoder *enc, size_t in_bits, size_t nseg, size_t seg_len, size_t nbits) {
+    return enc ? (size_t)stream_plaintexts(*enc->e, in_bits, nseg, seg_len, nbits) : 0;
+}
+fhe_status fhe_bfv_encode_words_dev(const fhe_encoder *enc, int scaled, size_t level, const uint64_t *words, size_t in_bits,
+                                    size_t nseg, size_t seg_len, size_t nbits, uint64_t *out, size_t batch, void *stream) {
+    return guard([&] {
+        need(enc, "encoder");
+        if (batch && nseg && seg_len) {
+            need(words, "words");
+            need(out, "out");
+        }
+        set_device(*enc->e->top);
+        require(nseg == 0 || seg_len == 0 || batch <= ((size_t)1 << 62) / nseg / seg_len, E_ARG, "encode: too many elements");
+        encode_stream(*enc->e, scaled != 0, level, words, false, (u64)batch * nseg * seg_len, in_bits, nseg, seg_len, nbits,
+                      out, batch, as_stream(stream));
+    });
+}
+size_t fhe_transcode_count(size_t in_bits, size_t nin, size_t out_bits) {
+    if (in_bits < 1 || in_bits > 64 || out_bits < 1 || out_bits > 64 || nin > TRANSCODE_MAX_ELEMS) return 0;
+    return (size_t)transcode_count(in_bits, nin, out_bits);
+}
+fhe_status fhe_transcode_dev(const void *in, int in_is_bytes, size_t in_bits, size_t nin, void *out, int out_is_bytes,
+                             size_t out_bits, size_t batch, void *stream) {
+    return guard([&] {
+        if (batch && nin) {
+            need(in, "in");
+            need(out, "out");
+        }
+        transcode(in, in_is_bytes != 0, in_bits, nin, out, out_is_bytes != 0, out_bits, batch, as_stream(stream));
+    });
+}
 fhe_status fhe_bfv_add_plain_dev(const fhe_ctx *ctx, int subtract, size_t nparts, const uint64_t *ct, const uint64_t *pt,
                                  int pt_shared, uint64_t *out, size_t batch, void *stream) {
     return guard([&] {

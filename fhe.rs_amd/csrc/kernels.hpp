@@ -38,6 +38,8 @@
 //   mbfv_share_kernel, mbfv_sum_kernel  the shares of the multiparty protocols and their aggregation   F/mbfv/*.rs
 //   bigt_project_kernel, bigt_tail_kernel   plaintext moduli above 64 bits: Vec<BigUint> encoding and the Large branch of
 //                           SecretKey::try_decrypt   F/bfv/plaintext_vec.rs:105-132, plaintext.rs:172-197, secret_key.rs:238-250
+//   encode_stream_kernel, transcode_ew_kernel   plaintexts from packed bits: fhe_util::transcode_* + Plaintext::try_encode
+//                           (encode_database, the SealPIR fold)   fhe-util lib.rs:71-190, examples/util.rs:97-145, sealpir.rs:176-200
 // Compile-time knobs live in knobs.hpp (pinned in the release build); rejected kernel variants in tools/lab/ (lab builds only).
 #pragma once
 #include "kernels_common.hpp"
@@ -54,6 +56,7 @@
 #include "kernels_noise.hpp"
 #include "kernels_mbfv.hpp"
 #include "kernels_bigt.hpp"
+#include "kernels_transcode.hpp"
 
 namespace fhe {
 namespace k {

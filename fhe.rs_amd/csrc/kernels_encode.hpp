@@ -65,16 +65,21 @@ struct LiftSrc {
     uint32_t mul_t;
     const u64x2 *delta;    // [rows] {delta_i, shoup} mod q_i, or null
 };
-__device__ __forceinline__ u64 lift_load(const LiftSrc &ls, uint32_t b, uint32_t j, uint32_t r, const DevMod &md) {
-    if (j >= ls.nvalues) return 0;
-    u64 v = reduce_u64(ls.src[(u64)b * ls.stride + j], ls.tm);
-    if (ls.mul_t) v = mul_shoup(v, ls.qmt.x, ls.qmt.y, ls.tm.p);
+// (the steps on one source word `w`, shared with the bit-stream loader of kernels_transcode.hpp)
+__device__ __forceinline__ u64 lift_steps(u64 w, const DevMod &tm, const u64x2 &qmt, uint32_t mul_t,
+                                          const u64x2 *__restrict__ delta, uint32_t r, const DevMod &md) {
+    u64 v = reduce_u64(w, tm);
+    if (mul_t) v = mul_shoup(v, qmt.x, qmt.y, tm.p);
     v = reduce_u64(v, md);
-    if (ls.delta) {
-        const u64x2 d = ls.delta[r];
+    if (delta) {
+        const u64x2 d = delta[r];
         v = mul_shoup(v, d.x, d.y, md.p);
     }
     return v;
+}
+__device__ __forceinline__ u64 lift_load(const LiftSrc &ls, uint32_t b, uint32_t j, uint32_t r, const DevMod &md) {
+    if (j >= ls.nvalues) return 0;
+    return lift_steps(ls.src[(u64)b * ls.stride + j], ls.tm, ls.qmt, ls.mul_t, ls.delta, r, md);
 }
 
 // One workgroup per (item, row): the lifted row in Ntt form, out[b][r][N] (N = 2^LOGM <= 16384).  NARROW: every modulus

@@ -533,6 +533,44 @@ fhe_status fhe_bfv_encode_dev(const fhe_encoder *enc, int encoding, int scaled, 
  * writes) -> values [batch][N].  Poly: the coefficients; SIMD: NttOperator::forward mod t, then out[i] = v[map[i]]. */
 fhe_status fhe_bfv_decode_dev(const fhe_encoder *enc, int encoding, const uint64_t *coeffs, uint64_t *out, size_t batch,
                               void *stream);
+/* Plaintexts from packed bits: fhe_util::transcode_from_bytes / transcode_to_bytes / transcode_bidirectional
+ * (crates/fhe-util/src/lib.rs:71-190) followed by Plaintext::try_encode(Encoding::poly_at_level), without an unpacked
+ * copy of the values in device memory.  The three transcoders are one operation on a bit stream: the low in_bits of each
+ * input element laid end to end, least significant bit first (a byte string is in_bits = 8); output element k is stream
+ * bits [k out_bits, (k + 1) out_bits), bits past the end read as zero; ceil(nin in_bits / out_bits) output elements, the
+ * last one possibly partial.  As everywhere in this section the values are reduced mod t on load: with
+ * nbits = ilog2(t), what the examples use, every value is below t and the result is the reference's bit for bit.
+ *
+ * fhe_bfv_encode_bytes_dev: encode_database (crates/fhe/examples/util.rs:97-145; both PIR servers): item b is bytes
+ * [b item_bytes, min((b + 1) item_bytes, nbytes)) of `bytes`, and everything from nbytes on reads as zero -- a short last
+ * item and the all-zero padding rows up to dim1 * dim2 come out of the same call.  Each item gives the
+ * ceil(item_bytes 8 / nbits) values of transcode_from_bytes(item, nbits), the coefficients of one plaintext -> out
+ * [batch][L_level][N] Ntt, its poly_ntt (scaled = 0) or Delta-scaled to_poly (scaled = 1), as fhe_bfv_encode_dev.
+ * item_bytes * 8 > N * nbits -> FHE_E_TOO_MANY_VALUES; nbits outside 1 ... 64 -> FHE_E_ARG; an encoder of a plaintext
+ * modulus above 64 bits -> FHE_E_PARAMETER_MISMATCH; level > max -> FHE_E_INVALID_LEVEL.  `bytes` may have any alignment. */
+fhe_status fhe_bfv_encode_bytes_dev(const fhe_encoder *enc, int scaled, size_t level, const uint8_t *bytes, size_t nbytes,
+                                    size_t item_bytes, size_t nbits, uint64_t *out, size_t batch, void *stream);
+/* The SealPIR fold (crates/fhe/examples/sealpir.rs:176-200): words [batch][nseg][seg_len], each word carrying in_bits
+ * (higher bits are masked off).  Every segment goes through transcode_bidirectional(segment, in_bits, nbits) on its own
+ * -- M = ceil(seg_len in_bits / nbits) values --, the segments' value lists of an item are appended, and
+ * PlaintextVec::try_encode(Encoding::poly_at_level) cuts them into nplain = ceil(nseg M / N) plaintexts of N values,
+ * the last one zero-padded -> out [batch][nplain][L_level][N] Ntt.  For the fold a segment is c0 or c1 of a ciphertext
+ * at its last level (nseg = 2, seg_len = N, in_bits = bits(q_0)).  fhe_bfv_encode_words_count returns nplain (0 for
+ * widths outside 1 ... 64 or a NULL encoder).  Refusals as fhe_bfv_encode_bytes_dev; in_bits outside 1 ... 64 ->
+ * FHE_E_ARG. */
+size_t fhe_bfv_encode_words_count(const fhe_encoder *enc, size_t in_bits, size_t nseg, size_t seg_len, size_t nbits);
+fhe_status fhe_bfv_encode_words_dev(const fhe_encoder *enc, int scaled, size_t level, const uint64_t *words, size_t in_bits,
+                                    size_t nseg, size_t seg_len, size_t nbits, uint64_t *out, size_t batch, void *stream);
+/* The transcoders on their own -- the client's way back (crates/fhe/examples/sealpir.rs:231-252, 273; mulpir.rs:195):
+ * transcode_bidirectional (u64 -> u64), transcode_to_bytes (u64 -> bytes, out_bits = 8) and transcode_from_bytes
+ * (bytes -> u64, in_bits = 8).  Rows [batch][nin] -> [batch][nout], nout = fhe_transcode_count(in_bits, nin, out_bits)
+ * = ceil(nin in_bits / out_bits) (0 for widths outside 1 ... 64).  A side given as bytes (in_is_bytes / out_is_bytes
+ * != 0) is an array of uint8_t whose elements carry at most 8 bits; otherwise of uint64_t.  Input bits above in_bits are
+ * masked off.  Widths outside 1 ... 64 (1 ... 8 for a byte side) -> FHE_E_ARG.  The call takes no handle: it runs on the
+ * calling thread's current device, which `stream` belongs to (as fhe_buf_zero_async). */
+size_t fhe_transcode_count(size_t in_bits, size_t nin, size_t out_bits);
+fhe_status fhe_transcode_dev(const void *in, int in_is_bytes, size_t in_bits, size_t nin, void *out, int out_is_bytes,
+                             size_t out_bits, size_t batch, void *stream);
 /* `&Ciphertext + &Plaintext` / `-` (F/bfv/ops/mod.rs:71-108, 166-203): out = ct with c0 +- pt, pt the Delta-scaled
  * form (fhe_bfv_encode_dev with scaled = 1) at the ciphertext's level.  ct, out [batch][nparts][L][N] Ntt; pt
  * [batch][L][N] (or [L][N] shared by the batch when pt_shared != 0); out == ct allowed. */

@@ -931,6 +931,58 @@ impl HipEncoder {
     }
 }
 impl HipEncoder {
+    /// `encode_database` (crates/fhe/examples/util.rs:97-145): item b is bytes `[b item_bytes, (b + 1) item_bytes)` of
+    /// the first `nbytes` bytes of `bytes` (`DeviceBuffer::upload_bytes`; what lies from `nbytes` on reads as zero), its
+    /// `transcode_from_bytes(item, nbits)` values the coefficients of one plaintext -> `[batch][L_level][N]` Ntt,
+    /// `poly_ntt` or with `scaled` `to_poly()`.  `batch` items: beyond `ceil(nbytes / item_bytes)` they are the all-zero
+    /// padding plaintexts (`fhe_bfv_encode_bytes_dev`).
+    pub fn encode_bytes_dev(&self, scaled: bool, level: usize, bytes: &DeviceBuffer, nbytes: usize, item_bytes: usize,
+                            nbits: usize, batch: usize, stream: &Stream) -> Result<DeviceBuffer> {
+        if nbytes > bytes.len() * 8 {
+            return Err(shape_error("encode_bytes_dev: nbytes exceeds the buffer"));
+        }
+        let ctx = self.params.context_at_level(level)?;
+        let out = DeviceBuffer::alloc_on(ctx.device(), (batch * ctx.poly_words()).max(1), stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_encode_bytes_dev(self.ptr, scaled as c_int, level, bytes.as_ptr() as *const u8, nbytes, item_bytes,
+                                          nbits, out.as_mut_ptr(), batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+    /// The SealPIR fold (crates/fhe/examples/sealpir.rs:176-200): `words` `[batch][nseg][seg_len]` carrying `in_bits`
+    /// each; every segment through `transcode_bidirectional(segment, in_bits, nbits)`, an item's value lists appended
+    /// and cut into plaintexts of N values -> (`[batch][nplain][L_level][N]` Ntt, nplain) (`fhe_bfv_encode_words_dev`).
+    pub fn encode_words_dev(&self, scaled: bool, level: usize, words: &DeviceBuffer, in_bits: usize, nseg: usize,
+                            seg_len: usize, nbits: usize, stream: &Stream) -> Result<(DeviceBuffer, usize)> {
+        let batch = whole_batch("encode_words_dev words", words.len(), nseg * seg_len)?;
+        let nplain = unsafe { ffi::fhe_bfv_encode_words_count(self.ptr, in_bits, nseg, seg_len, nbits) };
+        let ctx = self.params.context_at_level(level)?;
+        let out = DeviceBuffer::alloc_on(ctx.device(), (batch * nplain * ctx.poly_words()).max(1), stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_encode_words_dev(self.ptr, scaled as c_int, level, words.as_ptr(), in_bits, nseg, seg_len, nbits,
+                                          out.as_mut_ptr(), batch, stream.as_ptr())
+        })?;
+        Ok((out, nplain))
+    }
+}
+
+/// `fhe_util::transcode_bidirectional` (fhe-util/src/lib.rs:150-187) on device words: rows `[batch][nin]` carrying
+/// `in_bits` each -> `[batch][ceil(nin in_bits / out_bits)]` words of `out_bits` bits (`fhe_transcode_dev`; the byte
+/// forms `transcode_to_bytes` / `transcode_from_bytes` are the same call with a byte side, through `ffi`).  Runs on the
+/// calling thread's current device, which `stream` and `input` belong to.
+pub fn transcode_dev(device: i32, input: &DeviceBuffer, in_bits: usize, nin: usize, out_bits: usize, stream: &Stream)
+                     -> Result<DeviceBuffer> {
+    let batch = whole_batch("transcode_dev input", input.len(), nin)?;
+    let nout = unsafe { ffi::fhe_transcode_count(in_bits, nin, out_bits) };
+    let out = DeviceBuffer::alloc_on(device, (batch * nout).max(1), stream)?;
+    check(unsafe {
+        ffi::fhe_transcode_dev(input.as_ptr() as *const c_void, 0, in_bits, nin, out.as_mut_ptr() as *mut c_void, 0, out_bits,
+                               batch, stream.as_ptr())
+    })?;
+    Ok(out)
+}
+
+impl HipEncoder {
     /// `SecretKey::measure_noise` (keys/secret_key.rs:55-98) on a device-resident batch: the bits of noise of each
     /// ciphertext, `[batch]`.  `scaler`: the cipher-to-plaintext scaler of the ciphertexts' level (as
     /// `HipScaler::decrypt_dev`), whose source context must be a level of this encoder's parameter set; `s_ntt`
