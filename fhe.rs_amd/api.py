@@ -1131,6 +1131,44 @@ class EvaluationKey:
             raise FheError(-11, "EvaluationKeyError::Unsupported(ColumnRotation)")
         return self.gk[e].relinearize(ct)
 
+    def hoisted(self, column_rotations=(), row_rotation=False):
+        """The rotations `column_rotations` (steps, in this order) and then the row rotation as ONE hoisted call per
+        ciphertext batch: a `HoistedRotations` holding the key set and the exponent list, both built once.  A missing
+        key raises what rotates_columns_by / rotates_rows raise."""
+        exps = []
+        for i in column_rotations:
+            if not (1 <= i < self.degree // 2):
+                raise FheError(-1, "InvalidRotationStep")
+            e = pow(3, i, 2 * self.degree)
+            if e not in self.gk:
+                raise FheError(-11, "EvaluationKeyError::Unsupported(ColumnRotation)")
+            exps.append(e)
+        if row_rotation:
+            e = 2 * self.degree - 1
+            if e not in self.gk:
+                raise FheError(-11, "EvaluationKeyError::Unsupported(RowRotation)")
+            exps.append(e)
+        if not exps:
+            raise FheError(-1, "hoisted rotations: no rotation was asked for")
+        return HoistedRotations([self.gk[e] for e in exps])
+
+
+class HoistedRotations:
+    """`EvaluationKey.hoisted(...)`: several rotations of each ciphertext on one digit decomposition (KeySet.
+    relinearize_hoisted).  rotate(ct): [batch, 2, L, N] -> [batch, R, 2, L, N], rotation r under galois_keys[r] -- the
+    layout Context.dot_product_scalar reads as R ciphertexts per item.  Not the reference's words (include/fhe_hip.h)."""
+
+    def __init__(self, galois_keys):
+        self.keys = list(galois_keys)
+        self.exponents = [g.exponent for g in self.keys]
+        self.set = KeySet([g.ksk for g in self.keys])
+
+    def __len__(self):
+        return len(self.exponents)
+
+    def rotate(self, ct):
+        return self.set.relinearize_hoisted(self.exponents, ct)
+
 
 class KeySet:
     """Keyed batches (fhe_kskset): the keys of many clients for ONE operation -- every client's relinearization key, or
@@ -1215,6 +1253,22 @@ class KeySet:
             return out
         return self._run(ct, [tuple(ct.shape)], lambda d, o: L.fhe_bfv_galois_keyed_dev(
             self._h, e, _dptr(d), _dptr(o[0]), b, _stream()))[0]
+
+    def relinearize_hoisted(self, exponents, ct):
+        """Hoisted rotations (fhe_bfv_galois_hoisted_dev): the set holds ONE client's Galois keys, key r for exponents[r];
+        [batch, 2, L, N] Ntt (or [2, L, N]) -> [batch, R, 2, L, N] (or [R, 2, L, N]), every rotation of a ciphertext on one
+        digit decomposition.  Not the reference's words: a restatement (include/fhe_hip.h) that decrypts to what
+        GaloisKey.relinearize's result does and equals it word for word only at exponent 1."""
+        L = _lib.lib()
+        ctx = self.ctx_ciphertext
+        if ct.shape[-3] != 2:
+            raise FheError(-13, "InvalidPolynomialCount: rotation expects 2 parts")
+        exps = [int(e) for e in exponents]
+        arr = (C.c_size_t * max(len(exps), 1))(*exps)
+        b = ctx._batch(ct) // 2
+        oshape = tuple(ct.shape[:-3]) + (len(exps),) + tuple(ct.shape[-3:])
+        return self._run(ct, [oshape], lambda d, o: L.fhe_bfv_galois_hoisted_dev(
+            self._h, arr, len(exps), _dptr(d), _dptr(o[0]), b, _stream()))[0]
 
 
 class EvaluationKeySet:

@@ -2182,6 +2182,89 @@ inline void galois_apply(const Ksk &ks, size_t exponent, const u64 *ct, u64 *out
                    nullptr, keyed);
 }
 
+// Hoisted rotations (kernels_kshoist.hpp; not in the reference, whose words this does NOT reproduce except at exponent
+// 1 -- the restatement is tests/hoist_ref.py): the Galois elements exponents[r], r < nrot, of each ciphertext under key r
+// of `set`, from ONE digit decomposition.  ct [batch][2][L][N] Ntt -> out [batch][nrot][2][L][N] Ntt.
+// One inverse transform of c1 (no substitution), then key_switch_polys_keyed's geometry unchanged -- tile choice, `narrow`,
+// `rns`, the W budget rule with equal chunks of ciphertexts and equal groups of key moduli -- with one stage A per (chunk,
+// group) and, on its W, one hoist_mac_kernel launch per k::HOIST_ROTS rotations.  Nothing is uploaded: the exponents
+// travel as kernel arguments.  R rotations cost one stage A and R multiply-accumulates; a loop of galois_apply pays the
+// transforms R times.
+inline void galois_hoisted(const KskSet &set, const size_t *exponents, size_t nrot, const u64 *ct, u64 *out, size_t batch,
+                           hipStream_t s) {
+    const Ksk &k_ = *set.keys[0];
+    const Ctx &kc = *set.ksk_ctx, &cc = *set.ct_ctx;
+    require(exponents != nullptr, E_ARG, "null argument: exponents");
+    require(nrot == set.keys.size(), E_ARG, "hoisted rotations: one exponent per key of the set");
+    const size_t N = kc.n, nd = set.ndigits, Lk = kc.L;
+    std::vector<uint32_t> exps(nrot);
+    for (size_t r = 0; r < nrot; r++) {
+        exps[r] = (uint32_t)(exponents[r] % (2 * N));
+        require((exps[r] & 1) == 1, E_INVALID_SUBST, "InvalidSubstitutionExponent");
+    }
+    if (kc.niterations_to(cc) != 0)
+        throw StatusError(E_ARG, "hoisted rotations: the keys must sit at the ciphertext's level (" + std::to_string(cc.L) +
+                                     " moduli), not above it (" + std::to_string(Lk) + ")");
+    if (!batch) return;
+    const u64 PL = (u64)cc.L * N;
+    require(!(out < ct + batch * 2 * PL && ct < out + batch * nrot * 2 * PL), E_ARG,
+            "hoisted rotations: `out` overlaps `ct` (every rotation gathers from the whole input)");
+    kc.need_device();
+    const uint32_t logn = (uint32_t)kc.logn;
+    WsGuard c2(batch * PL * sizeof(u64), s);
+    k::RowMap m = full_map(cc, cc.L);
+    m.src_poly_stride = 2 * PL;
+    m.dst_poly_stride = PL;
+    launch_ntt(cc, true, ct + PL, c2.u(), m, batch, s);
+    const bool sub14 = logn == 14 && 2 * batch * nd * Lk <= (size_t)device_cus(kc.device);
+    const uint32_t logm = logn > 14 ? 13 : sub14 ? 13 : logn;
+    const uint32_t g0 = logn - logm;
+    const bool narrow = !FHE_LAB_FLAG("NO_NARROW") && kc.below_2p60(0, kc.L);
+    const bool rns = k_.digit_arg() == (1u << 8);
+    size_t budget = set.w_budget.load(std::memory_order_relaxed);
+    if (!budget) budget = KS_W_BUDGET_DEFAULT;
+    const size_t row_bytes = N * sizeof(u64);
+    size_t pc = batch, jg = Lk;
+    if (pc * nd * jg * row_bytes > budget) {
+        jg = std::max<size_t>(1, budget / (pc * nd * row_bytes));
+        if (jg > Lk) jg = Lk;
+        if (pc * nd * jg * row_bytes > budget) pc = std::max<size_t>(1, budget / (nd * jg * row_bytes));
+    }
+    jg = (Lk + ((Lk + jg - 1) / jg) - 1) / ((Lk + jg - 1) / jg);
+    pc = (batch + ((batch + pc - 1) / pc) - 1) / ((batch + pc - 1) / pc);
+    WsGuard w(pc * nd * jg * row_bytes, s);
+    const uint32_t cpr = N >= 512 ? (uint32_t)(N / 512) : 1u;
+    for (size_t b0 = 0; b0 < batch; b0 += pc) {
+        const size_t nb = std::min(pc, batch - b0);
+        for (size_t j0 = 0; j0 < Lk; j0 += jg) {
+            const size_t njg = std::min(jg, Lk - j0);
+            const unsigned grid_a = (unsigned)((nb * nd * njg) << g0);
+            const u64 *pp = c2.u() + b0 * PL;
+            auto stage_a = [&](auto lm, auto g) {
+                launch_ks_ntt<decltype(lm)::value, decltype(g)::value>(k_, narrow, rns, grid_a, s, pp, PL, w.u(), (uint32_t)j0,
+                                                                       (uint32_t)njg, 1u, nullptr);
+            };
+            if (g0 == 0)
+                with_logn<3, 14>(logm, "unsupported key-switch row size", [&](auto lm) { stage_a(lm, int_c<0>{}); });
+            else if (g0 == 1) stage_a(int_c<13>{}, int_c<1>{});
+            else if (g0 == 2) stage_a(int_c<13>{}, int_c<2>{});
+            else stage_a(int_c<13>{}, int_c<3>{});
+            for (size_t r0 = 0; r0 < nrot; r0 += k::HOIST_ROTS) {
+                const size_t nr = std::min<size_t>(k::HOIST_ROTS, nrot - r0);
+                k::HoistExps he{};
+                for (size_t r = 0; r < nr; r++) he.e[r] = exps[r0 + r];
+                const size_t grid_b = (((njg * cpr) + 7) / 8) * nb * nr * 8;
+                require(grid_b <= 0x7fffffffu, E_ARG, "hoisted rotations: the launch exceeds the grid limit; lower the W budget");
+                u64 *o = out + (b0 * nrot + r0) * 2 * PL;
+                FHE_LAUNCH("hoist_mac", k::hoist_mac_kernel, dim3((unsigned)grid_b), dim3(256), 0, s, w.u(), o, o + PL,
+                           (u64)nrot * 2 * PL, 2 * PL, ct + b0 * 2 * PL, 2 * PL, set.table.p, (uint32_t)r0, he, kc.dmods(),
+                           (uint32_t)nd, (uint32_t)Lk, (uint32_t)j0, (uint32_t)njg, logn, ct + b0 * 2 * PL + PL, 2 * PL,
+                           (uint32_t)nb, (uint32_t)nr);
+            }
+        }
+    }
+}
+
 // `&Ciphertext * &RGSWCiphertext` (F/bfv/rgsw_ciphertext.rs:122-156)
 inline void rgsw_mul(const Ksk &k0, const Ksk &k1, const u64 *ct, u64 *out, size_t batch, hipStream_t s) {
     const Ctx &cc = *k0.ct_ctx;

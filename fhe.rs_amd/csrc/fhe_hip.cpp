@@ -1446,6 +1446,25 @@ fhe_status fhe_bfv_expand_keyed_dev(const fhe_kskset *const *gks, size_t nlevels
         expand(first.data(), nlevels, ct, out, size, batch, as_stream(stream), keyed.data());
     });
 }
+// Hoisted rotations: nrot Galois elements of each ciphertext on one digit decomposition (engine.hpp: galois_hoisted).
+fhe_status fhe_bfv_galois_hoisted_dev(const fhe_kskset *gks, const size_t *exponents, size_t nrot, const uint64_t *ct,
+                                      uint64_t *out, size_t batch, void *stream) {
+    return guard([&] {
+        need(gks, "gks");
+        need(exponents, "exponents");
+        const KskSet &set = *gks->s;
+        if (nrot != set.keys.size())
+            throw StatusError(FHE_E_ARG, "hoisted rotations: " + std::to_string(nrot) + " exponents for a set of " +
+                                             std::to_string(set.keys.size()) + " keys");
+        set.ksk_ctx->need_device();
+        set_device(*set.ksk_ctx);
+        if (batch) {
+            need(ct, "ct");
+            need(out, "out");
+        }
+        galois_hoisted(set, exponents, nrot, ct, out, batch, as_stream(stream));
+    });
+}
 
 // ----------------------------------------------------------------------------- mul ----
 static std::unique_ptr<Mul> make_mul(const Scaler *el, const Scaler *er, const Scaler *dn, const Ksk *rk,

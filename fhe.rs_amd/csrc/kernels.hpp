@@ -14,6 +14,8 @@
 //   ks_fused_split_kernel   the same for N >= 32768: per 8192-point sub-block, first stages in the loader
 //   ks_mac_keyed_kernel     stage B of the unfused key switch with one key per group of polynomials (keyed batches:
 //                           KeySwitchingKey::key_switch client by client)   F/bfv/keys/key_switching_key.rs:241-320
+//   hoist_mac_kernel        stage B for many Galois elements of one ciphertext on ONE digit decomposition (hoisted
+//                           rotations; a restatement, not the reference's words: kernels_kshoist.hpp)
 //   scale_kernel            RnsScaler::scale per column             M/rns/scaler.rs:249-352, M/rq/scaler.rs:85-94
 //   switch_down_kernel      Poly::switch_down                       M/rq/mod.rs:433-492
 //   substitute_kernel       Poly::substitute                        M/rq/mod.rs:360-412
@@ -47,6 +49,7 @@
 #include "kernels_ntt.hpp"
 #include "kernels_ks.hpp"
 #include "kernels_kskeyed.hpp"
+#include "kernels_kshoist.hpp"
 #include "kernels_scaler.hpp"
 #include "kernels_misc.hpp"
 #include "kernels_encode.hpp"

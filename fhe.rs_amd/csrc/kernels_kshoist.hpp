@@ -1,0 +1,110 @@
+// kernels_kshoist.hpp -- stage B of the unfused key switch for MANY GALOIS ELEMENTS OF ONE CIPHERTEXT (hoisted
+// rotations, Halevi-Shoup CRYPTO 2018 section 4).  Stage A (ks_ntt_kernel, kernels_ks.hpp) reads neither a key nor an
+// exponent, and in Ntt form the substitution x -> x^e is a gather (galois_src_index): one set of transformed digit rows
+// W serves every rotation of the ciphertext, and only the multiply-accumulate below knows which rotation it forms.
+//
+// NOT the reference's words.  GaloisKey::relinearize (F/bfv/keys/galois_key.rs:63-86) lifts the digits of
+// substitute(c1); this kernel substitutes the lifted digits of c1.  Where the power-basis substitution negates a
+// coefficient x of row i the reference lifts q_i - x into q_j, and W holds -x mod q_j.  Both digit sets are = sigma(c1)
+// mod q_i with magnitude below q_i, so the two results decrypt to the same plaintext under the same noise bound, and
+// they are word-equal only at exponent 1.  The specification is the restatement of tests/hoist_ref.py:
+//   W[i][j] = NTT_j(PowerBasis(c1)_i mod q_j) (i != j),  W[i][i] = c1 row i,
+//   out_r.c0[j] = sigma_r(c0[j]) + sum_i sigma_r(W[i][j]) * gk_r.c0[i][j],   out_r.c1[j] = sum_i sigma_r(W[i][j]) * gk_r.c1[i][j]
+// with sigma_r the Ntt branch of Poly::substitute (M/rq/mod.rs:368-388) for exponent e_r, canonical outputs.
+#pragma once
+#include "kernels_kskeyed.hpp"
+
+namespace fhe {
+namespace k {
+
+// The exponents of one launch's rotations (mod 2N, odd), a kernel argument: a call with more rotations than the table
+// holds takes several launches on the same W, and nothing is uploaded.
+constexpr uint32_t HOIST_ROTS = 64;
+struct HoistExps {
+    uint32_t e[HOIST_ROTS];
+};
+
+// hoist_mac_kernel: ks_mac_keyed_kernel's sum for nb ciphertexts x nr rotations.  Kept from it: one lane per 16-byte
+// chunk of an output row, lazy 128-bit accumulators folded every sixteen digits, mul_wide62 / reduce_u128, the own row
+// read from `xhat` (the caller's unpermuted c1) and the addend from `addend0` (c0), canonical outputs.
+// What differs: output (b, r) reads W of ciphertext b and key rot0 + r of `keys` (block-uniform, through to_sgpr: both
+// key pointers and the exponent are scalars), and EVERY operand but the key is read through the gather of exponent
+// exps.e[r].  The two words of a chunk stay neighbours under it: e is odd, so destination roff + 1 (roff even) adds
+// N/2 to the index before the last bit reversal, which flips bit 0 of the source -- one 16-byte load at the even source
+// and a swap.  For destinations that differ only in their low k bits the sources are a permutation of one aligned block
+// of 2^k words, so a wave's 128 destination words read one aligned 1 KiB block of the source row.
+// W is read once per rotation: cached loads (ks_mac_keyed_kernel streams it).  The key words are read once per ciphertext.
+// Grid: ids 8 apart share a key range (j, chunk) as in ks_mac_kernel, so an XCD keeps to one eighth of the ranges.
+// Within a group of eight ranges the ciphertext runs fastest, then the rotation: the neighbours of a block on its XCD
+// are the other ciphertexts under the SAME key slice (read from HBM once, then from L2), and the rotations in flight
+// on an XCD at a time walk the same nb x ndigits rows of W (nb x 256 KiB at N = 8192 x 4 moduli: within the 4 MiB L2 up
+// to 16 ciphertexts, from the Infinity Cache above).  The other order (rotation fastest) would keep W hot and re-read
+// every key slice once per ciphertext; the keys are the larger operand from nr > nb / 2 on.
+__global__ void __launch_bounds__(256)
+    hoist_mac_kernel(const u64 *__restrict__ w, u64 *__restrict__ out0, u64 *__restrict__ out1, u64 out_poly_stride,
+                     u64 out_rot_stride, const u64 *__restrict__ addend0, u64 addend_poly_stride,
+                     const KsKeyPtr *__restrict__ keys, uint32_t rot0, HoistExps exps, const DevMod *__restrict__ mods,
+                     uint32_t ndigits, uint32_t lk, uint32_t j0, uint32_t jg, uint32_t logn, const u64 *__restrict__ xhat,
+                     u64 xhat_poly_stride, uint32_t nb, uint32_t nr) {
+    const uint32_t n = 1u << logn;
+    const uint32_t cpr = n >= 512 ? n / 512 : 1;          // 256-lane chunks per row
+    const uint32_t nkr = jg * cpr;                        // key ranges of this launch
+    const uint32_t grp = blockIdx.x >> 3, x8 = blockIdx.x & 7;
+    const uint32_t per = nb * nr;
+    const uint32_t krhi = grp / per, br = grp - krhi * per;
+    const uint32_t kr = krhi * 8 + x8;
+    if (kr >= nkr) return;                                // (block-uniform) tail of the rounded-up grid
+    const uint32_t r = to_sgpr(br / nb), b = br - r * nb; // (block-uniform) which rotation of which ciphertext
+    const uint32_t jj = kr / cpr, cb = kr - jj * cpr, j = j0 + jj;
+    const uint32_t ci = cb * 256 + threadIdx.x;           // 16-byte chunk inside the row
+    if (2 * ci >= n) return;
+    const uint32_t gal = exps.e[r];
+    const KsKeyPtr kp = keys[rot0 + r];
+    const DevMod md = mods[j];
+    const u64 roff = 2 * (u64)ci;
+    const uint32_t src = galois_src_index((uint32_t)roff, gal, logn);   // (the source of roff + 1 is src ^ 1)
+    const u64 soff = src & ~1u;
+    const bool swap = (src & 1u) != 0;
+    auto gather = [&](const u64 *row) {
+        const u64x2 v = *reinterpret_cast<const u64x2 *>(row + soff);
+        return swap ? u64x2{v.y, v.x} : v;
+    };
+    const u64 *wp = w + (((u64)b * ndigits) * jg + jj) * n;             // + i * jg * n per digit
+    const u64 *kp0 = kp.k0 + (u64)j * n + roff, *kp1 = kp.k1 + (u64)j * n + roff;   // + i * lk * n per digit
+    const u64 *xrow = xhat + (u64)b * xhat_poly_stride + (u64)j * n;
+    u128_t a0x = 0, a0y = 0, a1x = 0, a1y = 0;
+    auto mac = [&](u128_t &acc, u64 x, u64 k) {
+        u64 hi, lo;
+        mul_wide62(x, k, hi, lo);
+        acc += ((u128_t)hi << 64) | lo;
+    };
+    auto fold = [&](u128_t &acc) { acc = reduce_u128((u64)(acc >> 64), (u64)acc, md); };
+    for (uint32_t i0 = 0; i0 < ndigits; i0 += 16) {
+        const uint32_t i1 = i0 + 16 < ndigits ? i0 + 16 : ndigits;
+        if (i0) fold(a0x), fold(a0y), fold(a1x), fold(a1y);
+#pragma unroll 4
+        for (uint32_t i = i0; i < i1; i++) {
+            const u64x2 xv = gather(i == j ? xrow : wp + (u64)i * jg * n);   // (stage A skips the own row: W[j][j] = c1 row j)
+            const u64x2 q0 = *reinterpret_cast<const u64x2 *>(kp0 + (u64)i * lk * n);
+            const u64x2 q1 = *reinterpret_cast<const u64x2 *>(kp1 + (u64)i * lk * n);
+            mac(a0x, xv.x, q0.x);
+            mac(a0y, xv.y, q0.y);
+            mac(a1x, xv.x, q1.x);
+            mac(a1y, xv.y, q1.y);
+        }
+    }
+    u64x2 r0, r1;
+    r0.x = reduce_u128((u64)(a0x >> 64), (u64)a0x, md);
+    r0.y = reduce_u128((u64)(a0y >> 64), (u64)a0y, md);
+    r1.x = reduce_u128((u64)(a1x >> 64), (u64)a1x, md);
+    r1.y = reduce_u128((u64)(a1y >> 64), (u64)a1y, md);
+    const u64x2 a = gather(addend0 + (u64)b * addend_poly_stride + (u64)j * n);
+    r0.x = add_mod(r0.x, a.x, md.p);
+    r0.y = add_mod(r0.y, a.y, md.p);
+    const u64 ooff = (u64)b * out_poly_stride + (u64)r * out_rot_stride + (u64)j * n + roff;
+    *reinterpret_cast<u64x2 *>(out0 + ooff) = r0;
+    *reinterpret_cast<u64x2 *>(out1 + ooff) = r1;
+}
+
+}  // namespace k
+}  // namespace fhe

@@ -422,6 +422,26 @@ fhe_status fhe_bfv_inner_sum_keyed_dev(const fhe_kskset *const *gks, const size_
  * (N >> l) + 1.  ct [batch][2][L][N] -> out [size][batch][2][L][N].  Sets of different sizes -> FHE_E_PARAMETER_MISMATCH. */
 fhe_status fhe_bfv_expand_keyed_dev(const fhe_kskset *const *gks, size_t nlevels, const uint64_t *ct, uint64_t *out,
                                     size_t size, size_t batch, void *stream);
+/* Many Galois elements of each ciphertext from ONE digit decomposition (hoisting, Halevi-Shoup CRYPTO 2018 section 4; not
+ * in the reference).  A loop of fhe_bfv_galois_dev pays the digit transforms once per rotation; here R rotations cost
+ * one set of transforms and R multiply-accumulates (hoist_mac_kernel).
+ * THE OUTPUT IS NOT THE REFERENCE'S WORDS.  GaloisKey::relinearize lifts the digits of substitute(c1); this call
+ * substitutes the lifted digits of c1: with p = PowerBasis(c1), W[i][j] = NTT_j(p_i mod q_j) for i != j, W[i][i] = c1 row i,
+ * and sigma_r the Ntt branch of Poly::substitute (M/rq/mod.rs:368-388) for exponents[r],
+ *   out_r.c0[j] = sigma_r(c0[j]) + sum_i sigma_r(W[i][j]) * gk_r.c0[i][j],  out_r.c1[j] = sum_i sigma_r(W[i][j]) * gk_r.c1[i][j]
+ * (mod q_j, canonical; tests/hoist_ref.py).  Both digit sets are = sigma(c1) mod q_i with magnitude below q_i, so the result
+ * decrypts to what fhe_bfv_galois_dev's does under the same noise bound, but its words differ from that call's at every
+ * exponent except 1.
+ * gks: a set of nrot RNS-digit Galois keys at the ciphertext's level, key r for exponents[r] (host array, mod 2N); a
+ * repeated exponent is allowed.  ct [batch][2][L][N] Ntt -> out [batch][nrot][2][L][N] Ntt (the layout
+ * fhe_bfv_dot_product_scalar_dev reads as `count = nrot` ciphertexts per item).  The exponents travel as kernel arguments
+ * (64 per launch): the call only enqueues.  Device-pointer form only.
+ * NULL set or exponents, nrot != fhe_kskset_size, keys above the ciphertext's level, `out` overlapping `ct`, a NULL buffer
+ * with batch > 0 -> FHE_E_ARG; an even exponent -> FHE_E_INVALID_SUBSTITUTION_EXPONENT; batch == 0 is a no-op.
+ * No automatic choice between this call and a loop of single rotations is made: one rotation is faster through
+ * fhe_bfv_galois_dev, two or more through this call (tools/bench_hoisted.py measures both; STATE.md). */
+fhe_status fhe_bfv_galois_hoisted_dev(const fhe_kskset *gks, const size_t *exponents, size_t nrot, const uint64_t *ct,
+                                      uint64_t *out, size_t batch, void *stream);
 
 /* ------------------------------------------------------------- Multiplicator ---- */
 /* Multiplicator::new_leveled_internal + enable_relinearization + enable_mod_switching

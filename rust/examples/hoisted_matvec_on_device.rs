@@ -1,0 +1,21 @@
+//! A plaintext matrix times an encrypted SIMD vector by the diagonal method: every column rotation of the ciphertext
+//! from ONE digit decomposition (`HipKskSet::galois_hoisted_dev`), then the products with the diagonals and their sum in
+//! one `dot_product_scalar_dev`.  The rotations are not the reference's words (include/fhe_hip.h); they decrypt to the
+//! same plaintexts.
+//! (No Rust toolchain exists in the build image: reviewed source, not compiled there.)
+use std::sync::Arc;
+
+use fhe_math_hip::{DeviceBuffer, DeviceCiphertexts, HipCtx, HipError, HipKsk, HipKskSet, Stream};
+
+/// `galois_keys[r]` is the client's Galois key of element `exponents[r]` (3^(r + 1) mod 2N for the column rotations by
+/// 1, 2, ...), `diagonals` the `poly_ntt` rows of the matrix's diagonals 1 ... R, `[R][L][N]`.  Returns, per ciphertext,
+/// the sum over r of rotation r times diagonal r (diagonal 0 times the ciphertext itself is one `mul_plain_dev` more).
+pub fn rotated_products(ctx: &Arc<HipCtx>, galois_keys: &[&HipKsk], exponents: &[usize], ct: &DeviceCiphertexts,
+                        diagonals: &DeviceBuffer) -> Result<DeviceCiphertexts, HipError> {
+    let s = Stream::new(ctx.device())?;
+    let set = HipKskSet::new(galois_keys)?;                                   // built once per client, reused per query
+    let rotations = set.galois_hoisted_dev(exponents, ct, &s)?;               // [batch][R] ciphertexts, one stage A
+    let sum = ctx.dot_product_scalar_dev(exponents.len(), &rotations, diagonals, &s)?;
+    rotations.release_on(&s)?;
+    Ok(sum)
+}

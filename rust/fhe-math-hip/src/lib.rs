@@ -322,6 +322,25 @@ impl CtxView<'_> {
         })?;
         Ok(out)
     }
+    /// `bfv::dot_product_scalar` (ops/dot_product.rs:54-180) on device-resident operands (`fhe_bfv_dot_product_scalar_dev`):
+    /// `cts` holds `count` ciphertexts per item (`cts.batch` a multiple of `count`: the layout `galois_hoisted_dev` writes),
+    /// `pts` the `count` `poly_ntt` rows every item shares -> one ciphertext per item.
+    pub fn dot_product_scalar_dev(&self, count: usize, cts: &DeviceCiphertexts, pts: &DeviceBuffer, stream: &Stream) -> Result<DeviceCiphertexts> {
+        if count == 0 {
+            return Err(HipError { status: status::EMPTY_DOT_PRODUCT, message: "dot_product_scalar_dev: no operands".into() });
+        }
+        if cts.rows != self.nmoduli() || cts.degree != self.degree() {
+            return Err(shape_error("dot_product_scalar_dev: the ciphertexts do not live over this context"));
+        }
+        let items = whole_batch("dot_product_scalar_dev ciphertexts", cts.batch, count)?;
+        expect_len("dot_product_scalar_dev plaintexts", pts.len(), count * self.poly_words())?;
+        let out = DeviceCiphertexts::alloc_on(self.device(), items, cts.parts, cts.rows, cts.degree, cts.level, stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_dot_product_scalar_dev(self.ptr, cts.parts, count, cts.buf.as_ptr(), 0, pts.as_ptr(), 1, out.buf.as_mut_ptr(),
+                                                items, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
 }
 
 pub struct HipCtx {
@@ -675,6 +694,21 @@ impl<'k> HipKskSet<'k> {
         let out = DeviceCiphertexts::alloc_on(self.first.ct_ctx().device(), ct.batch, 2, ct.rows, ct.degree, ct.level, stream)?;
         check(unsafe {
             ffi::fhe_bfv_galois_keyed_dev(self.ptr, exponent, ct.buf.as_ptr(), out.buf.as_mut_ptr(), ct.batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+    /// Hoisted rotations (`fhe_bfv_galois_hoisted_dev`; not in the reference): the set holds ONE client's Galois keys, key
+    /// `r` for `exponents[r]`, and every ciphertext is rotated by all of them on one digit decomposition.  The result has
+    /// `ct.batch * exponents.len()` ciphertexts laid out `[batch][rotations]`, what `dot_product_scalar_dev` reads as
+    /// `count = exponents.len()` ciphertexts per item.  Its words are NOT those of a loop of `HipKsk::galois_dev` except at
+    /// exponent 1 (the header states the restatement); both decrypt to the same plaintext under the same noise bound.
+    pub fn galois_hoisted_dev(&self, exponents: &[usize], ct: &DeviceCiphertexts, stream: &Stream) -> Result<DeviceCiphertexts> {
+        self.first.check_resident("galois_hoisted_dev", ct, 2)?;
+        expect_len("galois_hoisted_dev exponents", exponents.len(), self.len)?;
+        let out = DeviceCiphertexts::alloc_on(self.first.ct_ctx().device(), ct.batch * self.len, 2, ct.rows, ct.degree, ct.level, stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_galois_hoisted_dev(self.ptr, exponents.as_ptr(), exponents.len(), ct.buf.as_ptr(), out.buf.as_mut_ptr(),
+                                            ct.batch, stream.as_ptr())
         })?;
         Ok(out)
     }
