@@ -1169,6 +1169,11 @@ class HoistedRotations:
     def rotate(self, ct):
         return self.set.relinearize_hoisted(self.exponents, ct)
 
+    def matvec(self, ct, pts, pt0=None):
+        """The diagonal form of a plaintext matrix times an encrypted vector in one call (KeySet.matvec_hoisted):
+        pt0 * ct + sum_r pts[r] * rotation_r(ct) -> [batch, 2, L, N] (or [2, L, N]); no rotated ciphertext is stored."""
+        return self.set.matvec_hoisted(self.exponents, ct, pts, pt0)
+
 
 class KeySet:
     """Keyed batches (fhe_kskset): the keys of many clients for ONE operation -- every client's relinearization key, or
@@ -1201,6 +1206,16 @@ class KeySet:
         """Bytes of transformed digit rows per launch pair (fhe_kskset_set_w_budget; 0 = default)."""
         check(_lib.lib().fhe_kskset_set_w_budget(self._h, int(nbytes)))
         return self
+
+    def set_rot_split(self, groups=0):
+        """Rotation groups of one launch of matvec_hoisted (fhe_kskset_set_rot_split; 0 = the engine's rule)."""
+        check(_lib.lib().fhe_kskset_set_rot_split(self._h, int(groups)))
+        return self
+
+    def rot_split(self):
+        g = C.c_size_t()
+        check(_lib.lib().fhe_kskset_get_rot_split(self._h, C.byref(g)))
+        return g.value
 
     def w_budget(self):
         w = C.c_size_t()
@@ -1269,6 +1284,35 @@ class KeySet:
         oshape = tuple(ct.shape[:-3]) + (len(exps),) + tuple(ct.shape[-3:])
         return self._run(ct, [oshape], lambda d, o: L.fhe_bfv_galois_hoisted_dev(
             self._h, arr, len(exps), _dptr(d), _dptr(o[0]), b, _stream()))[0]
+
+    def matvec_hoisted(self, exponents, ct, pts, pt0=None):
+        """Hoisted matrix-vector product (fhe_bfv_matvec_hoisted_dev): pt0 * ct + sum_r pts[r] * rotation_r(ct), the set
+        holding ONE client's Galois keys, key r for exponents[r].  ct [batch, 2, L, N] Ntt (or [2, L, N]); pts
+        `Plaintext::poly_ntt` rows, [R, L, N] shared by the batch or [batch, R, L, N]; pt0 None, [L, N] or [batch, L, N]
+        likewise -> [batch, 2, L, N] (or [2, L, N]), of ct's kind.  Word for word relinearize_hoisted followed by
+        Context.dot_product_scalar, and like it not the reference's words (include/fhe_hip.h)."""
+        L = _lib.lib()
+        ctx = self.ctx_ciphertext
+        if ct.shape[-3] != 2:
+            raise FheError(-13, "InvalidPolynomialCount: rotation expects 2 parts")
+        exps = [int(e) for e in exponents]
+        arr = (C.c_size_t * max(len(exps), 1))(*exps)
+        lead = tuple(ct.shape[:-3])
+        b = ctx._batch(ct) // 2
+        shared = len(pts.shape) == 3
+        want = ((len(exps),) if shared else lead + (len(exps),)) + (ctx.nmoduli, ctx.degree)
+        if tuple(pts.shape) != want:
+            raise FheError(-1, "DotProductLengthMismatch: diagonals %s, expected %s" % (tuple(pts.shape), want))
+        if pt0 is not None and tuple(pt0.shape) != (() if shared else lead) + (ctx.nmoduli, ctx.degree):
+            raise FheError(-1, "DotProductLengthMismatch: the identity diagonal follows the diagonals' batch shape")
+        host = not _is_dev(ct)
+        dev = max(self.ctx_ksk.device, 0)
+        stage = (lambda a: DeviceArray.from_numpy(_np(a), dev)) if host else (lambda a: a)
+        d, p, p0 = stage(ct), stage(pts), (None if pt0 is None else stage(pt0))
+        out = DeviceArray(tuple(ct.shape), dev) if host else _empty_dev(d, tuple(ct.shape))
+        check(L.fhe_bfv_matvec_hoisted_dev(self._h, arr, len(exps), _dptr(d), _dptr(p), 1 if shared else 0,
+                                           None if p0 is None else _dptr(p0), _dptr(out), b, _stream()))
+        return out.download() if host else out
 
 
 class EvaluationKeySet:

@@ -1475,6 +1475,7 @@ struct KskSet {
     const Ctx *ct_ctx = nullptr, *ksk_ctx = nullptr;
     size_t ndigits = 0;
     std::atomic<size_t> w_budget{0};   // as Ksk::w_budget; 0 = default
+    std::atomic<size_t> rot_split{0};  // rotation groups of a hoisted matvec launch (hoist_rot_group); 0 = the rule
 };
 // The trailing optional argument of key_switch_polys / key_switch_add / galois_apply (one), inner_sum (one per rotation)
 // and expand (one per level): polynomial b of the call takes key (b / per_key) % nkeys of `set`.
@@ -2182,33 +2183,30 @@ inline void galois_apply(const Ksk &ks, size_t exponent, const u64 *ct, u64 *out
                    nullptr, keyed);
 }
 
-// Hoisted rotations (kernels_kshoist.hpp; not in the reference, whose words this does NOT reproduce except at exponent
-// 1 -- the restatement is tests/hoist_ref.py): the Galois elements exponents[r], r < nrot, of each ciphertext under key r
-// of `set`, from ONE digit decomposition.  ct [batch][2][L][N] Ntt -> out [batch][nrot][2][L][N] Ntt.
-// One inverse transform of c1 (no substitution), then key_switch_polys_keyed's geometry unchanged -- tile choice, `narrow`,
-// `rns`, the W budget rule with equal chunks of ciphertexts and equal groups of key moduli -- with one stage A per (chunk,
-// group) and, on its W, one hoist_mac_kernel launch per k::HOIST_ROTS rotations.  Nothing is uploaded: the exponents
-// travel as kernel arguments.  R rotations cost one stage A and R multiply-accumulates; a loop of galois_apply pays the
-// transforms R times.
-inline void galois_hoisted(const KskSet &set, const size_t *exponents, size_t nrot, const u64 *ct, u64 *out, size_t batch,
-                           hipStream_t s) {
-    const Ksk &k_ = *set.keys[0];
+// What galois_hoisted and matvec_hoisted share.  hoist_exponents: the refusals of the exponent list and the level, the
+// exponents reduced mod 2N.  hoist_each_w: one inverse transform of c1 (no substitution), then key_switch_polys_keyed's
+// geometry unchanged -- tile choice, `narrow`, `rns`, the W budget rule with equal chunks of ciphertexts and equal groups
+// of key moduli -- and ONE stage A per (chunk, group); stage_b(b0, nb, j0, njg, w) then runs on that W.
+inline std::vector<uint32_t> hoist_exponents(const KskSet &set, const size_t *exponents, size_t nrot, const std::string &what) {
     const Ctx &kc = *set.ksk_ctx, &cc = *set.ct_ctx;
     require(exponents != nullptr, E_ARG, "null argument: exponents");
-    require(nrot == set.keys.size(), E_ARG, "hoisted rotations: one exponent per key of the set");
-    const size_t N = kc.n, nd = set.ndigits, Lk = kc.L;
+    require(nrot == set.keys.size(), E_ARG, (what + ": one exponent per key of the set").c_str());
     std::vector<uint32_t> exps(nrot);
     for (size_t r = 0; r < nrot; r++) {
-        exps[r] = (uint32_t)(exponents[r] % (2 * N));
+        exps[r] = (uint32_t)(exponents[r] % (2 * kc.n));
         require((exps[r] & 1) == 1, E_INVALID_SUBST, "InvalidSubstitutionExponent");
     }
     if (kc.niterations_to(cc) != 0)
-        throw StatusError(E_ARG, "hoisted rotations: the keys must sit at the ciphertext's level (" + std::to_string(cc.L) +
-                                     " moduli), not above it (" + std::to_string(Lk) + ")");
-    if (!batch) return;
+        throw StatusError(E_ARG, what + ": the keys must sit at the ciphertext's level (" + std::to_string(cc.L) +
+                                     " moduli), not above it (" + std::to_string(kc.L) + ")");
+    return exps;
+}
+template <class StageB>
+inline void hoist_each_w(const KskSet &set, const u64 *ct, size_t batch, hipStream_t s, StageB &&stage_b) {
+    const Ksk &k_ = *set.keys[0];
+    const Ctx &kc = *set.ksk_ctx, &cc = *set.ct_ctx;
+    const size_t N = kc.n, nd = set.ndigits, Lk = kc.L;
     const u64 PL = (u64)cc.L * N;
-    require(!(out < ct + batch * 2 * PL && ct < out + batch * nrot * 2 * PL), E_ARG,
-            "hoisted rotations: `out` overlaps `ct` (every rotation gathers from the whole input)");
     kc.need_device();
     const uint32_t logn = (uint32_t)kc.logn;
     WsGuard c2(batch * PL * sizeof(u64), s);
@@ -2233,7 +2231,6 @@ inline void galois_hoisted(const KskSet &set, const size_t *exponents, size_t nr
     jg = (Lk + ((Lk + jg - 1) / jg) - 1) / ((Lk + jg - 1) / jg);
     pc = (batch + ((batch + pc - 1) / pc) - 1) / ((batch + pc - 1) / pc);
     WsGuard w(pc * nd * jg * row_bytes, s);
-    const uint32_t cpr = N >= 512 ? (uint32_t)(N / 512) : 1u;
     for (size_t b0 = 0; b0 < batch; b0 += pc) {
         const size_t nb = std::min(pc, batch - b0);
         for (size_t j0 = 0; j0 < Lk; j0 += jg) {
@@ -2249,20 +2246,133 @@ inline void galois_hoisted(const KskSet &set, const size_t *exponents, size_t nr
             else if (g0 == 1) stage_a(int_c<13>{}, int_c<1>{});
             else if (g0 == 2) stage_a(int_c<13>{}, int_c<2>{});
             else stage_a(int_c<13>{}, int_c<3>{});
-            for (size_t r0 = 0; r0 < nrot; r0 += k::HOIST_ROTS) {
-                const size_t nr = std::min<size_t>(k::HOIST_ROTS, nrot - r0);
-                k::HoistExps he{};
-                for (size_t r = 0; r < nr; r++) he.e[r] = exps[r0 + r];
-                const size_t grid_b = (((njg * cpr) + 7) / 8) * nb * nr * 8;
-                require(grid_b <= 0x7fffffffu, E_ARG, "hoisted rotations: the launch exceeds the grid limit; lower the W budget");
-                u64 *o = out + (b0 * nrot + r0) * 2 * PL;
-                FHE_LAUNCH("hoist_mac", k::hoist_mac_kernel, dim3((unsigned)grid_b), dim3(256), 0, s, w.u(), o, o + PL,
-                           (u64)nrot * 2 * PL, 2 * PL, ct + b0 * 2 * PL, 2 * PL, set.table.p, (uint32_t)r0, he, kc.dmods(),
-                           (uint32_t)nd, (uint32_t)Lk, (uint32_t)j0, (uint32_t)njg, logn, ct + b0 * 2 * PL + PL, 2 * PL,
-                           (uint32_t)nb, (uint32_t)nr);
-            }
+            stage_b(b0, nb, j0, njg, w.u());
         }
     }
+}
+// (blocks of a stage B over nb ciphertexts x njg key moduli x `per` rotations or rotation groups: key ranges in eights)
+inline size_t hoist_grid_b(const Ctx &kc, size_t njg, size_t nb, size_t per) {
+    const size_t cpr = kc.n >= 512 ? kc.n / 512 : 1;
+    const size_t grid_b = (((njg * cpr) + 7) / 8) * nb * per * 8;
+    require(grid_b <= 0x7fffffffu, E_ARG, "hoisted rotations: the launch exceeds the grid limit; lower the W budget");
+    return grid_b;
+}
+
+// Hoisted rotations (kernels_kshoist.hpp; not in the reference, whose words this does NOT reproduce except at exponent
+// 1 -- the restatement is tests/hoist_ref.py): the Galois elements exponents[r], r < nrot, of each ciphertext under key r
+// of `set`, from ONE digit decomposition.  ct [batch][2][L][N] Ntt -> out [batch][nrot][2][L][N] Ntt.
+// The transforms and geometry of hoist_each_w, and on each W one hoist_mac_kernel launch per k::HOIST_ROTS rotations.
+// Nothing is uploaded: the exponents travel as kernel arguments.  R rotations cost one stage A and R
+// multiply-accumulates; a loop of galois_apply pays the transforms R times.
+inline void galois_hoisted(const KskSet &set, const size_t *exponents, size_t nrot, const u64 *ct, u64 *out, size_t batch,
+                           hipStream_t s) {
+    const Ctx &kc = *set.ksk_ctx, &cc = *set.ct_ctx;
+    const std::vector<uint32_t> exps = hoist_exponents(set, exponents, nrot, "hoisted rotations");
+    if (!batch) return;
+    const u64 PL = (u64)cc.L * kc.n;
+    require(!(out < ct + batch * 2 * PL && ct < out + batch * nrot * 2 * PL), E_ARG,
+            "hoisted rotations: `out` overlaps `ct` (every rotation gathers from the whole input)");
+    hoist_each_w(set, ct, batch, s, [&](size_t b0, size_t nb, size_t j0, size_t njg, const u64 *w) {
+        for (size_t r0 = 0; r0 < nrot; r0 += k::HOIST_ROTS) {
+            const size_t nr = std::min<size_t>(k::HOIST_ROTS, nrot - r0);
+            k::HoistExps he{};
+            for (size_t r = 0; r < nr; r++) he.e[r] = exps[r0 + r];
+            const size_t grid_b = hoist_grid_b(kc, njg, nb, nr);
+            u64 *o = out + (b0 * nrot + r0) * 2 * PL;
+            FHE_LAUNCH("hoist_mac", k::hoist_mac_kernel, dim3((unsigned)grid_b), dim3(256), 0, s, w, o, o + PL,
+                       (u64)nrot * 2 * PL, 2 * PL, ct + b0 * 2 * PL, 2 * PL, set.table.p, (uint32_t)r0, he, kc.dmods(),
+                       (uint32_t)set.ndigits, (uint32_t)kc.L, (uint32_t)j0, (uint32_t)njg, (uint32_t)kc.logn,
+                       ct + b0 * 2 * PL + PL, 2 * PL, (uint32_t)nb, (uint32_t)nr);
+        }
+    });
+}
+
+inline void mbfv_sum(const Ctx &c, const u64 *shares, size_t nshares, u64 share_stride, size_t npolys, const u64 *base,
+                     u64 base_stride, u64 *out, hipStream_t s);   // (defined with the multiparty protocols below)
+
+// The rotation groups of one hoist_matvec_kernel launch over nr rotations (the ONE statement of the rule).  A block per
+// (ciphertext, key range) leaves a small batch short of the device -- batch 1 at N = 8192 x 4 moduli is 64 blocks -- so
+// the rotations are cut into groups whose blocks run side by side until the launch has two blocks per compute unit
+// (256 lanes a block, four blocks resident on a unit at the kernel's register count: two per unit keep every SIMD busy
+// with room for the tail), never into more groups than rotations.  A shape rule in the manner of sub14, no fit to
+// timings.  forced != 0 (fhe_kskset_set_rot_split): that many groups, clamped likewise.  Returns rotations per group;
+// the groups are ceil(nr / it), so none is empty.
+inline size_t hoist_rot_group(const Ctx &kc, size_t forced, size_t nb, size_t njg, size_t nr) {
+    const size_t cpr = kc.n >= 512 ? kc.n / 512 : 1;
+    size_t groups = forced;
+    if (!groups) {
+        const size_t blocks = nb * njg * cpr, want = 2 * (size_t)device_cus(kc.device);
+        groups = blocks >= want ? 1 : (want + blocks - 1) / blocks;
+    }
+    groups = std::min(groups, nr);
+    return (nr + groups - 1) / groups;
+}
+
+// Hoisted matrix-vector product (hoist_matvec_kernel; a restatement like galois_hoisted, whose caveat it inherits): the
+// diagonal form of a plaintext matrix times an encrypted vector, out = pt0 ct + sum_r pts_r rot_r(ct), in ONE call whose
+// only output is the result: word for word galois_hoisted followed by dot_product_scalar over (ct, rotations) and (pt0,
+// pts), without the [batch][nrot] block of rotated ciphertexts between them.
+// ct [batch][2][L][N] Ntt; pts [nrot][L][N] (pts_shared) or [batch][nrot][L][N]; pt0 NULL, [L][N] or [batch][L][N]; out
+// [batch][2][L][N].  galois_hoisted's transforms and geometry (hoist_each_w); on each W one launch per k::HOIST_ROTS
+// rotations, each cut into rotation groups (hoist_rot_group).  A call with ONE group in all writes `out` directly.
+// Otherwise every group writes a partial [batch][2][L][N] sum into wiped workspace and ONE mbfv_sum_kernel launch (its
+// layout serves: `shares` = partial sums, polynomials = batch x 2) adds them into `out` at the end.
+inline void matvec_hoisted(const KskSet &set, const size_t *exponents, size_t nrot, const u64 *ct, const u64 *pts,
+                           bool pts_shared, const u64 *pt0, u64 *out, size_t batch, hipStream_t s) {
+    const Ctx &kc = *set.ksk_ctx, &cc = *set.ct_ctx;
+    const std::vector<uint32_t> exps = hoist_exponents(set, exponents, nrot, "hoisted matvec");
+    if (!batch) return;
+    const u64 PL = (u64)cc.L * kc.n;
+    auto overlaps = [&](const u64 *p, u64 words) { return p != nullptr && out < p + words && p < out + batch * 2 * PL; };
+    require(!overlaps(ct, batch * 2 * PL), E_ARG,
+            "hoisted matvec: `out` overlaps `ct` (every rotation gathers from the whole input)");
+    require(!overlaps(pts, (pts_shared ? 1 : batch) * nrot * PL), E_ARG, "hoisted matvec: `out` overlaps `pts`");
+    require(!overlaps(pt0, (pts_shared ? 1 : batch) * PL), E_ARG, "hoisted matvec: `out` overlaps `pt0`");
+    require((((uintptr_t)ct | (uintptr_t)pts | (uintptr_t)pt0 | (uintptr_t)out) & 15) == 0, E_ARG,
+            "hoisted matvec: buffers must be 16-byte aligned");
+    const size_t forced = set.rot_split.load(std::memory_order_relaxed);
+    // The launches on one W and where their groups' partial sums go.  The plan is made once, on the first W -- the largest:
+    // chunks and key-modulus groups are equal but for the last -- and serves every W, so that the call has ONE number of
+    // partial sums and every (ciphertext, key modulus) is written in each of them exactly once.
+    struct Launch {
+        size_t r0, nr, rpg, ngroups, first;   // `first`: index of its group 0 among the call's partial sums
+    };
+    std::vector<Launch> plan;
+    auto make_plan = [&](size_t nb, size_t njg) {
+        plan.clear();
+        size_t total = 0;
+        for (size_t r0 = 0; r0 < nrot; r0 += k::HOIST_ROTS) {
+            const size_t nr = std::min<size_t>(k::HOIST_ROTS, nrot - r0);
+            const size_t rpg = hoist_rot_group(kc, forced, nb, njg, nr);
+            const size_t ng = (nr + rpg - 1) / rpg;
+            plan.push_back({r0, nr, rpg, ng, total});
+            total += ng;
+        }
+        return total;
+    };
+    size_t nparts = 0;
+    std::unique_ptr<WsGuard> partial;
+    const u64 part_words = (u64)batch * 2 * PL;
+    hoist_each_w(set, ct, batch, s, [&](size_t b0, size_t nb, size_t j0, size_t njg, const u64 *w) {
+        if (!nparts) {
+            nparts = make_plan(nb, njg);
+            if (nparts > 1) partial = std::make_unique<WsGuard>(nparts * part_words * sizeof(u64), s, true);
+        }
+        for (const Launch &l : plan) {
+            k::HoistExps he{};
+            for (size_t r = 0; r < l.nr; r++) he.e[r] = exps[l.r0 + r];
+            const size_t grid_b = hoist_grid_b(kc, njg, nb, l.ngroups);
+            u64 *o = (nparts > 1 ? partial->u() + l.first * part_words : out) + b0 * 2 * PL;
+            const u64 *c = ct + b0 * 2 * PL;
+            FHE_LAUNCH("hoist_matvec", k::hoist_matvec_kernel, dim3((unsigned)grid_b), dim3(256), 0, s, w, o, o + PL, 2 * PL,
+                       part_words, c, c + PL, 2 * PL, set.table.p, (uint32_t)l.r0, he,
+                       pts + (pts_shared ? 0 : b0 * nrot * PL) + l.r0 * PL, pts_shared ? (u64)0 : (u64)nrot * PL, PL,
+                       l.r0 == 0 && pt0 ? pt0 + (pts_shared ? 0 : b0 * PL) : nullptr, pts_shared ? (u64)0 : PL, kc.dmods(),
+                       (uint32_t)set.ndigits, (uint32_t)kc.L, (uint32_t)j0, (uint32_t)njg, (uint32_t)kc.logn, (uint32_t)nb,
+                       (uint32_t)l.nr, (uint32_t)l.rpg, (uint32_t)l.ngroups);
+        }
+    });
+    if (nparts > 1) mbfv_sum(cc, partial->u(), nparts, part_words, batch * 2, nullptr, 0, out, s);
 }
 
 // `&Ciphertext * &RGSWCiphertext` (F/bfv/rgsw_ciphertext.rs:122-156)

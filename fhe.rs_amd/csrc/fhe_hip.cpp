@@ -1353,6 +1353,19 @@ fhe_status fhe_kskset_get_w_budget(const fhe_kskset *s, size_t *bytes) {
         *bytes = s->s->w_budget.load(std::memory_order_relaxed);
     });
 }
+fhe_status fhe_kskset_set_rot_split(fhe_kskset *s, size_t groups) {
+    return guard([&] {
+        need(s, "set");
+        s->s->rot_split.store(groups, std::memory_order_relaxed);
+    });
+}
+fhe_status fhe_kskset_get_rot_split(const fhe_kskset *s, size_t *groups) {
+    return guard([&] {
+        need(s, "set");
+        need(groups, "groups");
+        *groups = s->s->rot_split.load(std::memory_order_relaxed);
+    });
+}
 // The checks every keyed call shares; returns items per key (0: nothing to do).
 static size_t keyed_per_key(const KskSet &set, size_t batch) {
     set.ksk_ctx->need_device();
@@ -1463,6 +1476,28 @@ fhe_status fhe_bfv_galois_hoisted_dev(const fhe_kskset *gks, const size_t *expon
             need(out, "out");
         }
         galois_hoisted(set, exponents, nrot, ct, out, batch, as_stream(stream));
+    });
+}
+// Hoisted matrix-vector product: the rotations, the products with the diagonals and their sum in one stage B (engine.hpp:
+// matvec_hoisted).
+fhe_status fhe_bfv_matvec_hoisted_dev(const fhe_kskset *gks, const size_t *exponents, size_t nrot, const uint64_t *ct,
+                                      const uint64_t *pts, int pts_shared, const uint64_t *pt0, uint64_t *out, size_t batch,
+                                      void *stream) {
+    return guard([&] {
+        need(gks, "gks");
+        need(exponents, "exponents");
+        const KskSet &set = *gks->s;
+        if (nrot != set.keys.size())
+            throw StatusError(FHE_E_ARG, "hoisted matvec: " + std::to_string(nrot) + " exponents for a set of " +
+                                             std::to_string(set.keys.size()) + " keys");
+        set.ksk_ctx->need_device();
+        set_device(*set.ksk_ctx);
+        if (batch) {
+            need(ct, "ct");
+            need(pts, "pts");
+            need(out, "out");
+        }
+        matvec_hoisted(set, exponents, nrot, ct, pts, pts_shared != 0, pt0, out, batch, as_stream(stream));
     });
 }
 

@@ -16,6 +16,8 @@
 //                           KeySwitchingKey::key_switch client by client)   F/bfv/keys/key_switching_key.rs:241-320
 //   hoist_mac_kernel        stage B for many Galois elements of one ciphertext on ONE digit decomposition (hoisted
 //                           rotations; a restatement, not the reference's words: kernels_kshoist.hpp)
+//   hoist_matvec_kernel     the same with each rotation multiplied by its plaintext diagonal and the products summed in
+//                           registers (a plaintext matrix times an encrypted vector; hoist_mac_kernel + dot_kernel's words)
 //   scale_kernel            RnsScaler::scale per column             M/rns/scaler.rs:249-352, M/rq/scaler.rs:85-94
 //   switch_down_kernel      Poly::switch_down                       M/rq/mod.rs:433-492
 //   substitute_kernel       Poly::substitute                        M/rq/mod.rs:360-412

@@ -403,6 +403,10 @@ void fhe_kskset_destroy(fhe_kskset *s);
 size_t fhe_kskset_size(const fhe_kskset *s);
 fhe_status fhe_kskset_set_w_budget(fhe_kskset *s, size_t bytes);
 fhe_status fhe_kskset_get_w_budget(const fhe_kskset *s, size_t *bytes);
+/* Rotation groups of one launch of fhe_bfv_matvec_hoisted_dev (below): 0 = the engine's rule, k = k groups, clamped to
+ * the rotations of the launch.  It changes how the work is cut, never a word of the result. */
+fhe_status fhe_kskset_set_rot_split(fhe_kskset *s, size_t groups);
+fhe_status fhe_kskset_get_rot_split(const fhe_kskset *s, size_t *groups);
 /* KeySwitchingKey::key_switch (:241-320) per client: p [batch][L][N] PowerBasis -> c0_out, c1_out [batch][Lk][N] Ntt. */
 fhe_status fhe_key_switch_keyed_dev(const fhe_kskset *s, const uint64_t *p, uint64_t *c0_out, uint64_t *c1_out,
                                     size_t batch, void *stream);
@@ -442,6 +446,33 @@ fhe_status fhe_bfv_expand_keyed_dev(const fhe_kskset *const *gks, size_t nlevels
  * fhe_bfv_galois_dev, two or more through this call (tools/bench_hoisted.py measures both; STATE.md). */
 fhe_status fhe_bfv_galois_hoisted_dev(const fhe_kskset *gks, const size_t *exponents, size_t nrot, const uint64_t *ct,
                                       uint64_t *out, size_t batch, void *stream);
+/* Hoisted matrix-vector product: the diagonal form of a plaintext matrix times an encrypted vector in ONE call whose only
+ * output is the result ciphertext (hoist_matvec_kernel; not in the reference).  With W and sigma_r as above,
+ *   out.c0[j] = pt0[j] c0[j] + sum_r pts_r[j] (sigma_r(c0[j]) + sum_i sigma_r(W[i][j]) gk_r.c0[i][j])
+ *   out.c1[j] = pt0[j] c1[j] + sum_r pts_r[j]                   sum_i sigma_r(W[i][j]) gk_r.c1[i][j]
+ * (mod q_j, canonical; tests/hoistmv_ref.py).  This equals, word for word, fhe_bfv_galois_hoisted_dev followed by
+ * fhe_bfv_dot_product_scalar_dev(ctx, 2, nrot or nrot + 1, ...) with the unrotated ciphertext and pt0 first when pt0 is
+ * given -- that composition is the specification -- without writing and re-reading the [batch][nrot] rotated ciphertexts.
+ * LIKE THAT CALL'S, THE OUTPUT IS NOT THE REFERENCE'S WORDS: the rotations inside it substitute the lifted digits of c1
+ * where GaloisKey::relinearize lifts the digits of substitute(c1), so the result decrypts to what a loop of
+ * fhe_bfv_galois_dev and a dot product gives, under the same noise bound, but differs from it word for word unless
+ * every exponent is 1.
+ * gks, exponents, nrot: as fhe_bfv_galois_hoisted_dev (a repeated exponent is allowed).  ct [batch][2][L][N] Ntt.  pts:
+ * Plaintext::poly_ntt rows over the ciphertext's context, [nrot][L][N] shared by the batch when pts_shared != 0, else
+ * [batch][nrot][L][N].  pt0: the identity diagonal (the term of the unrotated ciphertext: no Galois key of exponent 1 is
+ * needed, and no key switch adds its noise), [L][N] or [batch][L][N] by the same flag, NULL for none.
+ * out [batch][2][L][N] Ntt.  16-byte aligned buffers.  Device-pointer form only; the call only enqueues.
+ * A launch covers 64 rotations; its rotations may be cut into groups whose blocks run side by side
+ * (fhe_kskset_set_rot_split: 0 = a rule on the shape and the device's compute units, k = k groups, clamped to the
+ * rotations of a launch).  A call that is one group writes `out` directly; otherwise the groups write partial sums into
+ * wiped workspace and one more launch adds them.  The result does not depend on the split.
+ * NULL set, exponents, or ct / pts / out with batch > 0, nrot != fhe_kskset_size, keys above the ciphertext's level, `out`
+ * overlapping ct, pts or pt0 -> FHE_E_ARG; an even exponent -> FHE_E_INVALID_SUBSTITUTION_EXPONENT; batch == 0 is a no-op
+ * (NULL buffers allowed).  A refused call leaves `out` untouched.
+ * No automatic choice between this call and the composition is made (tools/bench_hoisted_matvec.py measures both). */
+fhe_status fhe_bfv_matvec_hoisted_dev(const fhe_kskset *gks, const size_t *exponents, size_t nrot, const uint64_t *ct,
+                                      const uint64_t *pts, int pts_shared, const uint64_t *pt0, uint64_t *out, size_t batch,
+                                      void *stream);
 
 /* ------------------------------------------------------------- Multiplicator ---- */
 /* Multiplicator::new_leveled_internal + enable_relinearization + enable_mod_switching

@@ -19,3 +19,15 @@ pub fn rotated_products(ctx: &Arc<HipCtx>, galois_keys: &[&HipKsk], exponents: &
     rotations.release_on(&s)?;
     Ok(sum)
 }
+
+/// The same product in ONE call (`HipKskSet::matvec_hoisted_dev`): the rotations never reach memory, and `diagonal0`
+/// (`[L][N]`) multiplies the ciphertext itself, so the whole matrix-vector product is the result.  `groups`: rotation
+/// groups per launch for a host that has measured its shape (0 keeps the engine's rule).
+pub fn matrix_times_vector(galois_keys: &[&HipKsk], exponents: &[usize], ct: &DeviceCiphertexts, diagonals: &DeviceBuffer,
+                           diagonal0: &DeviceBuffer, groups: usize, s: &Stream) -> Result<DeviceCiphertexts, HipError> {
+    let set = HipKskSet::new(galois_keys)?;
+    if set.rot_split()? != groups {
+        set.set_rot_split(groups)?;
+    }
+    set.matvec_hoisted_dev(exponents, ct, diagonals, Some(diagonal0), s)
+}

@@ -663,6 +663,15 @@ impl<'k> HipKskSet<'k> {
         check(unsafe { ffi::fhe_kskset_get_w_budget(self.ptr, &mut bytes) })?;
         Ok(bytes)
     }
+    /// Rotation groups of one launch of `matvec_hoisted_dev` (`fhe_kskset_set_rot_split`; 0 = the engine's rule).
+    pub fn set_rot_split(&self, groups: usize) -> Result<()> {
+        check(unsafe { ffi::fhe_kskset_set_rot_split(self.ptr, groups) })
+    }
+    pub fn rot_split(&self) -> Result<usize> {
+        let mut groups = 0usize;
+        check(unsafe { ffi::fhe_kskset_get_rot_split(self.ptr, &mut groups) })?;
+        Ok(groups)
+    }
     fn check_keyed(&self, what: &str, ct: &DeviceCiphertexts, parts: usize) -> Result<()> {
         self.first.check_resident(what, ct, parts)?;
         if ct.batch % self.len != 0 {
@@ -709,6 +718,32 @@ impl<'k> HipKskSet<'k> {
         check(unsafe {
             ffi::fhe_bfv_galois_hoisted_dev(self.ptr, exponents.as_ptr(), exponents.len(), ct.buf.as_ptr(), out.buf.as_mut_ptr(),
                                             ct.batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+    /// Hoisted matrix-vector product (`fhe_bfv_matvec_hoisted_dev`; not in the reference): `pt0 * ct` plus the sum over `r`
+    /// of `diagonals[r]` times rotation `r` of `ct`, in one call whose only output is the result -- what
+    /// `galois_hoisted_dev` followed by `dot_product_scalar_dev` gives, word for word, without the `[batch][rotations]`
+    /// block between them (and, like it, NOT the reference's words; the header states the restatement).  `diagonals`
+    /// holds `poly_ntt` rows, `[R][L][N]` shared by the batch or `[batch][R][L][N]`; `pt0` is the identity diagonal
+    /// (`[L][N]` or `[batch][L][N]`, the same way), `None` for none.
+    pub fn matvec_hoisted_dev(&self, exponents: &[usize], ct: &DeviceCiphertexts, diagonals: &DeviceBuffer, pt0: Option<&DeviceBuffer>,
+                              stream: &Stream) -> Result<DeviceCiphertexts> {
+        self.first.check_resident("matvec_hoisted_dev", ct, 2)?;
+        expect_len("matvec_hoisted_dev exponents", exponents.len(), self.len)?;
+        let poly = ct.rows * ct.degree;
+        let shared = diagonals.len() == self.len * poly;
+        if !shared {
+            expect_len("matvec_hoisted_dev diagonals", diagonals.len(), ct.batch * self.len * poly)?;
+        }
+        if let Some(p) = pt0 {
+            expect_len("matvec_hoisted_dev identity diagonal", p.len(), if shared { poly } else { ct.batch * poly })?;
+        }
+        let out = DeviceCiphertexts::alloc_on(self.first.ct_ctx().device(), ct.batch, 2, ct.rows, ct.degree, ct.level, stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_matvec_hoisted_dev(self.ptr, exponents.as_ptr(), exponents.len(), ct.buf.as_ptr(), diagonals.as_ptr(),
+                                            shared as c_int, pt0.map_or(ptr::null(), |p| p.as_ptr()), out.buf.as_mut_ptr(), ct.batch,
+                                            stream.as_ptr())
         })?;
         Ok(out)
     }
