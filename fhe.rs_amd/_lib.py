@@ -130,6 +130,8 @@ SIGNATURES = {
     "fhe_kskset_get_w_budget": (i32, [vp, szp]),
     "fhe_kskset_set_rot_split": (i32, [vp, sz]),
     "fhe_kskset_get_rot_split": (i32, [vp, szp]),
+    "fhe_kskset_set_bsgs_tile": (i32, [vp, sz]),
+    "fhe_kskset_get_bsgs_tile": (i32, [vp, szp]),
     "fhe_key_switch_keyed_dev": (i32, [vp, vp, vp, vp, sz, vp]),
     "fhe_bfv_relinearize_keyed_dev": (i32, [vp, vp, vp, sz, vp]),
     "fhe_bfv_galois_keyed_dev": (i32, [vp, sz, vp, vp, sz, vp]),
@@ -137,6 +139,7 @@ SIGNATURES = {
     "fhe_bfv_expand_keyed_dev": (i32, [C.POINTER(vp), sz, vp, vp, sz, sz, vp]),
     "fhe_bfv_galois_hoisted_dev": (i32, [vp, szp, sz, vp, vp, sz, vp]),
     "fhe_bfv_matvec_hoisted_dev": (i32, [vp, szp, sz, vp, vp, i32, vp, vp, sz, vp]),
+    "fhe_bfv_matvec_bsgs_dev": (i32, [vp, szp, sz, vp, szp, sz, vp, vp, i32, vp, sz, vp]),
     "fhe_mul_create": (i32, [vp, vp, vp, vp, i32, C.POINTER(vp)]),
     "fhe_mul_destroy": (None, [vp]),
     "fhe_mul_out_shape": (i32, [vp, szp, szp]),

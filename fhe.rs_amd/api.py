@@ -1152,6 +1152,26 @@ class EvaluationKey:
             raise FheError(-1, "hoisted rotations: no rotation was asked for")
         return HoistedRotations([self.gk[e] for e in exps])
 
+    def bsgs(self, baby_steps, giant_steps):
+        """The baby-step/giant-step form of a matrix-vector product over B = baby_steps x G = giant_steps diagonals: a
+        `BsgsRotations` holding the column rotations 1 .. B - 1 (the babies) and g * B for g = 1 .. G - 1 (the giants),
+        B + G - 2 keys where `hoisted` needs G * B - 1.  A missing key raises what hoisted() raises."""
+        B, G = int(baby_steps), int(giant_steps)
+        if B < 2 or G < 2:
+            raise FheError(-1, "bsgs: at least two baby steps and two giant steps (else use hoisted())")
+        keys = []
+        for steps in (range(1, B), [g * B for g in range(1, G)]):
+            row = []
+            for i in steps:
+                if not (1 <= i < self.degree // 2):
+                    raise FheError(-1, "InvalidRotationStep")
+                e = pow(3, i, 2 * self.degree)
+                if e not in self.gk:
+                    raise FheError(-11, "EvaluationKeyError::Unsupported(ColumnRotation)")
+                row.append(self.gk[e])
+            keys.append(row)
+        return BsgsRotations(keys[0], keys[1])
+
 
 class HoistedRotations:
     """`EvaluationKey.hoisted(...)`: several rotations of each ciphertext on one digit decomposition (KeySet.
@@ -1173,6 +1193,33 @@ class HoistedRotations:
         """The diagonal form of a plaintext matrix times an encrypted vector in one call (KeySet.matvec_hoisted):
         pt0 * ct + sum_r pts[r] * rotation_r(ct) -> [batch, 2, L, N] (or [2, L, N]); no rotated ciphertext is stored."""
         return self.set.matvec_hoisted(self.exponents, ct, pts, pt0)
+
+
+class BsgsRotations:
+    """`EvaluationKey.bsgs(B, G)`: the baby-step/giant-step hoisted matrix-vector product (KeySet.matvec_bsgs) over the
+    column rotations 1 .. B - 1 (`baby`, a KeySet, with `baby_exponents`) and B, 2B .. (G - 1)B (`giant`,
+    `giant_exponents`).  matvec(ct, pts) computes
+        sum_g rot_{gB}( sum_b pts[g][b] * rot_b(ct) ),     pts [G, B, L, N] (or [batch, G, B, L, N]) poly_ntt rows,
+    so a caller who wants sum_r d_r * rot_r(ct) over the diagonals d_r, r = g B + b, OWES THE PRE-ROTATION
+        pts[g][b] = encode( rot_{-gB}(d_{gB+b}) ):
+    the slots of diagonal g B + b turned by g B column steps AGAINST the direction of rotates_columns_by (in both rows
+    of the slot matrix) before they are encoded.  Row g = 0 and column b = 0 take no rotation.  Not the reference's
+    words (include/fhe_hip.h); it decrypts to what the flat product on the diagonals d_r decrypts to."""
+
+    def __init__(self, baby_keys, giant_keys):
+        self.baby_keys, self.giant_keys = list(baby_keys), list(giant_keys)
+        self.baby_exponents = [g.exponent for g in self.baby_keys]
+        self.giant_exponents = [g.exponent for g in self.giant_keys]
+        self.baby = KeySet([g.ksk for g in self.baby_keys])
+        self.giant = KeySet([g.ksk for g in self.giant_keys])
+
+    @property
+    def shape(self):
+        """(G, B): the grid of diagonals matvec expects."""
+        return len(self.giant_exponents) + 1, len(self.baby_exponents) + 1
+
+    def matvec(self, ct, pts):
+        return self.baby.matvec_bsgs(self.baby_exponents, self.giant, self.giant_exponents, ct, pts)
 
 
 class KeySet:
@@ -1215,6 +1262,17 @@ class KeySet:
     def rot_split(self):
         g = C.c_size_t()
         check(_lib.lib().fhe_kskset_get_rot_split(self._h, C.byref(g)))
+        return g.value
+
+    def set_bsgs_tile(self, gt=0):
+        """Giant groups per block of matvec_bsgs's baby stage, read from the BABY set (fhe_kskset_set_bsgs_tile; 0 = the
+        engine's rule, 1 / 2 / 4 force an instance)."""
+        check(_lib.lib().fhe_kskset_set_bsgs_tile(self._h, int(gt)))
+        return self
+
+    def bsgs_tile(self):
+        g = C.c_size_t()
+        check(_lib.lib().fhe_kskset_get_bsgs_tile(self._h, C.byref(g)))
         return g.value
 
     def w_budget(self):
@@ -1312,6 +1370,36 @@ class KeySet:
         out = DeviceArray(tuple(ct.shape), dev) if host else _empty_dev(d, tuple(ct.shape))
         check(L.fhe_bfv_matvec_hoisted_dev(self._h, arr, len(exps), _dptr(d), _dptr(p), 1 if shared else 0,
                                            None if p0 is None else _dptr(p0), _dptr(out), b, _stream()))
+        return out.download() if host else out
+
+    def matvec_bsgs(self, baby_exps, giant_set, giant_exps, ct, pts):
+        """Baby-step/giant-step hoisted matrix-vector product (fhe_bfv_matvec_bsgs_dev): this set holds ONE client's baby
+        Galois keys (key r for baby_exps[r]), `giant_set` the giant keys.  ct [batch, 2, L, N] Ntt (or [2, L, N]); pts
+        `Plaintext::poly_ntt` rows, [G, B, L, N] shared by the batch or [batch, G, B, L, N], G = len(giant_exps) + 1,
+        B = len(baby_exps) + 1; column 0 of a group is its identity diagonal, row 0 the group without a giant rotation
+        -> sum_g rot_giant_g( sum_b pts[g][b] * rot_baby_b(ct) ), [batch, 2, L, N] (or [2, L, N]), of ct's kind.
+        Word for word G matvec_hoisted calls, one-key relinearize_hoisted calls and additions; like them not the
+        reference's words (include/fhe_hip.h)."""
+        L = _lib.lib()
+        ctx = self.ctx_ciphertext
+        if ct.shape[-3] != 2:
+            raise FheError(-13, "InvalidPolynomialCount: rotation expects 2 parts")
+        bex, gex = [int(e) for e in baby_exps], [int(e) for e in giant_exps]
+        ba, ga = (C.c_size_t * max(len(bex), 1))(*bex), (C.c_size_t * max(len(gex), 1))(*gex)
+        lead = tuple(ct.shape[:-3])
+        b = ctx._batch(ct) // 2
+        shared = len(pts.shape) == 4
+        grid = (len(gex) + 1, len(bex) + 1)
+        want = (grid if shared else lead + grid) + (ctx.nmoduli, ctx.degree)
+        if tuple(pts.shape) != want:
+            raise FheError(-1, "DotProductLengthMismatch: diagonals %s, expected %s" % (tuple(pts.shape), want))
+        host = not _is_dev(ct)
+        dev = max(self.ctx_ksk.device, 0)
+        stage = (lambda a: DeviceArray.from_numpy(_np(a), dev)) if host else (lambda a: a)
+        d, p = stage(ct), stage(pts)
+        out = DeviceArray(tuple(ct.shape), dev) if host else _empty_dev(d, tuple(ct.shape))
+        check(L.fhe_bfv_matvec_bsgs_dev(self._h, ba, len(bex), giant_set._h, ga, len(gex), _dptr(d), _dptr(p),
+                                        1 if shared else 0, _dptr(out), b, _stream()))
         return out.download() if host else out
 
 

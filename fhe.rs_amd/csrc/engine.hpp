@@ -1476,6 +1476,7 @@ struct KskSet {
     size_t ndigits = 0;
     std::atomic<size_t> w_budget{0};   // as Ksk::w_budget; 0 = default
     std::atomic<size_t> rot_split{0};  // rotation groups of a hoisted matvec launch (hoist_rot_group); 0 = the rule
+    std::atomic<size_t> bsgs_tile{0};  // giant groups per block of bsgs_baby_kernel (bsgs_group_tile); 0 = the rule, 1 / 2 / 4
 };
 // The trailing optional argument of key_switch_polys / key_switch_add / galois_apply (one), inner_sum (one per rotation)
 // and expand (one per level): polynomial b of the call takes key (b / per_key) % nkeys of `set`.
@@ -2187,6 +2188,11 @@ inline void galois_apply(const Ksk &ks, size_t exponent, const u64 *ct, u64 *out
 // exponents reduced mod 2N.  hoist_each_w: one inverse transform of c1 (no substitution), then key_switch_polys_keyed's
 // geometry unchanged -- tile choice, `narrow`, `rns`, the W budget rule with equal chunks of ciphertexts and equal groups
 // of key moduli -- and ONE stage A per (chunk, group); stage_b(b0, nb, j0, njg, w) then runs on that W.
+// `granule` (matvec_bsgs's giant pass): every ciphertext of the batch stands for `granule` items, `ct` holding the batch x
+// granule 2-part polynomial pairs ciphertext-major, and a chunk holds WHOLE ciphertexts -- W is [nb x granule][nd][jg][N],
+// b0 and nb still count ciphertexts.  The budget rule is the same with a ciphertext costing `granule`
+// rows per digit and key modulus; where the budget is below one ciphertext's items at one key modulus the chunk is one
+// ciphertext (pc = max(1, ...)).  granule = 1: the ciphertexts themselves, what galois_hoisted and matvec_hoisted launch.
 inline std::vector<uint32_t> hoist_exponents(const KskSet &set, const size_t *exponents, size_t nrot, const std::string &what) {
     const Ctx &kc = *set.ksk_ctx, &cc = *set.ct_ctx;
     require(exponents != nullptr, E_ARG, "null argument: exponents");
@@ -2202,26 +2208,26 @@ inline std::vector<uint32_t> hoist_exponents(const KskSet &set, const size_t *ex
     return exps;
 }
 template <class StageB>
-inline void hoist_each_w(const KskSet &set, const u64 *ct, size_t batch, hipStream_t s, StageB &&stage_b) {
+inline void hoist_each_w(const KskSet &set, const u64 *ct, size_t batch, hipStream_t s, StageB &&stage_b, size_t granule = 1) {
     const Ksk &k_ = *set.keys[0];
     const Ctx &kc = *set.ksk_ctx, &cc = *set.ct_ctx;
     const size_t N = kc.n, nd = set.ndigits, Lk = kc.L;
     const u64 PL = (u64)cc.L * N;
     kc.need_device();
     const uint32_t logn = (uint32_t)kc.logn;
-    WsGuard c2(batch * PL * sizeof(u64), s);
+    WsGuard c2(batch * granule * PL * sizeof(u64), s);
     k::RowMap m = full_map(cc, cc.L);
     m.src_poly_stride = 2 * PL;
     m.dst_poly_stride = PL;
-    launch_ntt(cc, true, ct + PL, c2.u(), m, batch, s);
-    const bool sub14 = logn == 14 && 2 * batch * nd * Lk <= (size_t)device_cus(kc.device);
+    launch_ntt(cc, true, ct + PL, c2.u(), m, batch * granule, s);
+    const bool sub14 = logn == 14 && 2 * batch * granule * nd * Lk <= (size_t)device_cus(kc.device);
     const uint32_t logm = logn > 14 ? 13 : sub14 ? 13 : logn;
     const uint32_t g0 = logn - logm;
     const bool narrow = !FHE_LAB_FLAG("NO_NARROW") && kc.below_2p60(0, kc.L);
     const bool rns = k_.digit_arg() == (1u << 8);
     size_t budget = set.w_budget.load(std::memory_order_relaxed);
     if (!budget) budget = KS_W_BUDGET_DEFAULT;
-    const size_t row_bytes = N * sizeof(u64);
+    const size_t row_bytes = granule * N * sizeof(u64);
     size_t pc = batch, jg = Lk;
     if (pc * nd * jg * row_bytes > budget) {
         jg = std::max<size_t>(1, budget / (pc * nd * row_bytes));
@@ -2235,8 +2241,8 @@ inline void hoist_each_w(const KskSet &set, const u64 *ct, size_t batch, hipStre
         const size_t nb = std::min(pc, batch - b0);
         for (size_t j0 = 0; j0 < Lk; j0 += jg) {
             const size_t njg = std::min(jg, Lk - j0);
-            const unsigned grid_a = (unsigned)((nb * nd * njg) << g0);
-            const u64 *pp = c2.u() + b0 * PL;
+            const unsigned grid_a = (unsigned)((nb * granule * nd * njg) << g0);
+            const u64 *pp = c2.u() + b0 * granule * PL;
             auto stage_a = [&](auto lm, auto g) {
                 launch_ks_ntt<decltype(lm)::value, decltype(g)::value>(k_, narrow, rns, grid_a, s, pp, PL, w.u(), (uint32_t)j0,
                                                                        (uint32_t)njg, 1u, nullptr);
@@ -2307,6 +2313,18 @@ inline size_t hoist_rot_group(const Ctx &kc, size_t forced, size_t nb, size_t nj
     groups = std::min(groups, nr);
     return (nr + groups - 1) / groups;
 }
+// The giant groups one block of bsgs_baby_kernel<GT> serves (the ONE statement of this rule, hoist_rot_group's twin): a
+// larger tile reads every baby key and every row of W once for GT inner sums, and leaves 1 / GT of the blocks.  So: the
+// largest instance, no wider than the G groups, whose launch still has two blocks per compute unit; else 1.  A shape
+// rule like sub14, no fit to timings.  forced (fhe_kskset_set_bsgs_tile on the BABY set): 1, 2 or 4.
+inline size_t bsgs_group_tile(const Ctx &kc, size_t forced, size_t nb, size_t njg, size_t G) {
+    if (forced) return forced;
+    const size_t cpr = kc.n >= 512 ? kc.n / 512 : 1;
+    const size_t want = 2 * (size_t)device_cus(kc.device);
+    for (size_t gt : {(size_t)4, (size_t)2})
+        if (gt <= G && nb * njg * cpr * ((G + gt - 1) / gt) >= want) return gt;
+    return 1;
+}
 
 // Hoisted matrix-vector product (hoist_matvec_kernel; a restatement like galois_hoisted, whose caveat it inherits): the
 // diagonal form of a plaintext matrix times an encrypted vector, out = pt0 ct + sum_r pts_r rot_r(ct), in ONE call whose
@@ -2373,6 +2391,83 @@ inline void matvec_hoisted(const KskSet &set, const size_t *exponents, size_t nr
         }
     });
     if (nparts > 1) mbfv_sum(cc, partial->u(), nparts, part_words, batch * 2, nullptr, 0, out, s);
+}
+
+// Baby-step/giant-step hoisted matrix-vector product (kernels_bsgs.hpp; a restatement like its two parents, whose
+// caveat it inherits).  G = ngiant + 1 groups of B = nbaby + 1 diagonals, pts [G][B][L][N] (pts_shared) or
+// [batch][G][B][L][N]; column 0 of a group is its identity diagonal, row 0 the group without a giant rotation:
+//   inner_g = matvec_hoisted(baby, baby_exps, ct, pts[g][1..B), pt0 = pts[g][0])                       g = 0 .. ngiant
+//   out     = inner_0 + sum_{g = 1 .. ngiant} galois_hoisted({giant key g - 1}, {giant_exps[g - 1]}, inner_g)
+// word for word.  (1) hoist_each_w over `ct` under the baby set's budget: one bsgs_baby_kernel launch per W writes the G
+// inner sums into workspace, ciphertext-major: inner_0 into `first` [batch][2][L][N] and inner_1.. into `inner`
+// [batch][ngiant][2][L][N] -- apart, so that the items of the giant pass are ONE uniform array and its inverse transform
+// one launch ([batch][G] would leave a hole per ciphertext: a launch per ciphertext, measured at 3.8 of 5.5 ms for batch
+// 256 at N = 8192).  The tile of groups per block is bsgs_group_tile's.  (2) a second hoist_each_w pass over the ngiant x
+// batch items of `inner` under the giant set's budget and geometry, with the ciphertext as the item granule, and one
+// bsgs_giant_kernel launch per W; the giants are cut into groups by
+// hoist_rot_group (the giant set's rot_split forces it).  A call that is one group writes `out` directly, otherwise the
+// groups write partial sums into wiped workspace and ONE mbfv_sum_kernel launch adds them, as matvec_hoisted does.
+// A key table holds k::HOIST_ROTS rotations: at most 65 x 65 diagonals per call.
+inline void matvec_bsgs(const KskSet &baby, const size_t *baby_exps, size_t nbaby, const KskSet &giant,
+                        const size_t *giant_exps, size_t ngiant, const u64 *ct, const u64 *pts, bool pts_shared, u64 *out,
+                        size_t batch, hipStream_t s) {
+    const Ctx &kc = *baby.ksk_ctx, &cc = *baby.ct_ctx;
+    require(baby.ct_ctx->same_ring(*giant.ct_ctx) && baby.ksk_ctx->same_ring(*giant.ksk_ctx) && baby.ndigits == giant.ndigits &&
+                baby.ksk_ctx->device == giant.ksk_ctx->device && baby.ksk_ctx->same_tables(*giant.ksk_ctx, kc.L),
+            E_PARAMETER_MISMATCH, "bsgs matvec: the baby and giant sets differ in parameters, levels, device or digit count");
+    const std::vector<uint32_t> bexps = hoist_exponents(baby, baby_exps, nbaby, "bsgs matvec (baby set)");
+    const std::vector<uint32_t> gexps = hoist_exponents(giant, giant_exps, ngiant, "bsgs matvec (giant set)");
+    require(nbaby <= k::HOIST_ROTS && ngiant <= k::HOIST_ROTS, E_ARG,
+            "bsgs matvec: at most 64 baby and 64 giant rotations per call (65 x 65 diagonals); split the giants over calls");
+    if (!batch) return;
+    const size_t G = ngiant + 1, B = nbaby + 1;
+    const u64 PL = (u64)cc.L * kc.n;
+    auto overlaps = [&](const u64 *p, u64 words) { return out < p + words && p < out + batch * 2 * PL; };
+    require(!overlaps(ct, batch * 2 * PL), E_ARG, "bsgs matvec: `out` overlaps `ct`");
+    require(!overlaps(pts, (pts_shared ? 1 : batch) * G * B * PL), E_ARG, "bsgs matvec: `out` overlaps `pts`");
+    require((((uintptr_t)ct | (uintptr_t)pts | (uintptr_t)out) & 15) == 0, E_ARG, "bsgs matvec: buffers must be 16-byte aligned");
+    const size_t tile_forced = baby.bsgs_tile.load(std::memory_order_relaxed);
+    const size_t split_forced = giant.rot_split.load(std::memory_order_relaxed);
+    k::HoistExps be{}, ge{};
+    for (size_t r = 0; r < nbaby; r++) be.e[r] = bexps[r];
+    for (size_t r = 0; r < ngiant; r++) ge.e[r] = gexps[r];
+    WsGuard first(batch * 2 * PL * sizeof(u64), s), inner(batch * ngiant * 2 * PL * sizeof(u64), s);
+    const u64 IS = (u64)ngiant * 2 * PL;   // words of one ciphertext's inner sums 1 .. ngiant
+    hoist_each_w(baby, ct, batch, s, [&](size_t b0, size_t nb, size_t j0, size_t njg, const u64 *w) {
+        const size_t gt = bsgs_group_tile(kc, tile_forced, nb, njg, G);
+        const size_t ntiles = (G + gt - 1) / gt;
+        const size_t grid_b = hoist_grid_b(kc, njg, nb, ntiles);
+        u64 *o = inner.u() + b0 * IS, *f = first.u() + b0 * 2 * PL;
+        const u64 *c = ct + b0 * 2 * PL;
+        auto launch = [&](auto t) {
+            FHE_LAUNCH("bsgs_baby", k::bsgs_baby_kernel<decltype(t)::value>, dim3((unsigned)grid_b), dim3(256), 0, s, w, f, f + PL,
+                       2 * PL, o, o + PL, IS, 2 * PL, c, c + PL, 2 * PL, baby.table.p, be, pts + (pts_shared ? 0 : b0 * G * B * PL),
+                       pts_shared ? (u64)0 : (u64)G * B * PL, (u64)B * PL, PL, kc.dmods(), (uint32_t)baby.ndigits, (uint32_t)kc.L,
+                       (uint32_t)j0, (uint32_t)njg, (uint32_t)kc.logn, (uint32_t)nb, (uint32_t)nbaby, (uint32_t)G,
+                       (uint32_t)ntiles);
+        };
+        if (gt == 4) launch(int_c<4>{});
+        else if (gt == 2) launch(int_c<2>{});
+        else launch(int_c<1>{});
+    });
+    // The giant groups are planned once, on the first W -- the largest -- and serve every W: ONE number of partial sums.
+    size_t gpg = 0, ngroups = 0;
+    std::unique_ptr<WsGuard> partial;
+    const u64 part_words = (u64)batch * 2 * PL;
+    hoist_each_w(giant, inner.u(), batch, s, [&](size_t b0, size_t nb, size_t j0, size_t njg, const u64 *w) {
+        if (!gpg) {
+            gpg = hoist_rot_group(kc, split_forced, nb, njg, ngiant);
+            ngroups = (ngiant + gpg - 1) / gpg;
+            if (ngroups > 1) partial = std::make_unique<WsGuard>(ngroups * part_words * sizeof(u64), s, true);
+        }
+        const size_t grid_b = hoist_grid_b(kc, njg, nb, ngroups);
+        u64 *o = (ngroups > 1 ? partial->u() : out) + b0 * 2 * PL;
+        const u64 *in = inner.u() + b0 * IS, *f = first.u() + b0 * 2 * PL;
+        FHE_LAUNCH("bsgs_giant", k::bsgs_giant_kernel, dim3((unsigned)grid_b), dim3(256), 0, s, w, o, o + PL, 2 * PL, part_words,
+                   f, f + PL, 2 * PL, in, in + PL, IS, 2 * PL, giant.table.p, ge, kc.dmods(), (uint32_t)giant.ndigits, (uint32_t)kc.L, (uint32_t)j0,
+                   (uint32_t)njg, (uint32_t)kc.logn, (uint32_t)nb, (uint32_t)ngiant, (uint32_t)gpg, (uint32_t)ngroups);
+    }, ngiant);
+    if (ngroups > 1) mbfv_sum(cc, partial->u(), ngroups, part_words, batch * 2, nullptr, 0, out, s);
 }
 
 // `&Ciphertext * &RGSWCiphertext` (F/bfv/rgsw_ciphertext.rs:122-156)

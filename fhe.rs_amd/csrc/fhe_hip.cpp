@@ -1366,6 +1366,21 @@ fhe_status fhe_kskset_get_rot_split(const fhe_kskset *s, size_t *groups) {
         *groups = s->s->rot_split.load(std::memory_order_relaxed);
     });
 }
+fhe_status fhe_kskset_set_bsgs_tile(fhe_kskset *s, size_t gt) {
+    return guard([&] {
+        need(s, "set");
+        if (gt != 0 && gt != 1 && gt != 2 && gt != 4)
+            throw StatusError(FHE_E_ARG, "bsgs tile: 0 (the rule), 1, 2 or 4 giant groups per block, not " + std::to_string(gt));
+        s->s->bsgs_tile.store(gt, std::memory_order_relaxed);
+    });
+}
+fhe_status fhe_kskset_get_bsgs_tile(const fhe_kskset *s, size_t *gt) {
+    return guard([&] {
+        need(s, "set");
+        need(gt, "gt");
+        *gt = s->s->bsgs_tile.load(std::memory_order_relaxed);
+    });
+}
 // The checks every keyed call shares; returns items per key (0: nothing to do).
 static size_t keyed_per_key(const KskSet &set, size_t batch) {
     set.ksk_ctx->need_device();
@@ -1498,6 +1513,33 @@ fhe_status fhe_bfv_matvec_hoisted_dev(const fhe_kskset *gks, const size_t *expon
             need(out, "out");
         }
         matvec_hoisted(set, exponents, nrot, ct, pts, pts_shared != 0, pt0, out, batch, as_stream(stream));
+    });
+}
+// Baby-step/giant-step hoisted matrix-vector product (engine.hpp: matvec_bsgs).
+fhe_status fhe_bfv_matvec_bsgs_dev(const fhe_kskset *baby, const size_t *baby_exps, size_t nbaby, const fhe_kskset *giant,
+                                   const size_t *giant_exps, size_t ngiant, const uint64_t *ct, const uint64_t *pts,
+                                   int pts_shared, uint64_t *out, size_t batch, void *stream) {
+    return guard([&] {
+        need(baby, "baby");
+        need(baby_exps, "baby_exps");
+        need(giant, "giant");
+        need(giant_exps, "giant_exps");
+        const KskSet &bs = *baby->s, &gs = *giant->s;
+        auto count = [](const char *which, size_t n, const KskSet &set) {
+            if (n != set.keys.size())
+                throw StatusError(FHE_E_ARG, std::string("bsgs matvec: ") + std::to_string(n) + " " + which +
+                                                 " exponents for a set of " + std::to_string(set.keys.size()) + " keys");
+        };
+        count("baby", nbaby, bs);
+        count("giant", ngiant, gs);
+        bs.ksk_ctx->need_device();
+        set_device(*bs.ksk_ctx);
+        if (batch) {
+            need(ct, "ct");
+            need(pts, "pts");
+            need(out, "out");
+        }
+        matvec_bsgs(bs, baby_exps, nbaby, gs, giant_exps, ngiant, ct, pts, pts_shared != 0, out, batch, as_stream(stream));
     });
 }
 

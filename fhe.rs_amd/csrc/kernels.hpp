@@ -18,6 +18,8 @@
 //                           rotations; a restatement, not the reference's words: kernels_kshoist.hpp)
 //   hoist_matvec_kernel     the same with each rotation multiplied by its plaintext diagonal and the products summed in
 //                           registers (a plaintext matrix times an encrypted vector; hoist_mac_kernel + dot_kernel's words)
+//   bsgs_baby_kernel<GT>, bsgs_giant_kernel   the baby-step/giant-step form of that product: G inner sums from one digit
+//                           loop per baby rotation, then the giants' key switches summed in registers (kernels_bsgs.hpp)
 //   scale_kernel            RnsScaler::scale per column             M/rns/scaler.rs:249-352, M/rq/scaler.rs:85-94
 //   switch_down_kernel      Poly::switch_down                       M/rq/mod.rs:433-492
 //   substitute_kernel       Poly::substitute                        M/rq/mod.rs:360-412
@@ -52,6 +54,7 @@
 #include "kernels_ks.hpp"
 #include "kernels_kskeyed.hpp"
 #include "kernels_kshoist.hpp"
+#include "kernels_bsgs.hpp"
 #include "kernels_scaler.hpp"
 #include "kernels_misc.hpp"
 #include "kernels_encode.hpp"

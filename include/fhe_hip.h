@@ -407,6 +407,11 @@ fhe_status fhe_kskset_get_w_budget(const fhe_kskset *s, size_t *bytes);
  * the rotations of the launch.  It changes how the work is cut, never a word of the result. */
 fhe_status fhe_kskset_set_rot_split(fhe_kskset *s, size_t groups);
 fhe_status fhe_kskset_get_rot_split(const fhe_kskset *s, size_t *groups);
+/* Giant groups served by one block of the baby stage of fhe_bfv_matvec_bsgs_dev (below), read from the BABY set: 0 = the
+ * engine's rule on the shape and the device's compute units, 1, 2 or 4 = that kernel instance; anything else ->
+ * FHE_E_ARG.  It changes how the work is cut, never a word of the result. */
+fhe_status fhe_kskset_set_bsgs_tile(fhe_kskset *s, size_t gt);
+fhe_status fhe_kskset_get_bsgs_tile(const fhe_kskset *s, size_t *gt);
 /* KeySwitchingKey::key_switch (:241-320) per client: p [batch][L][N] PowerBasis -> c0_out, c1_out [batch][Lk][N] Ntt. */
 fhe_status fhe_key_switch_keyed_dev(const fhe_kskset *s, const uint64_t *p, uint64_t *c0_out, uint64_t *c1_out,
                                     size_t batch, void *stream);
@@ -473,6 +478,37 @@ fhe_status fhe_bfv_galois_hoisted_dev(const fhe_kskset *gks, const size_t *expon
 fhe_status fhe_bfv_matvec_hoisted_dev(const fhe_kskset *gks, const size_t *exponents, size_t nrot, const uint64_t *ct,
                                       const uint64_t *pts, int pts_shared, const uint64_t *pt0, uint64_t *out, size_t batch,
                                       void *stream);
+/* Baby-step/giant-step hoisted matrix-vector product (Halevi-Shoup, CRYPTO 2018, section 4.3; bsgs_baby_kernel and
+ * bsgs_giant_kernel; not in the reference): with G = ngiant + 1 groups of B = nbaby + 1 diagonals,
+ *   out = sum_g rot_giant_g( sum_b pts[g][b] * rot_baby_b(ct) ),
+ * from nbaby + ngiant Galois keys and digit loops where the flat call above needs G * B - 1.  A caller who wants
+ * sum_r d_r * rot_r(ct) with r = g B + b owes the pre-rotation pts[g][b] = rot_{-gB}(d_{gB+b}) of the plaintext diagonals.
+ * The specification is a composition of the two calls above:
+ *   inner_g = fhe_bfv_matvec_hoisted_dev(baby, baby_exps, nbaby, ct, pts[g][1..B), pts_shared, pt0 = pts[g][0])   g = 0 .. ngiant
+ *   out     = inner_0 + sum_{g=1..ngiant} fhe_bfv_galois_hoisted_dev({giant key g-1}, {giant_exps[g-1]}, 1, inner_g)
+ * with canonical sums mod q_j (tests/bsgs_ref.py); the call equals it word for word, whatever tile, split or W budget it
+ * runs under.  LIKE THOSE CALLS', THE OUTPUT IS NOT THE REFERENCE'S WORDS: the rotations inside it substitute the lifted
+ * digits of c1 where GaloisKey::relinearize lifts the digits of substitute(c1), so the result decrypts to what the flat
+ * product on the un-pre-rotated diagonals decrypts to, but differs from a loop of fhe_bfv_galois_dev word for word.
+ * baby, giant: two key sets of ONE client, key r of a set for exponent r of its list (odd, reduced mod 2N; a repeated
+ * exponent is allowed).  ct, out [batch][2][L][N] Ntt.  pts: Plaintext::poly_ntt rows over the ciphertext's context,
+ * [G][B][L][N] shared by the batch when pts_shared != 0, else [batch][G][B][L][N]; column b = 0 of every group is that
+ * group's identity diagonal (no baby key, no key switch), row g = 0 the group that takes no giant rotation.  16-byte
+ * aligned buffers.  Device-pointer form only; the call only enqueues.
+ * LIMIT: a key table holds 64 rotations, so nbaby, ngiant <= 64 -- 65 x 65 diagonals per call; a caller with more splits
+ * the giants over calls and adds the results.
+ * The baby stage computes all G inner sums from one digit loop per baby rotation, a block serving a tile of 1, 2 or 4
+ * groups (fhe_kskset_set_bsgs_tile on `baby`); the giant stage key-switches the G - 1 inner sums under their own keys
+ * and sums them in registers, the giants cut into groups by the rule of fhe_kskset_set_rot_split (read from `giant`).
+ * NULL set or exponent list, nbaby != fhe_kskset_size(baby), ngiant != fhe_kskset_size(giant), nbaby or ngiant above 64,
+ * NULL ct / pts / out with batch > 0, `out` overlapping ct or pts, a buffer not 16-byte aligned, either set's keys
+ * above the ciphertext's level -> FHE_E_ARG; an even exponent in either list -> FHE_E_INVALID_SUBSTITUTION_EXPONENT;
+ * the two sets differing in ring, levels, device or digit count -> FHE_E_PARAMETER_MISMATCH; batch == 0 is a no-op (NULL
+ * buffers allowed).  A refused call leaves `out` untouched.
+ * No automatic choice of B and G, or between this call and the flat one, is made (tools/bench_bsgs_matvec.py measures). */
+fhe_status fhe_bfv_matvec_bsgs_dev(const fhe_kskset *baby, const size_t *baby_exps, size_t nbaby, const fhe_kskset *giant,
+                                   const size_t *giant_exps, size_t ngiant, const uint64_t *ct, const uint64_t *pts,
+                                   int pts_shared, uint64_t *out, size_t batch, void *stream);
 
 /* ------------------------------------------------------------- Multiplicator ---- */
 /* Multiplicator::new_leveled_internal + enable_relinearization + enable_mod_switching

@@ -31,3 +31,18 @@ pub fn matrix_times_vector(galois_keys: &[&HipKsk], exponents: &[usize], ct: &De
     }
     set.matvec_hoisted_dev(exponents, ct, diagonals, Some(diagonal0), s)
 }
+
+/// The baby-step/giant-step form (`HipKskSet::matvec_bsgs_dev`): `baby_keys` rotate by 1 ... B - 1, `giant_keys` by B, 2B ...
+/// (G - 1)B, and `grid` holds the `[G][B][L][N]` diagonals the caller has pre-rotated (`grid[g][b] = rot_{-gB}(d_{gB+b})`),
+/// so `B + G - 2` keys serve `G * B` diagonals.  `tile`: giant groups per block of the baby stage for a host that has
+/// measured its shape (0 keeps the engine's rule; 1, 2 or 4).
+pub fn matrix_times_vector_bsgs(baby_keys: &[&HipKsk], baby_exps: &[usize], giant_keys: &[&HipKsk], giant_exps: &[usize],
+                                ct: &DeviceCiphertexts, grid: &DeviceBuffer, tile: usize, s: &Stream)
+                                -> Result<DeviceCiphertexts, HipError> {
+    let baby = HipKskSet::new(baby_keys)?;
+    let giant = HipKskSet::new(giant_keys)?;
+    if baby.bsgs_tile()? != tile {
+        baby.set_bsgs_tile(tile)?;
+    }
+    baby.matvec_bsgs_dev(baby_exps, &giant, giant_exps, ct, grid, s)
+}

@@ -672,6 +672,16 @@ impl<'k> HipKskSet<'k> {
         check(unsafe { ffi::fhe_kskset_get_rot_split(self.ptr, &mut groups) })?;
         Ok(groups)
     }
+    /// Giant groups per block of the baby stage of `matvec_bsgs_dev`, read from the BABY set (`fhe_kskset_set_bsgs_tile`;
+    /// 0 = the engine's rule, 1 / 2 / 4 force a kernel instance, anything else is refused).
+    pub fn set_bsgs_tile(&self, gt: usize) -> Result<()> {
+        check(unsafe { ffi::fhe_kskset_set_bsgs_tile(self.ptr, gt) })
+    }
+    pub fn bsgs_tile(&self) -> Result<usize> {
+        let mut gt = 0usize;
+        check(unsafe { ffi::fhe_kskset_get_bsgs_tile(self.ptr, &mut gt) })?;
+        Ok(gt)
+    }
     fn check_keyed(&self, what: &str, ct: &DeviceCiphertexts, parts: usize) -> Result<()> {
         self.first.check_resident(what, ct, parts)?;
         if ct.batch % self.len != 0 {
@@ -744,6 +754,33 @@ impl<'k> HipKskSet<'k> {
             ffi::fhe_bfv_matvec_hoisted_dev(self.ptr, exponents.as_ptr(), exponents.len(), ct.buf.as_ptr(), diagonals.as_ptr(),
                                             shared as c_int, pt0.map_or(ptr::null(), |p| p.as_ptr()), out.buf.as_mut_ptr(), ct.batch,
                                             stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+    /// Baby-step/giant-step hoisted matrix-vector product (`fhe_bfv_matvec_bsgs_dev`; not in the reference): `self` holds
+    /// the baby Galois keys (key `r` for `baby_exps[r]`), `giant` the giant keys; with `G = giant.len() + 1` groups of
+    /// `B = self.len() + 1` diagonals the result is the sum over `g` of giant rotation `g` of the sum over `b` of
+    /// `diagonals[g][b]` times baby rotation `b` of `ct` -- `B + G - 2` keys and digit loops where `matvec_hoisted_dev`
+    /// needs `G * B - 1`.  `diagonals` holds `poly_ntt` rows, `[G][B][L][N]` shared by the batch or `[batch][G][B][L][N]`;
+    /// column 0 of a group is its identity diagonal, row 0 the group without a giant rotation, and the caller owes the
+    /// pre-rotation `diagonals[g][b] = rot_{-gB}(d_{gB+b})`.  Word for word the composition of `matvec_hoisted_dev` and
+    /// one-key `galois_hoisted_dev` calls the header states, and like them NOT the reference's words.  At most 64 keys
+    /// per set (65 x 65 diagonals per call).
+    pub fn matvec_bsgs_dev(&self, baby_exps: &[usize], giant: &HipKskSet<'_>, giant_exps: &[usize], ct: &DeviceCiphertexts,
+                           diagonals: &DeviceBuffer, stream: &Stream) -> Result<DeviceCiphertexts> {
+        self.first.check_resident("matvec_bsgs_dev", ct, 2)?;
+        expect_len("matvec_bsgs_dev baby exponents", baby_exps.len(), self.len)?;
+        expect_len("matvec_bsgs_dev giant exponents", giant_exps.len(), giant.len)?;
+        let grid = (giant.len + 1) * (self.len + 1) * ct.rows * ct.degree;
+        let shared = diagonals.len() == grid;
+        if !shared {
+            expect_len("matvec_bsgs_dev diagonals", diagonals.len(), ct.batch * grid)?;
+        }
+        let out = DeviceCiphertexts::alloc_on(self.first.ct_ctx().device(), ct.batch, 2, ct.rows, ct.degree, ct.level, stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_matvec_bsgs_dev(self.ptr, baby_exps.as_ptr(), baby_exps.len(), giant.ptr, giant_exps.as_ptr(), giant_exps.len(),
+                                         ct.buf.as_ptr(), diagonals.as_ptr(), shared as c_int, out.buf.as_mut_ptr(), ct.batch,
+                                         stream.as_ptr())
         })?;
         Ok(out)
     }
