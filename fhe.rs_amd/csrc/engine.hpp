@@ -1789,66 +1789,98 @@ inline void launch_ks_ntt(const Ksk &k_, bool narrow, bool rns, unsigned grid, h
             });
     });
 }
-inline void key_switch_polys_unfused(const Ksk &k_, int mode, const u64 *p, u64 p_stride, u64 *o0, u64 *o1,
-                                     u64 out_stride, const u64 *a0, const u64 *a1, u64 a_stride, size_t npolys,
-                                     hipStream_t s, const u64 *xhat, u64 xhat_stride, uint32_t gal,
-                                     const KsExtraFwd *extra = nullptr) {
+// The geometry of an unfused call, stated once for the single-key, keyed and hoisted forms (the Python restatement of the
+// cut: chunk_rule in tests/keyed_cases.py).  `items` polynomials or ciphertexts, each `granule` rows of W per digit
+// and key modulus (hoist_each_w; 1 otherwise); k_: the key, or the first key of a set (only its key-independent
+// fields are read).
+//  * Stage A's tile: whole rows up to 16384 points, 8192-point sub-blocks above, and at 16384 on request (sub14_always)
+//    or, where the caller allows it (sub14_small), while whole-row tiles would leave half the device idle -- one
+//    ciphertext at 8 moduli: 64 rows, 0.0527 vs 0.0556 ms; four: 256 rows, 0.0684 vs 0.0668.
+//  * W = [pc][granule][nd][jg][N]: groups of jg key moduli over chunks of pc items, as large as the budget allows
+//    (0: KS_W_BUDGET_DEFAULT).  Key-modulus groups are cut first: a group's key slice is then still read once per
+//    launch pair.  Equal groups and equal chunks: no small tail launch.
+struct KsGeometry {
+    uint32_t logm, g0;   // stage A: tiles of 2^logm points, g0 stages folded into the loader
+    bool narrow, rns;
+    size_t pc, jg;       // items per chunk, key moduli per group
+    size_t w_bytes;
+};
+inline KsGeometry ks_unfused_geometry(const Ksk &k_, size_t items, size_t budget, bool sub14_small, bool sub14_always = false,
+                                      size_t granule = 1) {
     const Ctx &kc = *k_.ksk_ctx;
-    const size_t N = kc.n, nd = k_.ndigits, Lk = kc.L;
+    const size_t nd = k_.ndigits, Lk = kc.L;
     const uint32_t logn = (uint32_t)kc.logn;
-    // tile geometry of stage A: whole rows up to 16384 points, 8192-point sub-blocks above (and at 16384 on request)
-    // (KS_AUTO at N = 16384: sub-block tiles while the whole-row tiles of stage A would leave half the device idle --
-    // one ciphertext at 8 moduli: 64 rows, 0.0527 vs 0.0556 ms; four: 256 rows, 0.0684 vs 0.0668)
-    // (with extra rows to transform in the same launch -- bfv_mul's c0, c1 -- whole-row tiles: saving that launch is worth
-    // more than the smaller tiles, 21 us against 3 us at one ciphertext)
-    const bool sub14 = logn == 14 && (mode == KS_UNFUSED_SUB ||
-                                      (mode == KS_AUTO && !extra && 2 * npolys * nd * Lk <= (size_t)device_cus(kc.device)));
-    const uint32_t logm = logn > 14 ? 13 : sub14 ? 13 : logn;
-    const uint32_t g0 = logn - logm;
-    const bool narrow = !FHE_LAB_FLAG("NO_NARROW") && kc.below_2p60(0, kc.L);
-    const bool rns = k_.digit_arg() == (1u << 8);
-    // W = [pc][nd][jg][N]: groups of jg key moduli over chunks of pc polynomials, as large as the budget allows
-    // (key-modulus groups are cut first: a group's key slice is then still read once per launch pair)
-    size_t budget = k_.w_budget.load(std::memory_order_relaxed);
+    KsGeometry g;
+    const bool sub14 = logn == 14 && (sub14_always ||
+                                      (sub14_small && 2 * items * granule * nd * Lk <= (size_t)device_cus(kc.device)));
+    g.logm = logn > 14 ? 13 : sub14 ? 13 : logn;
+    g.g0 = logn - g.logm;
+    g.narrow = !FHE_LAB_FLAG("NO_NARROW") && kc.below_2p60(0, kc.L);
+    g.rns = k_.digit_arg() == (1u << 8);
     if (!budget) budget = KS_W_BUDGET_DEFAULT;
-    const size_t row_bytes = N * sizeof(u64);
-    size_t pc = npolys, jg = Lk;
+    const size_t row_bytes = granule * kc.n * sizeof(u64);
+    size_t pc = items, jg = Lk;
     if (pc * nd * jg * row_bytes > budget) {
         jg = std::max<size_t>(1, budget / (pc * nd * row_bytes));
         if (jg > Lk) jg = Lk;
         if (pc * nd * jg * row_bytes > budget) pc = std::max<size_t>(1, budget / (nd * jg * row_bytes));
     }
-    // (equal groups / chunks: no small tail launch)
-    jg = (Lk + ((Lk + jg - 1) / jg) - 1) / ((Lk + jg - 1) / jg);
-    pc = (npolys + ((npolys + pc - 1) / pc) - 1) / ((npolys + pc - 1) / pc);
-    WsGuard w(pc * nd * jg * row_bytes, s);
+    g.jg = (Lk + ((Lk + jg - 1) / jg) - 1) / ((Lk + jg - 1) / jg);
+    g.pc = (items + ((items + pc - 1) / pc) - 1) / ((items + pc - 1) / pc);
+    g.w_bytes = g.pc * nd * g.jg * row_bytes;
+    return g;
+}
+// Stage A of one (chunk, group): `rows` polynomials (items x granule) from p, key moduli [j0, j0 + njg), into w.
+inline void launch_ks_stage_a(const Ksk &k_, const KsGeometry &g, size_t rows, size_t j0, size_t njg, hipStream_t s, const u64 *p,
+                              u64 p_stride, u64 *w, uint32_t skip_own, const KsExtraFwd *ride = nullptr) {
+    const unsigned grid_a = (unsigned)((rows * k_.ndigits * njg) << g.g0);
+    auto stage_a = [&](auto lm, auto g0, const KsExtraFwd *ex) {
+        launch_ks_ntt<decltype(lm)::value, decltype(g0)::value>(k_, g.narrow, g.rns, grid_a, s, p, p_stride, w, (uint32_t)j0,
+                                                                (uint32_t)njg, skip_own, ex);
+    };
+    if (g.g0 == 0)
+        with_logn<3, 14>(g.logm, "unsupported key-switch row size", [&](auto lm) { stage_a(lm, int_c<0>{}, ride); });
+    else if (g.g0 == 1) stage_a(int_c<13>{}, int_c<1>{}, nullptr);
+    else if (g.g0 == 2) stage_a(int_c<13>{}, int_c<2>{}, nullptr);
+    else stage_a(int_c<13>{}, int_c<3>{}, nullptr);
+}
+// Blocks of a stage B (kernels_ksmac.hpp: KsMacAt) over njg key moduli x nb polynomials or ciphertexts x `m` of whatever
+// else the kernel's grid runs over: key ranges in eights.
+inline unsigned ks_grid_b(const Ctx &kc, size_t njg, size_t nb, size_t m = 1, const char *what = "unfused key switch") {
+    const size_t grid_b = (((njg * k::ks_mac_chunks_per_row(kc.n)) + 7) / 8) * nb * m * 8;
+    if (grid_b > 0x7fffffffu)   // (as an `unsigned` it would wrap)
+        throw StatusError(E_ARG, std::string(what) + ": the launch exceeds the grid limit; lower the W budget");
+    return (unsigned)grid_b;
+}
+inline unsigned hoist_grid_b(const Ctx &kc, size_t njg, size_t nb, size_t m) { return ks_grid_b(kc, njg, nb, m, "hoisted rotations"); }
+inline void key_switch_polys_unfused(const Ksk &k_, int mode, const u64 *p, u64 p_stride, u64 *o0, u64 *o1,
+                                     u64 out_stride, const u64 *a0, const u64 *a1, u64 a_stride, size_t npolys,
+                                     hipStream_t s, const u64 *xhat, u64 xhat_stride, uint32_t gal,
+                                     const KsExtraFwd *extra = nullptr) {
+    const Ctx &kc = *k_.ksk_ctx;
+    const size_t nd = k_.ndigits, Lk = kc.L;
+    const uint32_t logn = (uint32_t)kc.logn;
+    // (with extra rows to transform in the same launch -- bfv_mul's c0, c1 -- whole-row tiles: saving that launch is worth
+    // more than the smaller tiles, 21 us against 3 us at one ciphertext)
+    const KsGeometry g = ks_unfused_geometry(k_, npolys, k_.w_budget.load(std::memory_order_relaxed), mode == KS_AUTO && !extra,
+                                             mode == KS_UNFUSED_SUB);
+    WsGuard w(g.w_bytes, s);
     const uint32_t skip_own = xhat != nullptr ? 1u : 0u;
     // the extra rows ride on the stage-A launch only when there is exactly one (whole-row tiles, one chunk of polynomials,
     // one group of key moduli); otherwise they get their own forward transform first, as before
-    const bool merge_extra = extra != nullptr && g0 == 0 && logm == logn && pc == npolys && jg == Lk;
+    const bool merge_extra = extra != nullptr && g.g0 == 0 && g.logm == logn && g.pc == npolys && g.jg == Lk;
     if (extra != nullptr && !merge_extra) {
         k::RowMap m = full_map(kc, extra->nrows);
         m.src_poly_stride = m.dst_poly_stride = extra->poly_stride;
         launch_ntt(kc, false, extra->rows, extra->rows, m, extra->npolys, s);
     }
     const KsExtraFwd *ride = merge_extra ? extra : nullptr;
-    for (size_t b0 = 0; b0 < npolys; b0 += pc) {
-        const size_t nb = std::min(pc, npolys - b0);
-        for (size_t j0 = 0; j0 < Lk; j0 += jg) {
-            const size_t njg = std::min(jg, Lk - j0);
-            const unsigned grid_a = (unsigned)((nb * nd * njg) << g0);
-            const u64 *pp = p + b0 * p_stride;
-            auto stage_a = [&](auto lm, auto g, const KsExtraFwd *ex) {
-                launch_ks_ntt<decltype(lm)::value, decltype(g)::value>(k_, narrow, rns, grid_a, s, pp, p_stride, w.u(), (uint32_t)j0,
-                                                                       (uint32_t)njg, skip_own, ex);
-            };
-            if (g0 == 0)
-                with_logn<3, 14>(logm, "unsupported key-switch row size", [&](auto lm) { stage_a(lm, int_c<0>{}, ride); });
-            else if (g0 == 1) stage_a(int_c<13>{}, int_c<1>{}, nullptr);
-            else if (g0 == 2) stage_a(int_c<13>{}, int_c<2>{}, nullptr);
-            else stage_a(int_c<13>{}, int_c<3>{}, nullptr);
-            const uint32_t cpr = N >= 512 ? (uint32_t)(N / 512) : 1u;
-            const unsigned grid_b = (unsigned)((((njg * cpr) + 7) / 8) * nb * 8);
+    for (size_t b0 = 0; b0 < npolys; b0 += g.pc) {
+        const size_t nb = std::min(g.pc, npolys - b0);
+        for (size_t j0 = 0; j0 < Lk; j0 += g.jg) {
+            const size_t njg = std::min(g.jg, Lk - j0);
+            launch_ks_stage_a(k_, g, nb, j0, njg, s, p + b0 * p_stride, p_stride, w.u(), skip_own, ride);
+            const unsigned grid_b = ks_grid_b(kc, njg, nb);
             FHE_LAUNCH("ks_mac", k::ks_mac_kernel, dim3(grid_b), dim3(256), 0, s, w.u(), o0 + b0 * out_stride,
                        o1 + b0 * out_stride, out_stride, a0 ? a0 + b0 * a_stride : nullptr, a1 ? a1 + b0 * a_stride : nullptr,
                        a_stride, k_.c0.p, k_.c1.p, kc.dmods(), (uint32_t)nd, (uint32_t)Lk, (uint32_t)j0, (uint32_t)njg, logn,
@@ -1857,11 +1889,10 @@ inline void key_switch_polys_unfused(const Ksk &k_, int mode, const u64 *p, u64 
     }
 }
 
-// The keyed form (KskSet, kernels_kskeyed.hpp): key_switch_polys_unfused with ks_mac_keyed_kernel as its stage B.  The
-// geometry is that function's, unchanged -- tile choice (no extra rows here), `narrow`, `rns`, the W budget rule with equal
-// chunks and equal key-modulus groups -- and stage A is launch_ks_ntt, which reads only the key-independent fields of the
-// first key.  Each stage-B launch is told the index of its first polynomial within the call, so a chunk of polynomials
-// need not end on a key boundary.
+// The keyed form (KskSet, kernels_kskeyed.hpp): key_switch_polys_unfused with ks_mac_keyed_kernel as its stage B, on the
+// same geometry (no extra rows here) and the same stage A, which reads only the key-independent fields of the first
+// key.  Each stage-B launch is told the index of its first polynomial within the call, so a chunk of polynomials need
+// not end on a key boundary.
 inline void key_switch_polys_keyed(const KskSet &set, size_t per_key, const u64 *p, u64 p_stride, u64 *o0, u64 *o1,
                                    u64 out_stride, const u64 *a0, const u64 *a1, u64 a_stride, size_t npolys,
                                    hipStream_t s, const u64 *xhat, u64 xhat_stride, uint32_t gal) {
@@ -1870,48 +1901,21 @@ inline void key_switch_polys_keyed(const KskSet &set, size_t per_key, const u64 
     kc.need_device();
     require(per_key > 0, E_ARG, "keyed batches: at least one polynomial per key");
     if (!npolys) return;
-    const size_t N = kc.n, nd = set.ndigits, Lk = kc.L, nkeys = set.keys.size();
-    const uint32_t logn = (uint32_t)kc.logn;
-    const bool sub14 = logn == 14 && 2 * npolys * nd * Lk <= (size_t)device_cus(kc.device);
-    const uint32_t logm = logn > 14 ? 13 : sub14 ? 13 : logn;
-    const uint32_t g0 = logn - logm;
-    const bool narrow = !FHE_LAB_FLAG("NO_NARROW") && kc.below_2p60(0, kc.L);
-    const bool rns = k_.digit_arg() == (1u << 8);
-    size_t budget = set.w_budget.load(std::memory_order_relaxed);
-    if (!budget) budget = KS_W_BUDGET_DEFAULT;
-    const size_t row_bytes = N * sizeof(u64);
-    size_t pc = npolys, jg = Lk;
-    if (pc * nd * jg * row_bytes > budget) {
-        jg = std::max<size_t>(1, budget / (pc * nd * row_bytes));
-        if (jg > Lk) jg = Lk;
-        if (pc * nd * jg * row_bytes > budget) pc = std::max<size_t>(1, budget / (nd * jg * row_bytes));
-    }
-    jg = (Lk + ((Lk + jg - 1) / jg) - 1) / ((Lk + jg - 1) / jg);
-    pc = (npolys + ((npolys + pc - 1) / pc) - 1) / ((npolys + pc - 1) / pc);
-    WsGuard w(pc * nd * jg * row_bytes, s);
+    const size_t nd = set.ndigits, Lk = kc.L, nkeys = set.keys.size();
+    const KsGeometry g = ks_unfused_geometry(k_, npolys, set.w_budget.load(std::memory_order_relaxed), true);
+    WsGuard w(g.w_bytes, s);
     const uint32_t skip_own = xhat != nullptr ? 1u : 0u;
-    for (size_t b0 = 0; b0 < npolys; b0 += pc) {
-        const size_t nb = std::min(pc, npolys - b0);
-        for (size_t j0 = 0; j0 < Lk; j0 += jg) {
-            const size_t njg = std::min(jg, Lk - j0);
-            const unsigned grid_a = (unsigned)((nb * nd * njg) << g0);
-            const u64 *pp = p + b0 * p_stride;
-            auto stage_a = [&](auto lm, auto g) {
-                launch_ks_ntt<decltype(lm)::value, decltype(g)::value>(k_, narrow, rns, grid_a, s, pp, p_stride, w.u(), (uint32_t)j0,
-                                                                       (uint32_t)njg, skip_own, nullptr);
-            };
-            if (g0 == 0)
-                with_logn<3, 14>(logm, "unsupported key-switch row size", [&](auto lm) { stage_a(lm, int_c<0>{}); });
-            else if (g0 == 1) stage_a(int_c<13>{}, int_c<1>{});
-            else if (g0 == 2) stage_a(int_c<13>{}, int_c<2>{});
-            else stage_a(int_c<13>{}, int_c<3>{});
-            const uint32_t cpr = N >= 512 ? (uint32_t)(N / 512) : 1u;
-            const unsigned grid_b = (unsigned)((((njg * cpr) + 7) / 8) * nb * 8);
-            FHE_LAUNCH("ks_mac_keyed", k::ks_mac_keyed_kernel, dim3(grid_b), dim3(256), 0, s, w.u(), o0 + b0 * out_stride,
-                       o1 + b0 * out_stride, out_stride, a0 ? a0 + b0 * a_stride : nullptr, a1 ? a1 + b0 * a_stride : nullptr,
-                       a_stride, set.table.p, (uint32_t)nkeys, (uint32_t)per_key, (uint32_t)b0, kc.dmods(), (uint32_t)nd,
-                       (uint32_t)Lk, (uint32_t)j0, (uint32_t)njg, logn, xhat ? xhat + b0 * xhat_stride : nullptr, xhat_stride,
-                       (uint32_t)nb, gal);
+    for (size_t b0 = 0; b0 < npolys; b0 += g.pc) {
+        const size_t nb = std::min(g.pc, npolys - b0);
+        for (size_t j0 = 0; j0 < Lk; j0 += g.jg) {
+            const size_t njg = std::min(g.jg, Lk - j0);
+            launch_ks_stage_a(k_, g, nb, j0, njg, s, p + b0 * p_stride, p_stride, w.u(), skip_own);
+            const unsigned grid_b = ks_grid_b(kc, njg, nb);
+            FHE_LAUNCH("ks_mac_keyed", k::ks_mac_keyed_kernel, dim3(grid_b), dim3(256), 0, s, w.u(),
+                       o0 + b0 * out_stride, o1 + b0 * out_stride, out_stride, a0 ? a0 + b0 * a_stride : nullptr,
+                       a1 ? a1 + b0 * a_stride : nullptr, a_stride, set.table.p, (uint32_t)nkeys, (uint32_t)per_key, (uint32_t)b0,
+                       kc.dmods(), (uint32_t)nd, (uint32_t)Lk, (uint32_t)j0, (uint32_t)njg, (uint32_t)kc.logn,
+                       xhat ? xhat + b0 * xhat_stride : nullptr, xhat_stride, (uint32_t)nb, gal);
         }
     }
 }
@@ -2184,10 +2188,11 @@ inline void galois_apply(const Ksk &ks, size_t exponent, const u64 *ct, u64 *out
                    nullptr, keyed);
 }
 
-// What galois_hoisted and matvec_hoisted share.  hoist_exponents: the refusals of the exponent list and the level, the
-// exponents reduced mod 2N.  hoist_each_w: one inverse transform of c1 (no substitution), then key_switch_polys_keyed's
-// geometry unchanged -- tile choice, `narrow`, `rns`, the W budget rule with equal chunks of ciphertexts and equal groups
-// of key moduli -- and ONE stage A per (chunk, group); stage_b(b0, nb, j0, njg, w) then runs on that W.
+// What galois_hoisted, matvec_hoisted and matvec_bsgs share.  hoist_exponents: the refusals of the exponent list and the
+// level, the exponents reduced mod 2N.  hoist_exps_arg: exponents [r0, r0 + nr) as a kernel argument (nothing is
+// uploaded).  hoist_each_w: one inverse transform of c1 (no substitution), then the unfused geometry
+// (ks_unfused_geometry: chunks of ciphertexts, groups of key moduli) and ONE stage A per (chunk, group);
+// stage_b(b0, nb, j0, njg, w) then runs on that W.
 // `granule` (matvec_bsgs's giant pass): every ciphertext of the batch stands for `granule` items, `ct` holding the batch x
 // granule 2-part polynomial pairs ciphertext-major, and a chunk holds WHOLE ciphertexts -- W is [nb x granule][nd][jg][N],
 // b0 and nb still count ciphertexts.  The budget rule is the same with a ciphertext costing `granule`
@@ -2207,62 +2212,57 @@ inline std::vector<uint32_t> hoist_exponents(const KskSet &set, const size_t *ex
                                      " moduli), not above it (" + std::to_string(kc.L) + ")");
     return exps;
 }
+inline k::HoistExps hoist_exps_arg(const std::vector<uint32_t> &exps, size_t r0, size_t nr) {
+    k::HoistExps he{};
+    for (size_t r = 0; r < nr; r++) he.e[r] = exps[r0 + r];
+    return he;
+}
 template <class StageB>
 inline void hoist_each_w(const KskSet &set, const u64 *ct, size_t batch, hipStream_t s, StageB &&stage_b, size_t granule = 1) {
     const Ksk &k_ = *set.keys[0];
     const Ctx &kc = *set.ksk_ctx, &cc = *set.ct_ctx;
-    const size_t N = kc.n, nd = set.ndigits, Lk = kc.L;
-    const u64 PL = (u64)cc.L * N;
+    const size_t Lk = kc.L;
+    const u64 PL = (u64)cc.L * kc.n;
     kc.need_device();
-    const uint32_t logn = (uint32_t)kc.logn;
     WsGuard c2(batch * granule * PL * sizeof(u64), s);
     k::RowMap m = full_map(cc, cc.L);
     m.src_poly_stride = 2 * PL;
     m.dst_poly_stride = PL;
     launch_ntt(cc, true, ct + PL, c2.u(), m, batch * granule, s);
-    const bool sub14 = logn == 14 && 2 * batch * granule * nd * Lk <= (size_t)device_cus(kc.device);
-    const uint32_t logm = logn > 14 ? 13 : sub14 ? 13 : logn;
-    const uint32_t g0 = logn - logm;
-    const bool narrow = !FHE_LAB_FLAG("NO_NARROW") && kc.below_2p60(0, kc.L);
-    const bool rns = k_.digit_arg() == (1u << 8);
-    size_t budget = set.w_budget.load(std::memory_order_relaxed);
-    if (!budget) budget = KS_W_BUDGET_DEFAULT;
-    const size_t row_bytes = granule * N * sizeof(u64);
-    size_t pc = batch, jg = Lk;
-    if (pc * nd * jg * row_bytes > budget) {
-        jg = std::max<size_t>(1, budget / (pc * nd * row_bytes));
-        if (jg > Lk) jg = Lk;
-        if (pc * nd * jg * row_bytes > budget) pc = std::max<size_t>(1, budget / (nd * jg * row_bytes));
-    }
-    jg = (Lk + ((Lk + jg - 1) / jg) - 1) / ((Lk + jg - 1) / jg);
-    pc = (batch + ((batch + pc - 1) / pc) - 1) / ((batch + pc - 1) / pc);
-    WsGuard w(pc * nd * jg * row_bytes, s);
-    for (size_t b0 = 0; b0 < batch; b0 += pc) {
-        const size_t nb = std::min(pc, batch - b0);
-        for (size_t j0 = 0; j0 < Lk; j0 += jg) {
-            const size_t njg = std::min(jg, Lk - j0);
-            const unsigned grid_a = (unsigned)((nb * granule * nd * njg) << g0);
-            const u64 *pp = c2.u() + b0 * granule * PL;
-            auto stage_a = [&](auto lm, auto g) {
-                launch_ks_ntt<decltype(lm)::value, decltype(g)::value>(k_, narrow, rns, grid_a, s, pp, PL, w.u(), (uint32_t)j0,
-                                                                       (uint32_t)njg, 1u, nullptr);
-            };
-            if (g0 == 0)
-                with_logn<3, 14>(logm, "unsupported key-switch row size", [&](auto lm) { stage_a(lm, int_c<0>{}); });
-            else if (g0 == 1) stage_a(int_c<13>{}, int_c<1>{});
-            else if (g0 == 2) stage_a(int_c<13>{}, int_c<2>{});
-            else stage_a(int_c<13>{}, int_c<3>{});
+    const KsGeometry g = ks_unfused_geometry(k_, batch, set.w_budget.load(std::memory_order_relaxed), true, false, granule);
+    WsGuard w(g.w_bytes, s);
+    for (size_t b0 = 0; b0 < batch; b0 += g.pc) {
+        const size_t nb = std::min(g.pc, batch - b0);
+        for (size_t j0 = 0; j0 < Lk; j0 += g.jg) {
+            const size_t njg = std::min(g.jg, Lk - j0);
+            launch_ks_stage_a(k_, g, nb * granule, j0, njg, s, c2.u() + b0 * granule * PL, PL, w.u(), 1u);
             stage_b(b0, nb, j0, njg, w.u());
         }
     }
 }
-// (blocks of a stage B over nb ciphertexts x njg key moduli x `per` rotations or rotation groups: key ranges in eights)
-inline size_t hoist_grid_b(const Ctx &kc, size_t njg, size_t nb, size_t per) {
-    const size_t cpr = kc.n >= 512 ? kc.n / 512 : 1;
-    const size_t grid_b = (((njg * cpr) + 7) / 8) * nb * per * 8;
-    require(grid_b <= 0x7fffffffu, E_ARG, "hoisted rotations: the launch exceeds the grid limit; lower the W budget");
-    return grid_b;
-}
+inline void mbfv_sum(const Ctx &c, const u64 *shares, size_t nshares, u64 share_stride, size_t npolys, const u64 *base,
+                     u64 base_stride, u64 *out, hipStream_t s);   // (defined with the multiparty protocols below)
+// Rotation or giant groups planned ONCE, on the first W -- the largest: chunks and key-modulus groups are equal but for the
+// last -- and serving every W, so that the call has ONE number of partial sums and every (ciphertext, key modulus) is
+// written in each of them exactly once.  One group in all: the launches write `out` directly.  Otherwise group i writes
+// partial sum i, [batch][2][L][N] in wiped workspace, and ONE mbfv_sum_kernel launch (its layout serves: `shares` =
+// partial sums, polynomials = batch x 2) adds them into `out` at the end.
+struct HoistPartials {
+    size_t nparts = 0;
+    u64 part_words = 0;
+    std::unique_ptr<WsGuard> ws;
+    template <class Plan>
+    void plan_on_first_w(Plan &&plan, u64 words, hipStream_t s) {   // plan(): the call's number of groups
+        if (nparts) return;
+        nparts = plan();
+        part_words = words;
+        if (nparts > 1) ws = std::make_unique<WsGuard>(nparts * part_words * sizeof(u64), s, true);
+    }
+    u64 *dest(u64 *out, size_t first) const { return nparts > 1 ? ws->u() + first * part_words : out; }   // of group `first`
+    void close(const Ctx &cc, size_t batch, u64 *out, hipStream_t s) const {
+        if (nparts > 1) mbfv_sum(cc, ws->u(), nparts, part_words, batch * 2, nullptr, 0, out, s);
+    }
+};
 
 // Hoisted rotations (kernels_kshoist.hpp; not in the reference, whose words this does NOT reproduce except at exponent
 // 1 -- the restatement is tests/hoist_ref.py): the Galois elements exponents[r], r < nrot, of each ciphertext under key r
@@ -2281,20 +2281,16 @@ inline void galois_hoisted(const KskSet &set, const size_t *exponents, size_t nr
     hoist_each_w(set, ct, batch, s, [&](size_t b0, size_t nb, size_t j0, size_t njg, const u64 *w) {
         for (size_t r0 = 0; r0 < nrot; r0 += k::HOIST_ROTS) {
             const size_t nr = std::min<size_t>(k::HOIST_ROTS, nrot - r0);
-            k::HoistExps he{};
-            for (size_t r = 0; r < nr; r++) he.e[r] = exps[r0 + r];
-            const size_t grid_b = hoist_grid_b(kc, njg, nb, nr);
+            const k::HoistExps he = hoist_exps_arg(exps, r0, nr);
+            const unsigned grid_b = hoist_grid_b(kc, njg, nb, nr);
             u64 *o = out + (b0 * nrot + r0) * 2 * PL;
-            FHE_LAUNCH("hoist_mac", k::hoist_mac_kernel, dim3((unsigned)grid_b), dim3(256), 0, s, w, o, o + PL,
+            FHE_LAUNCH("hoist_mac", k::hoist_mac_kernel, dim3(grid_b), dim3(256), 0, s, w, o, o + PL,
                        (u64)nrot * 2 * PL, 2 * PL, ct + b0 * 2 * PL, 2 * PL, set.table.p, (uint32_t)r0, he, kc.dmods(),
                        (uint32_t)set.ndigits, (uint32_t)kc.L, (uint32_t)j0, (uint32_t)njg, (uint32_t)kc.logn,
                        ct + b0 * 2 * PL + PL, 2 * PL, (uint32_t)nb, (uint32_t)nr);
         }
     });
 }
-
-inline void mbfv_sum(const Ctx &c, const u64 *shares, size_t nshares, u64 share_stride, size_t npolys, const u64 *base,
-                     u64 base_stride, u64 *out, hipStream_t s);   // (defined with the multiparty protocols below)
 
 // The rotation groups of one hoist_matvec_kernel launch over nr rotations (the ONE statement of the rule).  A block per
 // (ciphertext, key range) leaves a small batch short of the device -- batch 1 at N = 8192 x 4 moduli is 64 blocks -- so
@@ -2304,7 +2300,7 @@ inline void mbfv_sum(const Ctx &c, const u64 *shares, size_t nshares, u64 share_
 // timings.  forced != 0 (fhe_kskset_set_rot_split): that many groups, clamped likewise.  Returns rotations per group;
 // the groups are ceil(nr / it), so none is empty.
 inline size_t hoist_rot_group(const Ctx &kc, size_t forced, size_t nb, size_t njg, size_t nr) {
-    const size_t cpr = kc.n >= 512 ? kc.n / 512 : 1;
+    const size_t cpr = k::ks_mac_chunks_per_row(kc.n);
     size_t groups = forced;
     if (!groups) {
         const size_t blocks = nb * njg * cpr, want = 2 * (size_t)device_cus(kc.device);
@@ -2319,7 +2315,7 @@ inline size_t hoist_rot_group(const Ctx &kc, size_t forced, size_t nb, size_t nj
 // rule like sub14, no fit to timings.  forced (fhe_kskset_set_bsgs_tile on the BABY set): 1, 2 or 4.
 inline size_t bsgs_group_tile(const Ctx &kc, size_t forced, size_t nb, size_t njg, size_t G) {
     if (forced) return forced;
-    const size_t cpr = kc.n >= 512 ? kc.n / 512 : 1;
+    const size_t cpr = k::ks_mac_chunks_per_row(kc.n);
     const size_t want = 2 * (size_t)device_cus(kc.device);
     for (size_t gt : {(size_t)4, (size_t)2})
         if (gt <= G && nb * njg * cpr * ((G + gt - 1) / gt) >= want) return gt;
@@ -2349,48 +2345,38 @@ inline void matvec_hoisted(const KskSet &set, const size_t *exponents, size_t nr
     require((((uintptr_t)ct | (uintptr_t)pts | (uintptr_t)pt0 | (uintptr_t)out) & 15) == 0, E_ARG,
             "hoisted matvec: buffers must be 16-byte aligned");
     const size_t forced = set.rot_split.load(std::memory_order_relaxed);
-    // The launches on one W and where their groups' partial sums go.  The plan is made once, on the first W -- the largest:
-    // chunks and key-modulus groups are equal but for the last -- and serves every W, so that the call has ONE number of
-    // partial sums and every (ciphertext, key modulus) is written in each of them exactly once.
+    // The launches on one W and where their groups' partial sums go (HoistPartials: planned on the first W).
     struct Launch {
         size_t r0, nr, rpg, ngroups, first;   // `first`: index of its group 0 among the call's partial sums
     };
     std::vector<Launch> plan;
-    auto make_plan = [&](size_t nb, size_t njg) {
-        plan.clear();
-        size_t total = 0;
-        for (size_t r0 = 0; r0 < nrot; r0 += k::HOIST_ROTS) {
-            const size_t nr = std::min<size_t>(k::HOIST_ROTS, nrot - r0);
-            const size_t rpg = hoist_rot_group(kc, forced, nb, njg, nr);
-            const size_t ng = (nr + rpg - 1) / rpg;
-            plan.push_back({r0, nr, rpg, ng, total});
-            total += ng;
-        }
-        return total;
-    };
-    size_t nparts = 0;
-    std::unique_ptr<WsGuard> partial;
-    const u64 part_words = (u64)batch * 2 * PL;
+    HoistPartials parts;
     hoist_each_w(set, ct, batch, s, [&](size_t b0, size_t nb, size_t j0, size_t njg, const u64 *w) {
-        if (!nparts) {
-            nparts = make_plan(nb, njg);
-            if (nparts > 1) partial = std::make_unique<WsGuard>(nparts * part_words * sizeof(u64), s, true);
-        }
+        parts.plan_on_first_w([&] {
+            size_t total = 0;
+            for (size_t r0 = 0; r0 < nrot; r0 += k::HOIST_ROTS) {
+                const size_t nr = std::min<size_t>(k::HOIST_ROTS, nrot - r0);
+                const size_t rpg = hoist_rot_group(kc, forced, nb, njg, nr);
+                const size_t ng = (nr + rpg - 1) / rpg;
+                plan.push_back({r0, nr, rpg, ng, total});
+                total += ng;
+            }
+            return total;
+        }, (u64)batch * 2 * PL, s);
         for (const Launch &l : plan) {
-            k::HoistExps he{};
-            for (size_t r = 0; r < l.nr; r++) he.e[r] = exps[l.r0 + r];
-            const size_t grid_b = hoist_grid_b(kc, njg, nb, l.ngroups);
-            u64 *o = (nparts > 1 ? partial->u() + l.first * part_words : out) + b0 * 2 * PL;
+            const k::HoistExps he = hoist_exps_arg(exps, l.r0, l.nr);
+            const unsigned grid_b = hoist_grid_b(kc, njg, nb, l.ngroups);
+            u64 *o = parts.dest(out, l.first) + b0 * 2 * PL;
             const u64 *c = ct + b0 * 2 * PL;
-            FHE_LAUNCH("hoist_matvec", k::hoist_matvec_kernel, dim3((unsigned)grid_b), dim3(256), 0, s, w, o, o + PL, 2 * PL,
-                       part_words, c, c + PL, 2 * PL, set.table.p, (uint32_t)l.r0, he,
+            FHE_LAUNCH("hoist_matvec", k::hoist_matvec_kernel, dim3(grid_b), dim3(256), 0, s, w, o, o + PL, 2 * PL,
+                       parts.part_words, c, c + PL, 2 * PL, set.table.p, (uint32_t)l.r0, he,
                        pts + (pts_shared ? 0 : b0 * nrot * PL) + l.r0 * PL, pts_shared ? (u64)0 : (u64)nrot * PL, PL,
                        l.r0 == 0 && pt0 ? pt0 + (pts_shared ? 0 : b0 * PL) : nullptr, pts_shared ? (u64)0 : PL, kc.dmods(),
                        (uint32_t)set.ndigits, (uint32_t)kc.L, (uint32_t)j0, (uint32_t)njg, (uint32_t)kc.logn, (uint32_t)nb,
                        (uint32_t)l.nr, (uint32_t)l.rpg, (uint32_t)l.ngroups);
         }
     });
-    if (nparts > 1) mbfv_sum(cc, partial->u(), nparts, part_words, batch * 2, nullptr, 0, out, s);
+    parts.close(cc, batch, out, s);
 }
 
 // Baby-step/giant-step hoisted matrix-vector product (kernels_bsgs.hpp; a restatement like its two parents, whose
@@ -2428,19 +2414,17 @@ inline void matvec_bsgs(const KskSet &baby, const size_t *baby_exps, size_t nbab
     require((((uintptr_t)ct | (uintptr_t)pts | (uintptr_t)out) & 15) == 0, E_ARG, "bsgs matvec: buffers must be 16-byte aligned");
     const size_t tile_forced = baby.bsgs_tile.load(std::memory_order_relaxed);
     const size_t split_forced = giant.rot_split.load(std::memory_order_relaxed);
-    k::HoistExps be{}, ge{};
-    for (size_t r = 0; r < nbaby; r++) be.e[r] = bexps[r];
-    for (size_t r = 0; r < ngiant; r++) ge.e[r] = gexps[r];
+    const k::HoistExps be = hoist_exps_arg(bexps, 0, nbaby), ge = hoist_exps_arg(gexps, 0, ngiant);
     WsGuard first(batch * 2 * PL * sizeof(u64), s), inner(batch * ngiant * 2 * PL * sizeof(u64), s);
     const u64 IS = (u64)ngiant * 2 * PL;   // words of one ciphertext's inner sums 1 .. ngiant
     hoist_each_w(baby, ct, batch, s, [&](size_t b0, size_t nb, size_t j0, size_t njg, const u64 *w) {
         const size_t gt = bsgs_group_tile(kc, tile_forced, nb, njg, G);
         const size_t ntiles = (G + gt - 1) / gt;
-        const size_t grid_b = hoist_grid_b(kc, njg, nb, ntiles);
+        const unsigned grid_b = hoist_grid_b(kc, njg, nb, ntiles);
         u64 *o = inner.u() + b0 * IS, *f = first.u() + b0 * 2 * PL;
         const u64 *c = ct + b0 * 2 * PL;
         auto launch = [&](auto t) {
-            FHE_LAUNCH("bsgs_baby", k::bsgs_baby_kernel<decltype(t)::value>, dim3((unsigned)grid_b), dim3(256), 0, s, w, f, f + PL,
+            FHE_LAUNCH("bsgs_baby", k::bsgs_baby_kernel<decltype(t)::value>, dim3(grid_b), dim3(256), 0, s, w, f, f + PL,
                        2 * PL, o, o + PL, IS, 2 * PL, c, c + PL, 2 * PL, baby.table.p, be, pts + (pts_shared ? 0 : b0 * G * B * PL),
                        pts_shared ? (u64)0 : (u64)G * B * PL, (u64)B * PL, PL, kc.dmods(), (uint32_t)baby.ndigits, (uint32_t)kc.L,
                        (uint32_t)j0, (uint32_t)njg, (uint32_t)kc.logn, (uint32_t)nb, (uint32_t)nbaby, (uint32_t)G,
@@ -2450,24 +2434,22 @@ inline void matvec_bsgs(const KskSet &baby, const size_t *baby_exps, size_t nbab
         else if (gt == 2) launch(int_c<2>{});
         else launch(int_c<1>{});
     });
-    // The giant groups are planned once, on the first W -- the largest -- and serve every W: ONE number of partial sums.
-    size_t gpg = 0, ngroups = 0;
-    std::unique_ptr<WsGuard> partial;
-    const u64 part_words = (u64)batch * 2 * PL;
+    size_t gpg = 0;   // giants per group (HoistPartials: planned on the first W)
+    HoistPartials parts;
     hoist_each_w(giant, inner.u(), batch, s, [&](size_t b0, size_t nb, size_t j0, size_t njg, const u64 *w) {
-        if (!gpg) {
+        parts.plan_on_first_w([&] {
             gpg = hoist_rot_group(kc, split_forced, nb, njg, ngiant);
-            ngroups = (ngiant + gpg - 1) / gpg;
-            if (ngroups > 1) partial = std::make_unique<WsGuard>(ngroups * part_words * sizeof(u64), s, true);
-        }
-        const size_t grid_b = hoist_grid_b(kc, njg, nb, ngroups);
-        u64 *o = (ngroups > 1 ? partial->u() : out) + b0 * 2 * PL;
+            return (ngiant + gpg - 1) / gpg;
+        }, (u64)batch * 2 * PL, s);
+        const size_t ngroups = parts.nparts;
+        const unsigned grid_b = hoist_grid_b(kc, njg, nb, ngroups);
+        u64 *o = parts.dest(out, 0) + b0 * 2 * PL;
         const u64 *in = inner.u() + b0 * IS, *f = first.u() + b0 * 2 * PL;
-        FHE_LAUNCH("bsgs_giant", k::bsgs_giant_kernel, dim3((unsigned)grid_b), dim3(256), 0, s, w, o, o + PL, 2 * PL, part_words,
+        FHE_LAUNCH("bsgs_giant", k::bsgs_giant_kernel, dim3(grid_b), dim3(256), 0, s, w, o, o + PL, 2 * PL, parts.part_words,
                    f, f + PL, 2 * PL, in, in + PL, IS, 2 * PL, giant.table.p, ge, kc.dmods(), (uint32_t)giant.ndigits, (uint32_t)kc.L, (uint32_t)j0,
                    (uint32_t)njg, (uint32_t)kc.logn, (uint32_t)nb, (uint32_t)ngiant, (uint32_t)gpg, (uint32_t)ngroups);
     }, ngiant);
-    if (ngroups > 1) mbfv_sum(cc, partial->u(), ngroups, part_words, batch * 2, nullptr, 0, out, s);
+    parts.close(cc, batch, out, s);
 }
 
 // `&Ciphertext * &RGSWCiphertext` (F/bfv/rgsw_ciphertext.rs:122-156)

@@ -1,6 +1,7 @@
 // kernels_ks.hpp -- the fused key switch: ks_fused_kernel (rows that fit LDS) and ks_fused_split_kernel (sub-blocks).
 #pragma once
 #include "kernels_passes.hpp"
+#include "kernels_ksmac.hpp"
 
 namespace fhe {
 namespace k {
@@ -853,91 +854,69 @@ __global__ void __launch_bounds__(ntt_threads_c(LOGM), 4)
     }
 }
 
-// Stage B.  One lane per 16-byte chunk of an output row (b, j); grid = (key range, polynomial) in an XCD-aware
-// order: the lanes of a block read nd * 2 * 4 KiB of key words that every polynomial of the launch needs again, so
-// the blocks of one key range get ids 8 apart (same XCD, dispatched back to back: the re-reads hit that L2).
-// Lazy accumulation: x < 2^62, k < 2^62 -> x * k < 2^124, sixteen terms fit 128 bits; longer digit loops fold the
-// accumulator through the 128-bit reduction every sixteen terms.
+// Stage B (the pieces it shares with its siblings: kernels_ksmac.hpp).  One lane per 16-byte chunk of an output row
+// (b, j); within a group of eight key ranges the polynomial runs fastest.  ONE reduction per output: the products go
+// into lazy 128-bit accumulators (KsMacQuad).
+// FHE_KS_MAC_SUM: what ks_mac_kernel and ks_mac_keyed_kernel (kernels_kskeyed.hpp) do once they know the key words
+// (k0, k1) of their polynomial b -- the sum, the addends, the store -- on the kernels' (common) argument names and the
+// coordinates `at`.  A macro body, undefined after ks_mac_keyed_kernel: called as a function it costs both kernels
+// 18 VGPRs and 38 instructions.  `gal`: see ks_fused_kernel.
+#define FHE_KS_MAC_SUM(b, k0, k1)                                                                                     \
+    const uint32_t n = at.n, j = at.j;                                                                                \
+    const DevMod md = mods[j];                                                                                        \
+    const u64 roff = at.roff();                                                                                       \
+    const u64 *wp = w + (((u64)(b) * ndigits) * jg + at.jj) * n + roff;   /* + i * jg * n per digit */                \
+    const u64 *kp0 = (k0) + (u64)j * n + roff, *kp1 = (k1) + (u64)j * n + roff;   /* + i * lk * n per digit */        \
+    const bool own = xhat != nullptr && j < ndigits;      /* (block-uniform) */                                       \
+    KsMacQuad acc;                                                                                                    \
+    /* (W is read exactly once, by this lane: a streaming load; the key words are other polynomials' too: cached) */  \
+    FHE_KS_DIGIT_LOOP(acc, ndigits, md, kp0, kp1, lk, n, {                                                            \
+        if (own && i == j) {                                                                                          \
+            const u64 *xrow = xhat + (u64)(b) * xhat_poly_stride + (u64)j * n;                                        \
+            if (gal) {                                                                                                \
+                xv.x = xrow[galois_src_index((uint32_t)roff, gal, logn)];                                             \
+                xv.y = xrow[galois_src_index((uint32_t)roff + 1, gal, logn)];                                         \
+            } else {                                                                                                  \
+                xv = *reinterpret_cast<const u64x2 *>(xrow + roff);                                                   \
+            }                                                                                                         \
+        } else {                                                                                                      \
+            xv = load_stream(reinterpret_cast<const u64x2 *>(wp + (u64)i * jg * n));                                  \
+        }                                                                                                             \
+    })                                                                                                                \
+    u64x2 r0, r1;                                                                                                     \
+    acc.reduce(md, r0, r1);                                                                                           \
+    const u64 ooff = (u64)(b) * out_poly_stride + (u64)j * n + roff;                                                  \
+    const u64 aoff = (u64)(b) * addend_poly_stride + (u64)j * n + roff;                                               \
+    if (addend0) {                                                                                                    \
+        u64x2 a;                                                                                                      \
+        if (gal) {                                                                                                    \
+            const u64 *arow = addend0 + aoff - roff;                                                                  \
+            a.x = arow[galois_src_index((uint32_t)roff, gal, logn)];                                                  \
+            a.y = arow[galois_src_index((uint32_t)roff + 1, gal, logn)];                                              \
+        } else {                                                                                                      \
+            a = *reinterpret_cast<const u64x2 *>(addend0 + aoff);                                                     \
+        }                                                                                                             \
+        r0.x = add_mod(r0.x, a.x, md.p);                                                                              \
+        r0.y = add_mod(r0.y, a.y, md.p);                                                                              \
+    }                                                                                                                 \
+    if (addend1) {                                                                                                    \
+        const u64x2 a = *reinterpret_cast<const u64x2 *>(addend1 + aoff);                                             \
+        r1.x = add_mod(r1.x, a.x, md.p);                                                                              \
+        r1.y = add_mod(r1.y, a.y, md.p);                                                                              \
+    }                                                                                                                 \
+    *reinterpret_cast<u64x2 *>(out0 + ooff) = r0;                                                                     \
+    *reinterpret_cast<u64x2 *>(out1 + ooff) = r1;
 __global__ void __launch_bounds__(256)
     ks_mac_kernel(const u64 *__restrict__ w, u64 *__restrict__ out0, u64 *__restrict__ out1, u64 out_poly_stride,
                   const u64 *__restrict__ addend0, const u64 *__restrict__ addend1, u64 addend_poly_stride,
                   const u64 *__restrict__ k0, const u64 *__restrict__ k1, const DevMod *__restrict__ mods,
                   uint32_t ndigits, uint32_t lk, uint32_t j0, uint32_t jg, uint32_t logn, const u64 *__restrict__ xhat,
-                  u64 xhat_poly_stride, uint32_t npolys, uint32_t gal) {   // (gal: see ks_fused_kernel)
-    const uint32_t n = 1u << logn;
-    const uint32_t cpr = n >= 512 ? n / 512 : 1;          // 256-lane chunks per row
-    const uint32_t nkr = jg * cpr;                        // key ranges of this launch
-    const uint32_t grp = blockIdx.x >> 3, x8 = blockIdx.x & 7;
-    const uint32_t krhi = grp / npolys, b = grp - krhi * npolys;
-    const uint32_t kr = krhi * 8 + x8;
-    if (kr >= nkr) return;                                // (block-uniform) tail of the rounded-up grid
-    const uint32_t jj = kr / cpr, cb = kr - jj * cpr, j = j0 + jj;
-    const uint32_t ci = cb * 256 + threadIdx.x;           // 16-byte chunk inside the row
-    if (2 * ci >= n) return;
-    const DevMod md = mods[j];
-    const u64 roff = 2 * (u64)ci;
-    const u64 *wp = w + (((u64)b * ndigits) * jg + jj) * n + roff;      // + i * jg * n per digit
-    const u64 *kp0 = k0 + (u64)j * n + roff, *kp1 = k1 + (u64)j * n + roff;   // + i * lk * n per digit
-    const bool own = xhat != nullptr && j < ndigits;      // (block-uniform)
-    u128_t a0x = 0, a0y = 0, a1x = 0, a1y = 0;
-    auto mac = [&](u128_t &acc, u64 x, u64 k) {
-        u64 hi, lo;
-        mul_wide62(x, k, hi, lo);
-        acc += ((u128_t)hi << 64) | lo;
-    };
-    auto fold = [&](u128_t &acc) { acc = reduce_u128((u64)(acc >> 64), (u64)acc, md); };
-    for (uint32_t i0 = 0; i0 < ndigits; i0 += 16) {
-        const uint32_t i1 = i0 + 16 < ndigits ? i0 + 16 : ndigits;
-        if (i0) fold(a0x), fold(a0y), fold(a1x), fold(a1y);
-#pragma unroll 4
-        for (uint32_t i = i0; i < i1; i++) {
-            // (W is read exactly once, by this lane: a streaming load; the key words are every polynomial's: cached)
-            u64x2 xv;
-            if (own && i == j) {
-                const u64 *xrow = xhat + (u64)b * xhat_poly_stride + (u64)j * n;
-                if (gal) {
-                    xv.x = xrow[galois_src_index((uint32_t)roff, gal, logn)];
-                    xv.y = xrow[galois_src_index((uint32_t)roff + 1, gal, logn)];
-                } else {
-                    xv = *reinterpret_cast<const u64x2 *>(xrow + roff);
-                }
-            } else {
-                xv = load_stream(reinterpret_cast<const u64x2 *>(wp + (u64)i * jg * n));
-            }
-            const u64x2 q0 = *reinterpret_cast<const u64x2 *>(kp0 + (u64)i * lk * n);
-            const u64x2 q1 = *reinterpret_cast<const u64x2 *>(kp1 + (u64)i * lk * n);
-            mac(a0x, xv.x, q0.x);
-            mac(a0y, xv.y, q0.y);
-            mac(a1x, xv.x, q1.x);
-            mac(a1y, xv.y, q1.y);
-        }
-    }
-    u64x2 r0, r1;
-    r0.x = reduce_u128((u64)(a0x >> 64), (u64)a0x, md);
-    r0.y = reduce_u128((u64)(a0y >> 64), (u64)a0y, md);
-    r1.x = reduce_u128((u64)(a1x >> 64), (u64)a1x, md);
-    r1.y = reduce_u128((u64)(a1y >> 64), (u64)a1y, md);
-    const u64 ooff = (u64)b * out_poly_stride + (u64)j * n + roff;
-    const u64 aoff = (u64)b * addend_poly_stride + (u64)j * n + roff;
-    if (addend0) {
-        u64x2 a;
-        if (gal) {
-            const u64 *arow = addend0 + aoff - roff;
-            a.x = arow[galois_src_index((uint32_t)roff, gal, logn)];
-            a.y = arow[galois_src_index((uint32_t)roff + 1, gal, logn)];
-        } else {
-            a = *reinterpret_cast<const u64x2 *>(addend0 + aoff);
-        }
-        r0.x = add_mod(r0.x, a.x, md.p);
-        r0.y = add_mod(r0.y, a.y, md.p);
-    }
-    if (addend1) {
-        const u64x2 a = *reinterpret_cast<const u64x2 *>(addend1 + aoff);
-        r1.x = add_mod(r1.x, a.x, md.p);
-        r1.y = add_mod(r1.y, a.y, md.p);
-    }
-    *reinterpret_cast<u64x2 *>(out0 + ooff) = r0;
-    *reinterpret_cast<u64x2 *>(out1 + ooff) = r1;
+                  u64 xhat_poly_stride, uint32_t npolys, uint32_t gal) {
+    KsMacAt at(logn, jg, npolys);
+    if (at.kr >= at.nkr) return;                          // (block-uniform) tail of the rounded-up grid
+    at.lane(j0);
+    if (2 * at.ci >= at.n) return;
+    FHE_KS_MAC_SUM(at.item, k0, k1)
 }
 
 }  // namespace k

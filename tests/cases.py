@@ -524,7 +524,44 @@ def case_key_switch_levels(fhe, dev, nmod=4, n=16):
                 assert np.array_equal(got[i], ct_arr(c))
 
 
-def case_key_switch_many_digits(fhe, dev, n=128, shapes=((50, 10), (58, 17), (62, 5), (60, 9), (45, 2), (61, 3))):
+def case_unfused_launch_counts(fhe, dev, nmod=3, n=16, npolys=5):
+    """The single-key unfused key switch under a W budget that cuts BOTH ways (hoist_cases.case_w_budget's: chunks of two
+    polynomials -- the last one short -- and groups of one key modulus): the words against the oracle, and the profiled
+    launches -- one ks_digit_ntt and one ks_mac per (chunk, key-modulus group) of keyed_cases.chunk_rule."""
+    from keyed_cases import chunk_rule
+    x = Xfer(dev)
+    rng = random.Random(15)
+    opar, par = _params(fhe, nmod, n)
+    sk = obfv.SecretKey.random(opar, rng)
+    ork = obfv.RelinearizationKey(sk, rng, 0, 0)
+    c0, _, c1, _ = ksk_arrays(ork.ksk)
+    p = [rand_poly(opar.ctx[0], POWER_BASIS, rng) for _ in range(npolys)]
+    inp = np.stack([arr(q) for q in p])
+    want = [ork.ksk.key_switch(q) for q in p]
+    budget = 2 * nmod * n * 8
+    pc, jg = chunk_rule(npolys, nmod, nmod, n, budget)
+    assert (pc, jg) == (2, 1) and npolys % pc != 0 and chunk_rule(npolys, nmod, nmod, n, 0) == (npolys, nmod)
+    for w_budget, pairs in ((budget, -(-npolys // pc) * -(-nmod // jg)), (0, 1)):
+        with fhe.KeySwitchingKey.forced_mode(fhe.KeySwitchingKey.UNFUSED, w_budget):
+            ksk = fhe.KeySwitchingKey(par.context_at_level(0), par.context_at_level(0), c0, c1)
+        src = x.to(inp)
+        fhe.prof_reset()
+        fhe.prof_enable(True)
+        try:
+            g0, g1 = ksk.key_switch(src)
+        finally:
+            fhe.prof_enable(False)
+        report = fhe.prof_report()
+        fhe.prof_reset()
+        g0, g1 = x.back(g0), x.back(g1)
+        for i, (w0, w1) in enumerate(want):
+            assert np.array_equal(g0[i], arr(w0)) and np.array_equal(g1[i], arr(w1)), (w_budget, i)
+        count = {label: report.get(label, (0, 0.0))[0] for label in ("ks_digit_ntt", "ks_mac")}
+        print("unfused launches under W budget", w_budget, ":", count, "expected", pairs, "each")
+        assert count == {"ks_digit_ntt": pairs, "ks_mac": pairs}, (w_budget, report)
+
+
+def case_key_switch_many_digits(fhe, dev, n=128,shapes=((50, 10), (58, 17), (62, 5), (60, 9), (45, 2), (61, 3))):
     """key_switching_key.rs:241-270 with long digit loops: the fused kernels go through the digits two per round
     (+ one single round for an odd count) and, for moduli below 2^60, leave their accumulators unreduced for up to
     eight digits before folding them back -- 9, 10 and 17 digits cross that fold once and twice.  Random residues

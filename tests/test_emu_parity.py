@@ -321,6 +321,12 @@ def test_unfused_small_w_budget(fhe):
         cases.case_galois(fhe, False)
 
 
+def test_unfused_launch_counts_under_w_budget(fhe):
+    """The plain single-key path: profiled stage-A and stage-B launches = chunks x key-modulus groups of chunk_rule, under
+    a budget that leaves a short last chunk and more than one group."""
+    cases.case_unfused_launch_counts(fhe, False)
+
+
 @pytest.mark.parametrize("nmod,level,chunk", [(2, 0, 0), (3, 1, 0), (4, 1, 1)])
 def test_unfused_multiply(fhe, nmod, level, chunk):
     with _unfused(fhe):

@@ -656,6 +656,13 @@ def test_unfused_key_switch_small(fhe, dev):
         cases.case_multiply(fhe, dev, nmod=3, level=0, chunk=2, batch=5)
 
 
+@pytest.mark.parametrize("dev", [False, True])
+def test_unfused_launch_counts_under_w_budget(fhe, dev):
+    """The plain single-key path: profiled stage-A and stage-B launches = chunks x key-modulus groups of chunk_rule, under
+    a budget that leaves a short last chunk and more than one group."""
+    cases.case_unfused_launch_counts(fhe, dev)
+
+
 @pytest.mark.parametrize("mode", ["fused", "unfused"])
 @pytest.mark.parametrize("sizes,n,batch", [([60, 58, 62, 50], 4096, 7), ([61, 45, 36], 2048, 33), ([62] * 6, 1024, 5),
                                            ([60, 60], 256, 3)])
