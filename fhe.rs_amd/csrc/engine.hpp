@@ -772,7 +772,6 @@ inline std::unique_ptr<Ctx> ctx_create(int device, size_t degree, const std::vec
 
 // ------------------------------------------------------------------- launch helpers ----
 inline hipStream_t as_stream(void *s) { return (hipStream_t)s; }
-inline unsigned blocks_for(u64 total, unsigned threads) { return (unsigned)((total + threads - 1) / threads); }
 constexpr unsigned EW_THREADS = 256;
 
 template <class K>
@@ -787,6 +786,33 @@ template <auto KERNEL, class... A>
 inline void launch_k(const char *name, dim3 grid, dim3 block, size_t lds, hipStream_t s, A... args) {
     allow_big_lds(KERNEL, lds);
     FHE_LAUNCH(name, KERNEL, grid, block, lds, s, args...);
+}
+
+// ---- launch geometry: a site names its kernel, its label, what it runs over and its arguments; how that becomes a
+// grid, and what is refused, is written here.  The two limits are this file's only assumptions about a grid: x below
+// 2^31 blocks (beyond it the `unsigned` of a dim3 would wrap), y and z at most GRID_YZ_MAX (nothing here relies on what
+// the runtime does with more: a site either refuses a larger batch or cuts it with for_groups).
+constexpr size_t GRID_YZ_MAX = 65535;
+inline u64 blocks_for(u64 total, u64 threads) { return (total + threads - 1) / threads; }
+inline unsigned grid_x(u64 blocks, const char *what, const char *advice = "") {
+    if (blocks > 0x7fffffffu) throw StatusError(E_ARG, std::string(what) + ": the launch exceeds the grid limit" + advice);
+    return (unsigned)blocks;
+}
+// `blocks` workgroups of `threads` lanes in one dimension
+template <auto KERNEL, class... A>
+inline void launch_blocks(const char *name, u64 blocks, unsigned threads, size_t lds, hipStream_t s, A... args) {
+    launch_k<KERNEL>(name, dim3(grid_x(blocks, name)), dim3(threads), lds, s, args...);
+}
+// element-wise: one lane per element of `total`
+template <auto KERNEL, unsigned THREADS = EW_THREADS, class... A>
+inline void launch_ew(const char *name, u64 total, hipStream_t s, A... args) {
+    launch_blocks<KERNEL>(name, blocks_for(total, THREADS), THREADS, 0, s, args...);
+}
+// x: one lane per element of `per`; y and z: whatever else the kernel's grid runs over (rows, parts, items of a batch)
+template <auto KERNEL, unsigned THREADS = EW_THREADS, size_t LDS = 0, class... A>
+inline void launch_rows(const char *name, u64 per, size_t y, size_t z, hipStream_t s, A... args) {
+    if (y > GRID_YZ_MAX || z > GRID_YZ_MAX) throw StatusError(E_ARG, std::string(name) + ": batch exceeds the grid limit");
+    launch_k<KERNEL>(name, dim3(grid_x(blocks_for(per, THREADS), name), (unsigned)y, (unsigned)z), dim3(THREADS), LDS, s, args...);
 }
 // (a kernel as a value, for the local launch lambdas of a site: decltype(kernel)::value is the kernel)
 template <auto KERNEL>
@@ -846,7 +872,7 @@ inline void with_tile(size_t logm, const char *what, bool narrow, int hr, F &&f)
 // ... and their launch: `grid` workgroups of one 2^lm-point tile each
 template <auto KERNEL, class... A>
 inline void launch_tile(const char *name, int lm, size_t grid, hipStream_t s, A... args) {
-    launch_k<KERNEL>(name, dim3((unsigned)grid), dim3(k::ntt_threads_c(lm)), k::lds_words(1u << lm) * sizeof(u64), s, args...);
+    launch_blocks<KERNEL>(name, grid, k::ntt_threads_c(lm), k::lds_words(1u << lm) * sizeof(u64), s, args...);
 }
 
 // A whole-row launch (rows of at most one LDS tile, N <= 16384: the encoding, sampling, encryption, key-generation
@@ -900,7 +926,7 @@ inline bool lab_try_ks_pair(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0, 
 // (GATHER: galois_apply folds the substitution from N = 4096 on: three tile sizes)
 template <bool INV, bool GATHER = false>
 inline void launch_ntt_lds(const Ctx &c, const char *name, const char *name_f64, uint32_t logm, bool narrow, int hr,
-                           unsigned grid, hipStream_t s, const u64 *in, u64 *out, const k::RowMap &map, uint32_t logn) {
+                           size_t grid, hipStream_t s, const u64 *in, u64 *out, const k::RowMap &map, uint32_t logn) {
     with_tile<GATHER ? 12 : 3>(
         logm, GATHER ? "unsupported NTT tile size for the gathering loader" : "unsupported NTT tile size", narrow, hr,
         [&](auto lm, auto nrw, auto h) {
@@ -911,18 +937,31 @@ inline void launch_ntt_lds(const Ctx &c, const char *name, const char *name_f64,
         });
 }
 
+// The logn - 13 global radix stages of rows larger than LDS (N = 32768 / 65536), over `rows` residue rows.
+template <bool INV>
+inline void launch_ntt_global(const Ctx &c, u64 rows, hipStream_t s, const u64 *in, u64 *out, const k::RowMap &map) {
+    const char *name = INV ? "ntt_inv_global" : "ntt_fwd_global";
+    const u64 blocks = rows * ((1u << 13) / 256);
+    auto launch = [&](auto kernel) {
+        launch_blocks<decltype(kernel)::value>(name, blocks, 256, 0, s, in, out, map, c.dmods(), INV ? c.ditw() : c.dtw(), c.dninv(),
+                                               (uint32_t)c.logn);
+    };
+    if (c.logn == 15) launch(kernel_c<k::ntt_global_kernel<INV, 2>>{});
+    else launch(kernel_c<k::ntt_global_kernel<INV, 3>>{});
+}
+
 // Forward / inverse NTT of `npolys * map.rows` residue rows.  N <= 16384: one LDS-resident
 // kernel.  N = 32768 / 65536: G0 global radix stages + LDS kernel on 8192-point sub-blocks.
 inline void launch_ntt(const Ctx &c, bool inverse, const u64 *in, u64 *out, k::RowMap map, size_t npolys,
                        hipStream_t s) {
     if (npolys == 0 || map.rows == 0) return;
     const uint32_t logn = (uint32_t)c.logn;
-    const unsigned rows_total = (unsigned)(npolys * map.rows);
+    const unsigned rows_total = grid_x(npolys * map.rows, "ntt");
     const size_t first = (size_t)((int32_t)map.row_begin + map.mod_offset);
     // every modulus of the launch below 2^60: the transform without per-stage conditional subtractions
     bool narrow = !FHE_LAB_FLAG("NO_NARROW") && c.below_2p60(first, map.rows);
     // (inverse: with subst_exp the source rows are read through the substitution x -> x^subst_exp, galois_apply)
-    auto inverse_lds = [&](uint32_t logm, int hr, unsigned grid) {
+    auto inverse_lds = [&](uint32_t logm, int hr, size_t grid) {
         with_bool(map.subst_exp != 0, [&](auto gather) {
             launch_ntt_lds<true, decltype(gather)::value>(c, "ntt_inv", "ntt_inv_f64", logm, narrow, hr, grid, s, in, out, map,
                                                           logn);
@@ -938,8 +977,8 @@ inline void launch_ntt(const Ctx &c, bool inverse, const u64 *in, u64 *out, k::R
         launch_ntt_lds<false>(c, "ntt_fwd", "ntt_fwd_f64", logn, narrow, hr, rows_total, s, in, out, map, logn);
         return;
     }
-    const uint32_t logm = 13, g0 = logn - logm, m = 1u << logm;
-    const unsigned gth = 256, gblocks = rows_total * (m / gth);
+    const uint32_t logm = 13, g0 = logn - logm;
+    const size_t tiles = (size_t)rows_total << g0;
     // the LDS halves take the bound-tracked narrow passes here too (round 4; rounds 1-3 ran rows larger than LDS on the
     // general passes whatever the moduli)
     narrow = narrow && !FHE_LAB_FLAG("NO_NARROW_SUB");
@@ -949,25 +988,15 @@ inline void launch_ntt(const Ctx &c, bool inverse, const u64 *in, u64 *out, k::R
     inplace.in2 = nullptr;   // (the second half of the transform works in `out`: one array)
     inplace.subst_exp = 0;
     if (!inverse) {
-        if (g0 == 2)
-            FHE_LAUNCH("ntt_fwd_global", (k::ntt_global_kernel<false, 2>), dim3(gblocks), dim3(gth), 0, s, in, out,
-                       map, c.dmods(), c.dtw(), c.dninv(), logn);
-        else
-            FHE_LAUNCH("ntt_fwd_global", (k::ntt_global_kernel<false, 3>), dim3(gblocks), dim3(gth), 0, s, in, out,
-                       map, c.dmods(), c.dtw(), c.dninv(), logn);
+        launch_ntt_global<false>(c, rows_total, s, in, out, map);
         if (narrow)   // (the global stages above leave values below 4p: FWD_B0 = 4)
-            launch_tile<k::ntt_kernel<false, 13, true, 4>>("ntt_fwd", 13, rows_total << g0, s, out, out, inplace, c.dmods(),
-                                                           c.dtw(), c.dninv(), logn);
+            launch_tile<k::ntt_kernel<false, 13, true, 4>>("ntt_fwd", 13, tiles, s, out, out, inplace, c.dmods(), c.dtw(),
+                                                           c.dninv(), logn);
         else
-            launch_ntt_lds<false>(c, "ntt_fwd", nullptr, logm, false, 0, rows_total << g0, s, out, out, inplace, logn);
+            launch_ntt_lds<false>(c, "ntt_fwd", nullptr, logm, false, 0, tiles, s, out, out, inplace, logn);
     } else {
-        inverse_lds(logm, 0, rows_total << g0);
-        if (g0 == 2)
-            FHE_LAUNCH("ntt_inv_global", (k::ntt_global_kernel<true, 2>), dim3(gblocks), dim3(gth), 0, s, out, out,
-                       inplace, c.dmods(), c.ditw(), c.dninv(), logn);
-        else
-            FHE_LAUNCH("ntt_inv_global", (k::ntt_global_kernel<true, 3>), dim3(gblocks), dim3(gth), 0, s, out, out,
-                       inplace, c.dmods(), c.ditw(), c.dninv(), logn);
+        inverse_lds(logm, 0, tiles);
+        launch_ntt_global<true>(c, rows_total, s, out, out, inplace);
     }
 }
 
@@ -991,11 +1020,26 @@ inline k::RowMap full_map(const Ctx &c, size_t rows_in_poly) {
     return m;
 }
 
+// ... with its own source and destination polynomial strides
+inline k::RowMap strided_map(const Ctx &c, size_t rows_in_poly, u64 src_stride, u64 dst_stride) {
+    k::RowMap m = full_map(c, rows_in_poly);
+    m.src_poly_stride = src_stride;
+    m.dst_poly_stride = dst_stride;
+    return m;
+}
+// the rows after the first `ncommon` of [npolys][c.L][N] (what a basis extension adds to the rows both bases share)
+inline k::RowMap new_rows_map(const Ctx &c, size_t ncommon) {
+    k::RowMap m = full_map(c, c.L);
+    m.rows = (uint32_t)(c.L - ncommon);
+    m.row_begin = (uint32_t)ncommon;
+    return m;
+}
+
 inline void launch_tensor_intt_rows(const Ctx &e, const k::TensorSrc &ts, u64 *out, size_t nb, uint32_t row_begin,
                                     uint32_t lrows, bool narrow, hipStream_t s, bool reverse, int f64_hr = 0) {
     const uint32_t logn = (uint32_t)e.logn, logm = logn <= 14 ? logn : 13;
     // 8 (row, pair, sub-block) combinations x 3 slots per group
-    const unsigned groups = (unsigned)(((((size_t)lrows * nb) << (logn - logm)) + 7) / 8);
+    const size_t groups = ((((size_t)lrows * nb) << (logn - logm)) + 7) / 8;
     auto launch = [&](auto kernel, bool nrw, bool f64) {
         launch_tile<decltype(kernel)::value>(f64 ? "tensor_intt_f64" : nrw ? "tensor_intt_narrow" : "tensor_intt", (int)logm,
                                              groups * 24, s, ts, out, e.dmods(), f64 ? e.ditw_f() : e.ditw(),
@@ -1045,18 +1089,7 @@ inline void launch_tensor_intt(const Ctx &e, const k::TensorSrc &ts, u64 *out, s
     if (reverse) std::reverse(runs.begin(), runs.end());
     for (const Run &r : runs)
         launch_tensor_intt_rows(e, ts, out, nb, r.r0, r.n, r.kind == 1, s, reverse, r.kind == 2 ? e.f64_class(r.r0, r.n) : 0);
-    const uint32_t logn = (uint32_t)e.logn;
-    if (logn > 14) {  // the global inverse stages finish every row
-        const uint32_t logm = 13;
-        const unsigned gth = 256, gblocks = (unsigned)(nb * 3 * e.L) * ((1u << logm) / gth);
-        const k::RowMap m = full_map(e, e.L);
-        if (logn - logm == 2)
-            FHE_LAUNCH("ntt_inv_global", (k::ntt_global_kernel<true, 2>), dim3(gblocks), dim3(gth), 0, s, out, out, m,
-                       e.dmods(), e.ditw(), e.dninv(), logn);
-        else
-            FHE_LAUNCH("ntt_inv_global", (k::ntt_global_kernel<true, 3>), dim3(gblocks), dim3(gth), 0, s, out, out, m,
-                       e.dmods(), e.ditw(), e.dninv(), logn);
-    }
+    if (e.logn > 14) launch_ntt_global<true>(e, nb * 3 * e.L, s, out, out, full_map(e, e.L));   // (they finish every row)
 }
 
 inline void ntt_polys(const Ctx &c, bool inverse, const u64 *in, u64 *out, size_t npolys, hipStream_t s) {
@@ -1068,8 +1101,12 @@ inline void ew_op(const Ctx &c, u64 *a, const u64 *b, size_t npolys, uint32_t op
     c.need_device();
     const u64 total = (u64)npolys * c.L * c.n;
     if (!total) return;
-    FHE_LAUNCH("ew", k::ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s, a, b, c.dmods(),
-               (uint32_t)c.L, (uint32_t)c.logn, op, total);
+    launch_ew<k::ew_kernel>("ew", total, s, a, b, c.dmods(), (uint32_t)c.L, (uint32_t)c.logn, op, total);
+}
+
+// `npolys` runs of `per` words, run i from in + i * in_stride to out + i * out_stride
+inline void copy_rows(const u64 *in, u64 in_stride, u64 *out, u64 out_stride, u64 per, size_t npolys, hipStream_t s) {
+    launch_ew<k::copy_rows_kernel>("copy_rows", per * npolys, s, in, out, in_stride, out_stride, per, per * npolys);
 }
 
 // ------------------------------------------------------------------ Rq wire format ----
@@ -1077,6 +1114,25 @@ inline size_t wire_poly_bytes(const Ctx &c) {
     size_t b = 0;
     for (size_t i = 0; i < c.L; i++) b += (size_t)(64 - __builtin_clzll(c.moduli[i] - 1)) * (c.n / 8);
     return b;
+}
+// One launch per 32768 polynomials (the grid's z) of a wire kernel pair: rows of >= 128 coefficients between 16-byte
+// aligned buffers (every row then starts on a 16-byte boundary) take the word-granular kernel over `word_lanes` lanes a
+// row, the others the byte-granular one, a lane per eight coefficients.
+template <auto WORDS, auto BYTES, class In, class Out>
+inline void launch_wire(const char *name, const Ctx &c, u64 word_lanes, const In *in, u64 in_stride, Out *out, u64 out_stride,
+                        size_t npolys, hipStream_t s) {
+    const u64 wb = wire_poly_bytes(c), groups = c.n / 8;
+    const bool words = c.n >= 128 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0;
+    for_groups(npolys, 32768, [&](size_t p0, size_t np) {
+        auto launch = [&](auto kernel, auto threads, u64 per) {
+            launch_rows<decltype(kernel)::value, decltype(threads)::value>(name, per, c.L, np, s, in + p0 * in_stride,
+                                                                           out + p0 * out_stride, c.dmods(), (uint32_t)c.L,
+                                                                           (uint32_t)c.logn, wb);
+        };
+        if (words) launch(kernel_c<WORDS>{}, int_c<256>{}, word_lanes);
+        else if (groups < 256) launch(kernel_c<BYTES>{}, int_c<64>{}, groups);
+        else launch(kernel_c<BYTES>{}, int_c<256>{}, groups);
+    });
 }
 // polys [npolys][L][N] -> bytes [npolys][wire_poly_bytes]; from_ntt: inverse NTT first (into scratch).
 inline void wire_serialize(const Ctx &c, const u64 *polys, uint8_t *bytes, size_t npolys, bool from_ntt, hipStream_t s) {
@@ -1088,37 +1144,15 @@ inline void wire_serialize(const Ctx &c, const u64 *polys, uint8_t *bytes, size_
         launch_ntt(c, true, polys, pb.u(), full_map(c, c.L), npolys, s);
         polys = pb.u();
     }
-    const unsigned groups = (unsigned)(c.n / 8), block = groups < 256 ? 64 : 256;
-    const u64 wb = wire_poly_bytes(c);
-    // rows of >= 128 coefficients (and a 16-byte aligned destination: every row then starts on a 16-byte boundary)
-    // take the word-granular kernel; its grid covers the widest row (62 bits)
-    const bool words = c.n >= 128 && ((uintptr_t)bytes & 15) == 0 && ((uintptr_t)polys & 15) == 0;
-    for (size_t p0 = 0; p0 < npolys; p0 += 32768) {  // gridDim.z <= 65535
-        const size_t np = std::min<size_t>(32768, npolys - p0);
-        if (words)
-            FHE_LAUNCH("wire_pack", k::wire_pack_words_kernel,
-                       dim3(blocks_for((c.n >> 7) * 64, 256), (unsigned)c.L, (unsigned)np), dim3(256), 0, s, polys + p0 * pe,
-                       bytes + p0 * wb, c.dmods(), (uint32_t)c.L, (uint32_t)c.logn, wb);
-        else
-            FHE_LAUNCH("wire_pack", k::wire_pack_kernel, dim3(blocks_for(groups, block), (unsigned)c.L, (unsigned)np),
-                       dim3(block), 0, s, polys + p0 * pe, bytes + p0 * wb, c.dmods(), (uint32_t)c.L, (uint32_t)c.logn, wb);
-    }
+    // (the word-granular grid covers the widest row, 62 bits)
+    launch_wire<k::wire_pack_words_kernel, k::wire_pack_kernel>("wire_pack", c, (c.n >> 7) * 64, polys, pe, bytes,
+                                                                wire_poly_bytes(c), npolys, s);
 }
 inline void wire_deserialize(const Ctx &c, const uint8_t *bytes, u64 *polys, size_t npolys, bool to_ntt, hipStream_t s) {
     c.need_device();
     if (!npolys) return;
-    const unsigned groups = (unsigned)(c.n / 8), block = groups < 256 ? 64 : 256;
-    const u64 wb = wire_poly_bytes(c), pe = (u64)c.L * c.n;
-    const bool words = c.n >= 128 && ((uintptr_t)bytes & 15) == 0 && ((uintptr_t)polys & 15) == 0;   // (see wire_serialize)
-    for (size_t p0 = 0; p0 < npolys; p0 += 32768) {
-        const size_t np = std::min<size_t>(32768, npolys - p0);
-        if (words)
-            FHE_LAUNCH("wire_unpack", k::wire_unpack_words_kernel, dim3(blocks_for(c.n / 2, 256), (unsigned)c.L, (unsigned)np),
-                       dim3(256), 0, s, bytes + p0 * wb, polys + p0 * pe, c.dmods(), (uint32_t)c.L, (uint32_t)c.logn, wb);
-        else
-            FHE_LAUNCH("wire_unpack", k::wire_unpack_kernel, dim3(blocks_for(groups, block), (unsigned)c.L, (unsigned)np),
-                       dim3(block), 0, s, bytes + p0 * wb, polys + p0 * pe, c.dmods(), (uint32_t)c.L, (uint32_t)c.logn, wb);
-    }
+    launch_wire<k::wire_unpack_words_kernel, k::wire_unpack_kernel>("wire_unpack", c, c.n / 2, bytes, wire_poly_bytes(c), polys,
+                                                                    (u64)c.L * c.n, npolys, s);
     if (to_ntt) launch_ntt(c, false, polys, polys, full_map(c, c.L), npolys, s);
 }
 
@@ -1126,9 +1160,8 @@ inline void wire_deserialize(const Ctx &c, const uint8_t *bytes, u64 *polys, siz
 inline void polys_from_seeds(const Ctx &c, const uint8_t *seeds, u64 *polys, size_t npolys, hipStream_t s) {
     c.need_device();
     if (!npolys) return;
-    FHE_LAUNCH("seed_expand", k::seed_expand_kernel, dim3((unsigned)npolys), dim3(k::SEED_THREADS), k::SEED_SMEM_BYTES, s, seeds,
-               polys,
-               c.dmods(), (uint32_t)c.L, (uint32_t)c.logn);
+    launch_blocks<k::seed_expand_kernel>("seed_expand", npolys, k::SEED_THREADS, k::SEED_SMEM_BYTES, s, seeds, polys, c.dmods(),
+                                         (uint32_t)c.L, (uint32_t)c.logn);
 }
 
 // ----------------------------------------------------------------------- rq::Scaler ----
@@ -1332,7 +1365,6 @@ inline void launch_scale(const Scaler &sc, const u64 *in, u64 in_stride, u64 *ou
     const Ctx &f = *sc.from, &t = *sc.to;
     const u64 total = (u64)npolys * f.n;
     if (!total) return;
-    const dim3 grid(blocks_for(total, EW_THREADS)), block(EW_THREADS);
     // profiler label: basis extension (more output rows than input) vs down-scaling
     const char *label = t.L > f.L ? "scale_extend" : "scale_down";
     // PLAIN instances carry no w / v_hi code: factor-one scalers whose v fits one word (every basis extension of BFV)
@@ -1342,8 +1374,8 @@ inline void launch_scale(const Scaler &sc, const u64 *in, u64 in_stride, u64 *ou
     with_scale_nf(f.L, ScaleNFs{}, [&](auto nf) {   // (the same NF scaler_upload padded the tables to)
         constexpr int NF = decltype(nf)::value;
         auto launch = [&](auto kernel) {
-            launch_k<decltype(kernel)::value>(label, grid, block, 0, s, in, out, in_stride, out_stride, sc.dev, t.dmods(),
-                                              (uint32_t)f.logn, total, asc);
+            launch_ew<decltype(kernel)::value>(label, total, s, in, out, in_stride, out_stride, sc.dev, t.dmods(), (uint32_t)f.logn,
+                                               total, asc);
         };
         if (plain) launch(kernel_c<k::scale_kernel<NF, true>>{});
         else if (sc.dev.wide_w) launch(kernel_c<k::scale_kernel<NF, false, true>>{});   // the reference's bit tests on an out-of-range t, to the letter
@@ -1360,20 +1392,13 @@ inline void scale_polys(const Scaler &sc, const u64 *in, u64 *out, size_t npolys
     f.need_device();
     if (!npolys) return;
     const u64 in_stride = (u64)f.L * f.n, out_stride = (u64)t.L * t.n;
-    if (sc.ncommon > 0 && copy_common) {
-        const u64 per = (u64)sc.ncommon * f.n, total = per * npolys;
-        FHE_LAUNCH("copy_rows", k::copy_rows_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s, in,
-                   out, in_stride, out_stride, per, total);
-    }
+    if (sc.ncommon > 0 && copy_common) copy_rows(in, in_stride, out, out_stride, (u64)sc.ncommon * f.n, npolys, s);
     if (sc.ncommon >= t.L) return;
     if (repr_is_ntt) {
         WsGuard pb(npolys * in_stride * sizeof(u64), s);
         launch_ntt(f, true, in, pb.u(), full_map(f, f.L), npolys, s);
         launch_scale(sc, pb.u(), in_stride, out, out_stride, npolys, s);
-        k::RowMap m = full_map(t, t.L);
-        m.rows = (uint32_t)(t.L - sc.ncommon);
-        m.row_begin = (uint32_t)sc.ncommon;
-        launch_ntt(t, false, out, out, m, npolys, s);
+        launch_ntt(t, false, out, out, new_rows_map(t, sc.ncommon), npolys, s);
     } else {
         launch_scale(sc, in, in_stride, out, out_stride, npolys, s);
     }
@@ -1389,12 +1414,9 @@ inline void scale_polys_pair(const Scaler &sc, const u64 *in0, const u64 *in1, u
     f.need_device();
     if (!npolys) return;
     const u64 in_stride = (u64)f.L * f.n, out_stride = (u64)t.L * t.n;
-    if (sc.ncommon > 0 && copy_common) {
-        const u64 per = (u64)sc.ncommon * f.n, total = per * npolys;
+    if (sc.ncommon > 0 && copy_common)
         for (int h = 0; h < 2; h++)
-            FHE_LAUNCH("copy_rows", k::copy_rows_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
-                       h ? in1 : in0, out + (u64)h * npolys * out_stride, in_stride, out_stride, per, total);
-    }
+            copy_rows(h ? in1 : in0, in_stride, out + (u64)h * npolys * out_stride, out_stride, (u64)sc.ncommon * f.n, npolys, s);
     if (sc.ncommon >= t.L) return;
     WsGuard pb(2 * npolys * in_stride * sizeof(u64), s);
     k::RowMap mi = full_map(f, f.L);
@@ -1402,10 +1424,7 @@ inline void scale_polys_pair(const Scaler &sc, const u64 *in0, const u64 *in1, u
     mi.split = (uint32_t)npolys;
     launch_ntt(f, true, in0, pb.u(), mi, 2 * npolys, s);
     launch_scale(sc, pb.u(), in_stride, out, out_stride, 2 * npolys, s);
-    k::RowMap m = full_map(t, t.L);
-    m.rows = (uint32_t)(t.L - sc.ncommon);
-    m.row_begin = (uint32_t)sc.ncommon;
-    launch_ntt(t, false, out, out, m, 2 * npolys, s);
+    launch_ntt(t, false, out, out, new_rows_map(t, sc.ncommon), 2 * npolys, s);
 }
 
 // Poly::<PowerBasis>::switch_down (M/rq/mod.rs:433-492) on npolys polynomials.
@@ -1415,8 +1434,8 @@ inline void switch_down_polys(const Ctx &c, const u64 *in, u64 in_stride, u64 *o
     require(c.next != nullptr, E_NO_MORE_CONTEXT, "NoMoreContext");
     const u64 total = (u64)npolys * c.n;
     if (!total) return;
-    FHE_LAUNCH("switch_down", k::switch_down_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s, in,
-               out, in_stride, out_stride, c.dmods(), c.d_inv_last.p, (uint32_t)c.L, (uint32_t)c.logn, total);
+    launch_ew<k::switch_down_kernel>("switch_down", total, s, in, out, in_stride, out_stride, c.dmods(), c.d_inv_last.p,
+                                     (uint32_t)c.L, (uint32_t)c.logn, total);
 }
 
 inline void substitute_polys(const Ctx &c, size_t exponent, const u64 *in, u64 *out, size_t npolys, bool ntt,
@@ -1427,8 +1446,8 @@ inline void substitute_polys(const Ctx &c, size_t exponent, const u64 *in, u64 *
     const u64 total = (u64)npolys * c.L * c.n;
     if (!total) return;
     const u64 stride = (u64)c.L * c.n;
-    FHE_LAUNCH("substitute", k::substitute_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s, in,
-               out, stride, stride, c.dmods(), (uint32_t)c.L, (uint32_t)c.logn, (uint32_t)e, ntt ? 1u : 0u, total);
+    launch_ew<k::substitute_kernel>("substitute", total, s, in, out, stride, stride, c.dmods(), (uint32_t)c.L, (uint32_t)c.logn,
+                                    (uint32_t)e, ntt ? 1u : 0u, total);
 }
 
 // ------------------------------------------------------------------ KeySwitchingKey ----
@@ -1560,6 +1579,11 @@ inline void ksk_alloc(Ksk &k_) {
     }
 }
 
+// The two instance rules every form of the key switch reads.  narrow: key moduli below 2^60, the transform runs without
+// most conditional subtractions (fwd_butterfly_narrow).  rns: residue-row digits of same-width moduli (lift_mode 1).
+inline bool ks_narrow(const Ctx &kc) { return !FHE_LAB_FLAG("NO_NARROW") && kc.below_2p60(0, kc.L); }
+inline bool ks_rns(const Ksk &k_) { return k_.digit_arg() == (1u << 8); }
+
 template <int LOGN>
 inline void launch_ks_fused(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0, u64 *o1, u64 out_stride,
                             const u64 *a0, const u64 *a1, u64 a_stride, size_t npolys, hipStream_t s,
@@ -1569,8 +1593,7 @@ inline void launch_ks_fused(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0, 
     if (!gal && lab_try_ks_pair<LOGN>(k_, p, p_stride, o0, o1, out_stride, a0, a1, a_stride, npolys, s)) return;   // lab/lab_engine.hpp
 #endif
     const size_t lds = (k::lds_words(1u << LOGN) + (k::ks_acc1_in_lds_c(LOGN) ? (size_t)1 << LOGN : 0)) * sizeof(u64);
-    // key moduli below 2^60: the transform runs without most conditional subtractions (fwd_butterfly_narrow)
-    const bool narrow = !FHE_LAB_FLAG("NO_NARROW") && kc.below_2p60(0, kc.L);
+    const bool narrow = ks_narrow(kc);
     // N = 16384 (ks_fused_kernel's GM): radix-8 while the twiddles are scalar, radix-4 after (GM_MIXED).  Lab builds:
     // FHE_LAB_KS14_PLAN = 8 radix-8 passes throughout (24 VGPRs spilled), 4 radix-4 passes throughout.
     static const int plan14 = FHE_LAB_INT("KS14_PLAN", 0);
@@ -1578,18 +1601,18 @@ inline void launch_ks_fused(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0, 
     // CU, each prefetching its next item's first row across its epilogue (lab builds, FHE_LAB_KS_PERSIST=0: one
     // workgroup per item)
     static const int ks_persist = FHE_LAB_INT("KS_PERSIST", 1);
-    unsigned ks_grid = (unsigned)(npolys * kc.L);
+    const uint32_t items = grid_x(npolys * kc.L, "key switch");
+    unsigned ks_grid = items;
 #if defined(FHE_HOST_EMULATION)
     constexpr bool ks_persist_size = true;   // (every size, so that the emulated suite walks the item loop)
 #else
     constexpr bool ks_persist_size = LOGN == 13 || (FHE_KS_PERSIST14 && LOGN == 14);
 #endif
-    if (ks_persist_size && ks_persist > 0) ks_grid = std::min<unsigned>(ks_grid, (unsigned)(device_cus(kc.device) * ks_persist));
+    if (ks_persist_size && ks_persist > 0) ks_grid = std::min<unsigned>(items, device_cus(kc.device) * ks_persist);
     // RNS instances (N = 4096, 8192): residue-row digits of same-width moduli, see the kernel.  (Not at N = 16384: in
     // round 3 that instance spilled 52 B; it no longer does, and measured again at C3 in round 4 it changes nothing --
     // relinearise of 512: 4.09 / 4.18 / 4.18 ms against 4.17 / 4.14 / 4.13, profiles/r04_ks14_rns_ab.jsonl.)
-    const bool rns = (LOGN == 12 || LOGN == 13) && k_.digit_arg() == (1u << 8);
-    const uint32_t items = (uint32_t)(npolys * kc.L);
+    const bool rns = (LOGN == 12 || LOGN == 13) && ks_rns(k_);
     const size_t lds_tile = k::lds_words(1u << LOGN) * sizeof(u64);   // (tile-only LDS: both accumulator sets in registers)
     // one launch of ks_fused_kernel; the F64 instances read the key's F64 words and the F64 tables
     auto launch = [&](const char *name, auto kernel, unsigned grid, int threads, size_t lds_k, bool f64) {
@@ -1657,7 +1680,7 @@ inline void launch_ks_fused(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0, 
         // FHE_LAB_KS14_T512 = 1: 512 threads x 32 coefficients, 256 VGPRs (two waves per SIMD), both accumulator sets in
         // registers, radix-16 passes (GM = 4), the RNS loader; = 2: the same with radix-8 passes
         static const int t512 = FHE_LAB_INT("KS14_T512", 0);
-        if (t512 && !gal && k_.digit_arg() == (1u << 8)) {
+        if (t512 && !gal && ks_rns(k_)) {
             with_bool(narrow, [&](auto nw) {
                 with_bool(t512 == 2, [&](auto radix8) {
                     launch("key_switch_fused",
@@ -1770,10 +1793,10 @@ inline void launch_ks_ntt(const Ksk &k_, bool narrow, bool rns, unsigned grid, h
     u64 *const erows = with_extra ? extra->rows : nullptr;
     const u64 estride = with_extra ? extra->poly_stride : 0;
     const uint32_t enr = with_extra ? (uint32_t)extra->nrows : 1u;
-    const unsigned egrid = with_extra ? (unsigned)(extra->npolys * extra->nrows) : 0u;
+    const size_t egrid = with_extra ? extra->npolys * extra->nrows : 0;
     auto launch = [&](const char *name, auto kernel, const k::u64x2 *tw) {
-        launch_tile<decltype(kernel)::value>(name, LOGM, grid + egrid, s, p, p_stride, w, kc.dmods(), tw, (uint32_t)k_.ndigits,
-                                             j0, jg, k_.digit_arg(), skip_own, erows, estride, enr, (uint32_t)grid);
+        launch_tile<decltype(kernel)::value>(name, LOGM, grid + egrid, s, p, p_stride, w, kc.dmods(), tw, (uint32_t)k_.ndigits, j0,
+                                             jg, k_.digit_arg(), skip_own, erows, estride, enr, (uint32_t)grid);
     };
     // Round 6: RNS digits under key moduli that are all below 2^50 -> the F64 stage A (whole-row tiles of 4096 ... 16384
     // points; W in canonical words, so stage B is unchanged)
@@ -1815,8 +1838,8 @@ inline KsGeometry ks_unfused_geometry(const Ksk &k_, size_t items, size_t budget
                                       (sub14_small && 2 * items * granule * nd * Lk <= (size_t)device_cus(kc.device)));
     g.logm = logn > 14 ? 13 : sub14 ? 13 : logn;
     g.g0 = logn - g.logm;
-    g.narrow = !FHE_LAB_FLAG("NO_NARROW") && kc.below_2p60(0, kc.L);
-    g.rns = k_.digit_arg() == (1u << 8);
+    g.narrow = ks_narrow(kc);
+    g.rns = ks_rns(k_);
     if (!budget) budget = KS_W_BUDGET_DEFAULT;
     const size_t row_bytes = granule * kc.n * sizeof(u64);
     size_t pc = items, jg = Lk;
@@ -1833,7 +1856,7 @@ inline KsGeometry ks_unfused_geometry(const Ksk &k_, size_t items, size_t budget
 // Stage A of one (chunk, group): `rows` polynomials (items x granule) from p, key moduli [j0, j0 + njg), into w.
 inline void launch_ks_stage_a(const Ksk &k_, const KsGeometry &g, size_t rows, size_t j0, size_t njg, hipStream_t s, const u64 *p,
                               u64 p_stride, u64 *w, uint32_t skip_own, const KsExtraFwd *ride = nullptr) {
-    const unsigned grid_a = (unsigned)((rows * k_.ndigits * njg) << g.g0);
+    const unsigned grid_a = grid_x((rows * k_.ndigits * njg) << g.g0, "unfused key switch");
     auto stage_a = [&](auto lm, auto g0, const KsExtraFwd *ex) {
         launch_ks_ntt<decltype(lm)::value, decltype(g0)::value>(k_, g.narrow, g.rns, grid_a, s, p, p_stride, w, (uint32_t)j0,
                                                                 (uint32_t)njg, skip_own, ex);
@@ -1847,10 +1870,12 @@ inline void launch_ks_stage_a(const Ksk &k_, const KsGeometry &g, size_t rows, s
 // Blocks of a stage B (kernels_ksmac.hpp: KsMacAt) over njg key moduli x nb polynomials or ciphertexts x `m` of whatever
 // else the kernel's grid runs over: key ranges in eights.
 inline unsigned ks_grid_b(const Ctx &kc, size_t njg, size_t nb, size_t m = 1, const char *what = "unfused key switch") {
-    const size_t grid_b = (((njg * k::ks_mac_chunks_per_row(kc.n)) + 7) / 8) * nb * m * 8;
-    if (grid_b > 0x7fffffffu)   // (as an `unsigned` it would wrap)
-        throw StatusError(E_ARG, std::string(what) + ": the launch exceeds the grid limit; lower the W budget");
-    return (unsigned)grid_b;
+    return grid_x((((njg * k::ks_mac_chunks_per_row(kc.n)) + 7) / 8) * nb * m * 8, what, "; lower the W budget");
+}
+// Extra residue rows (KsExtraFwd) that do not ride on a stage-A launch: their own forward transform, in place
+inline void ks_extra_forward(const Ctx &kc, const KsExtraFwd &extra, hipStream_t s) {
+    const k::RowMap m = strided_map(kc, extra.nrows, extra.poly_stride, extra.poly_stride);
+    launch_ntt(kc, false, extra.rows, extra.rows, m, extra.npolys, s);
 }
 inline unsigned hoist_grid_b(const Ctx &kc, size_t njg, size_t nb, size_t m) { return ks_grid_b(kc, njg, nb, m, "hoisted rotations"); }
 inline void key_switch_polys_unfused(const Ksk &k_, int mode, const u64 *p, u64 p_stride, u64 *o0, u64 *o1,
@@ -1869,11 +1894,7 @@ inline void key_switch_polys_unfused(const Ksk &k_, int mode, const u64 *p, u64 
     // the extra rows ride on the stage-A launch only when there is exactly one (whole-row tiles, one chunk of polynomials,
     // one group of key moduli); otherwise they get their own forward transform first, as before
     const bool merge_extra = extra != nullptr && g.g0 == 0 && g.logm == logn && g.pc == npolys && g.jg == Lk;
-    if (extra != nullptr && !merge_extra) {
-        k::RowMap m = full_map(kc, extra->nrows);
-        m.src_poly_stride = m.dst_poly_stride = extra->poly_stride;
-        launch_ntt(kc, false, extra->rows, extra->rows, m, extra->npolys, s);
-    }
+    if (extra != nullptr && !merge_extra) ks_extra_forward(kc, *extra, s);
     const KsExtraFwd *ride = merge_extra ? extra : nullptr;
     for (size_t b0 = 0; b0 < npolys; b0 += g.pc) {
         const size_t nb = std::min(g.pc, npolys - b0);
@@ -1954,11 +1975,7 @@ inline void key_switch_polys(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0,
             return;
         }
     }
-    if (extra != nullptr && extra->rows != nullptr) {   // (a fused launch: the extra rows' transform is its own launch)
-        k::RowMap m = full_map(kc, extra->nrows);
-        m.src_poly_stride = m.dst_poly_stride = extra->poly_stride;
-        launch_ntt(kc, false, extra->rows, extra->rows, m, extra->npolys, s);
-    }
+    if (extra != nullptr && extra->rows != nullptr) ks_extra_forward(kc, *extra, s);   // (a fused launch: their transform is its own)
     // N = 16384: whole-row kernel (1024 threads x 16 coefficients, 24 VGPRs spilled) or two 8192-point sub-blocks
     // with the first stage folded into the loader (FHE_KS_SPLIT14=1)
     static const bool split14 = FHE_LAB_INT("KS_SPLIT14", 0) != 0;
@@ -1973,7 +1990,7 @@ inline void key_switch_polys(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0,
         return;
     }
     // Rows larger than LDS (N >= 32768): one workgroup per part of a row, the first stages folded into its loader.
-    const bool narrow = !FHE_LAB_FLAG("NO_NARROW") && kc.below_2p60(0, kc.L);
+    const bool narrow = ks_narrow(kc);
     // N = 32768 / 65536 as two / four 16384-point parts on the N = 16384 kernel (one / two folded stages, knobs.hpp
     // FHE_KS_HALF15: 1 the generic loader, 2 the RNS loader where the key's digits are residue rows) -- 15 % ahead of the
     // 8192-point sub-blocks below once a launch fills the device (profiles/r04_ks_half15_ab.txt).  A launch whose
@@ -1987,8 +2004,8 @@ inline void key_switch_polys(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0,
     const bool parts16k = half15 && ks_mode != KS_FUSED_SUB && (ks_mode == KS_FUSED || !fits_at_once);
     if ((kc.logn == 15 || kc.logn == 16) && parts16k) {
         const size_t lds_ = k::lds_words(1u << 14) * sizeof(u64);
-        const unsigned grid = (unsigned)((npolys * kc.L) << (kc.logn - 14));
-        const bool rns = half15 == 2 && k_.digit_arg() == (1u << 8);
+        const unsigned grid = grid_x((npolys * kc.L) << (kc.logn - 14), "key switch");
+        const bool rns = half15 == 2 && ks_rns(k_);
         with_bool(kc.logn == 15, [&](auto one) {
             with_bool(narrow, [&](auto nw) {
                 with_bool(rns, [&](auto r) {
@@ -2009,9 +2026,9 @@ inline void key_switch_polys(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0,
         constexpr int G0 = decltype(g0)::value, LM = decltype(lm)::value;
         const size_t lds_ = (k::lds_words(1u << LM) + ((size_t)1 << LM)) * sizeof(u64);
         with_bool(narrow, [&](auto nw) {
-            with_bool(k_.digit_arg() == (1u << 8), [&](auto r) {   // RNS instance: residue-row digits of same-width moduli
-                launch_k<k::ks_fused_split_kernel<G0, LM, decltype(nw)::value, decltype(r)::value>>(
-                    "key_switch_fused_sub", dim3((unsigned)((npolys * kc.L) << G0)), dim3((1u << LM) / 8), lds_, s, p, p_stride, o0,
+            with_bool(ks_rns(k_), [&](auto r) {
+                launch_blocks<k::ks_fused_split_kernel<G0, LM, decltype(nw)::value, decltype(r)::value>>(
+                    "key_switch_fused_sub", (npolys * kc.L) << G0, (1u << LM) / 8, lds_, s, p, p_stride, o0,
                     o1, out_stride, a0, a1, a_stride, k_.c0.p, k_.c0s.p, k_.c1.p, k_.c1s.p, kc.dmods(), kc.dtw(),
                     (uint32_t)k_.ndigits, (uint32_t)kc.L, k_.digit_arg(), xhat, xhat_stride, gal);
             });
@@ -2034,9 +2051,7 @@ inline void switch_down_to_pb(const Ctx &from, size_t iters, const u64 *in, u64 
     require(from.at_level(iters) != nullptr, E_NO_MORE_CONTEXT, "NoMoreContext");
     if (!npolys) return;
     if (iters == 0) {
-        const u64 per = (u64)from.L * from.n, total = per * npolys;
-        FHE_LAUNCH("copy_rows", k::copy_rows_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s, in, out,
-                   in_stride, out_stride, per, total);
+        copy_rows(in, in_stride, out, out_stride, (u64)from.L * from.n, npolys, s);
         return;
     }
     if (iters == 1) {
@@ -2092,19 +2107,16 @@ inline void key_switch_add(const Ksk &k_, const u64 *p, u64 p_stride, const u64 
     switch_down_to_ntt(kc, (size_t)iters, r0.u(), d0.u(), npolys, s);
     switch_down_to_ntt(kc, (size_t)iters, r1.u(), d1.u(), npolys, s);
     // out = a + d  (strided copy of a -- or of d when there is no addend -- then add)
-    const u64 per = cstride, total = per * npolys;
     struct {
         const u64 *a, *d;
         u64 *o;
     } jobs[2] = {{a0, d0.u(), out0}, {a1, d1.u(), out1}};
     for (auto &jb : jobs) {
         if (jb.a) {
-            FHE_LAUNCH("copy_rows", k::copy_rows_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
-                       jb.a, jb.o, a_stride, out_stride, per, total);
+            copy_rows(jb.a, a_stride, jb.o, out_stride, cstride, npolys, s);
             for (size_t i = 0; i < npolys; i++) ew_op(cc, jb.o + i * out_stride, jb.d + i * cstride, 1, k::EW_ADD, s);
         } else {
-            FHE_LAUNCH("copy_rows", k::copy_rows_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
-                       jb.d, jb.o, cstride, out_stride, per, total);
+            copy_rows(jb.d, cstride, jb.o, out_stride, cstride, npolys, s);
         }
     }
 }
@@ -2117,19 +2129,14 @@ inline void dot_product_scalar(const Ctx &c, size_t nparts, size_t count, const 
     require(count > 0, E_EMPTY_DOT, "EmptyDotProduct: no operands");
     if (!batch || !nparts) return;
     const u64 pl = (u64)c.L * c.n;
-    require(batch <= 65535 && nparts <= 65535, E_ARG, "dot product: batch / parts exceed the grid limits");
+    require(batch <= GRID_YZ_MAX && nparts <= GRID_YZ_MAX, E_ARG, "dot product: batch / parts exceed the grid limits");
     const u64 cstride = cts_shared ? (u64)0 : (u64)count * nparts * pl, pstride = pts_shared ? (u64)0 : (u64)count * pl;
-    const dim3 block(EW_THREADS);
-    if (nparts == 1) {
-        FHE_LAUNCH("dot_product", (k::dot_kernel<1>), dim3(blocks_for(pl / 2, EW_THREADS), 1, (unsigned)batch), block, 0, s,
-                   cts, cstride, pts, pstride, out, c.dmods(), c.dpow2(), (uint32_t)nparts, (uint32_t)count,
-                   (uint32_t)c.logn, pl);
-    } else {  // two parts per lane (a ciphertext), further parts in extra grid rows
-        FHE_LAUNCH("dot_product", (k::dot_kernel<2>), dim3(blocks_for(pl / 2, EW_THREADS), (unsigned)((nparts + 1) / 2),
-                                                          (unsigned)batch),
-                   block, 0, s, cts, cstride, pts, pstride, out, c.dmods(), c.dpow2(), (uint32_t)nparts, (uint32_t)count,
-                   (uint32_t)c.logn, pl);
-    }
+    auto launch = [&](auto kernel, size_t y) {
+        launch_rows<decltype(kernel)::value>("dot_product", pl / 2, y, batch, s, cts, cstride, pts, pstride, out, c.dmods(),
+                                             c.dpow2(), (uint32_t)nparts, (uint32_t)count, (uint32_t)c.logn, pl);
+    };
+    if (nparts == 1) launch(kernel_c<k::dot_kernel<1>>{}, 1);
+    else launch(kernel_c<k::dot_kernel<2>>{}, (nparts + 1) / 2);   // (two parts per lane, further parts in extra grid rows)
 }
 
 // `Ciphertext * Plaintext` (F/bfv/ops/mod.rs:229-257)
@@ -2138,13 +2145,12 @@ inline void mul_plain(const Ctx &c, size_t nparts, const u64 *ct, const u64 *pt,
     c.need_device();
     if (!batch || !nparts) return;
     const u64 pl = (u64)c.L * c.n;
-    require(batch <= 65535 && nparts <= 65535, E_ARG, "mul_plain: batch / parts exceed the grid limits");
+    require(batch <= GRID_YZ_MAX && nparts <= GRID_YZ_MAX, E_ARG, "mul_plain: batch / parts exceed the grid limits");
     // (the kernel moves 16 bytes per lane: every device allocator hands out 256-byte aligned blocks and rows are whole
     // multiples of 64 bytes, so only a pointer into the middle of a coefficient pair can fail this)
     require((((uintptr_t)ct | (uintptr_t)pt | (uintptr_t)out) & 15) == 0, E_ARG, "mul_plain: buffers must be 16-byte aligned");
-    FHE_LAUNCH("mul_plain", k::mul_plain_kernel, dim3(blocks_for(pl / 2, EW_THREADS), 1, (unsigned)batch),
-               dim3(EW_THREADS), 0, s, ct, pt, pt_shared ? (u64)0 : pl, out, c.dmods(), (uint32_t)nparts,
-               (uint32_t)c.logn, pl);
+    launch_rows<k::mul_plain_kernel>("mul_plain", pl / 2, 1, batch, s, ct, pt, pt_shared ? (u64)0 : pl, out, c.dmods(),
+                                     (uint32_t)nparts, (uint32_t)c.logn, pl);
 }
 
 // GaloisKey::relinearize (F/bfv/keys/galois_key.rs:63-86): ct, out [batch][2][L][N] Ntt
@@ -2166,9 +2172,7 @@ inline void galois_apply(const Ksk &ks, size_t exponent, const u64 *ct, u64 *out
     const bool overlap = out < ct + batch * 2 * PL && ct < out + batch * 2 * PL;
     if (cc.logn >= 12 && ks.ksk_ctx->niterations_to(cc) == 0 && !overlap && !FHE_LAB_FLAG("NO_GALOIS_FOLD")) {
         WsGuard c2(batch * PL * sizeof(u64), s);
-        k::RowMap m = full_map(cc, cc.L);
-        m.src_poly_stride = 2 * PL;
-        m.dst_poly_stride = PL;
+        k::RowMap m = strided_map(cc, cc.L, 2 * PL, PL);
         m.subst_exp = (uint32_t)e;
         launch_ntt(cc, true, ct + PL, c2.u(), m, batch, s);
         key_switch_add(ks, c2.u(), PL, ct, nullptr, 2 * PL, out, out + PL, 2 * PL, batch, s, ct + PL, 2 * PL, (uint32_t)e,
@@ -2178,10 +2182,7 @@ inline void galois_apply(const Ksk &ks, size_t exponent, const u64 *ct, u64 *out
     // substitute both parts at once: sub [b][2][L][N]; c2 = PowerBasis(substitute(c1))
     WsGuard sub(batch * 2 * PL * sizeof(u64), s), c2(batch * PL * sizeof(u64), s);
     substitute_polys(cc, exponent, ct, sub.u(), batch * 2, true, s);
-    k::RowMap m = full_map(cc, cc.L);
-    m.src_poly_stride = 2 * PL;
-    m.dst_poly_stride = PL;
-    launch_ntt(cc, true, sub.u() + PL, c2.u(), m, batch, s);
+    launch_ntt(cc, true, sub.u() + PL, c2.u(), strided_map(cc, cc.L, 2 * PL, PL), batch, s);
     // out0 = key_switch0 + substitute(c0) ; out1 = key_switch1   (galois_key.rs:66-79)
     // (substitute(c1) in Ntt form doubles as the transforms of digit j under key modulus j)
     key_switch_add(ks, c2.u(), PL, sub.u(), nullptr, 2 * PL, out, out + PL, 2 * PL, batch, s, sub.u() + PL, 2 * PL, 0,
@@ -2225,10 +2226,7 @@ inline void hoist_each_w(const KskSet &set, const u64 *ct, size_t batch, hipStre
     const u64 PL = (u64)cc.L * kc.n;
     kc.need_device();
     WsGuard c2(batch * granule * PL * sizeof(u64), s);
-    k::RowMap m = full_map(cc, cc.L);
-    m.src_poly_stride = 2 * PL;
-    m.dst_poly_stride = PL;
-    launch_ntt(cc, true, ct + PL, c2.u(), m, batch * granule, s);
+    launch_ntt(cc, true, ct + PL, c2.u(), strided_map(cc, cc.L, 2 * PL, PL), batch * granule, s);
     const KsGeometry g = ks_unfused_geometry(k_, batch, set.w_budget.load(std::memory_order_relaxed), true, false, granule);
     WsGuard w(g.w_bytes, s);
     for (size_t b0 = 0; b0 < batch; b0 += g.pc) {
@@ -2495,12 +2493,18 @@ inline void check_plain_context(const Scaler &sc) {
     require(sc.to->L >= 1 && sc.to->moduli[0] == sc.from->moduli[0], E_PARAMETER_MISMATCH,
             "the plaintext context must start with the first ciphertext modulus");
 }
-// c0 + c1 s + c2 s^2 + ... in PowerBasis: ph [batch][L][N]
+// c0 + c1 s + c2 s^2 + ... in Ntt form: ph [batch][L][N]  (the ciphertext is the grid's second dimension)
+inline void launch_phase(const Ctx &cc, const u64 *s_ntt, const u64 *ct, size_t nparts, u64 *ph, size_t batch, hipStream_t s) {
+    const u64 PL = (u64)cc.L * cc.n;
+    for_groups(batch, GRID_YZ_MAX, [&](size_t b0, size_t nb) {
+        launch_rows<k::phase_kernel>("phase", PL, nb, 1, s, ct + b0 * nparts * PL, s_ntt, ph + b0 * PL, cc.dmods(),
+                                     (uint32_t)nparts, (uint32_t)cc.logn, PL);
+    });
+}
+// ... and in PowerBasis
 inline void phase_power_basis(const Ctx &cc, const u64 *s_ntt, const u64 *ct, size_t nparts, u64 *ph, size_t batch,
                               hipStream_t s) {
-    const u64 PL = (u64)cc.L * cc.n;
-    FHE_LAUNCH("phase", k::phase_kernel, dim3(blocks_for(PL, EW_THREADS), (unsigned)batch), dim3(EW_THREADS), 0, s, ct,
-               s_ntt, ph, cc.dmods(), (uint32_t)nparts, (uint32_t)cc.logn, PL);
+    launch_phase(cc, s_ntt, ct, nparts, ph, batch, s);
     launch_ntt(cc, true, ph, ph, full_map(cc, cc.L), batch, s);
 }
 // Scaler::scale (t / q) of the PowerBasis phase, then ((d_0 + t) mod q_0) mod t: out [batch][N]
@@ -2514,8 +2518,7 @@ inline void decrypt_tail(const Scaler &sc, u64 t, const u64 *ph, u64 *out, size_
     std::memcpy(&q0, &cc.root->mods[0], sizeof(DevMod));  // (host tables live on the chain's root)
     std::memcpy(&tmd, &tm, sizeof(DevMod));
     const u64 total = (u64)batch * cc.n;
-    FHE_LAUNCH("decrypt_tail", k::decrypt_tail_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s, d.u(),
-               (u64)pc.L * cc.n, out, q0, tmd, (uint32_t)cc.logn, total);
+    launch_ew<k::decrypt_tail_kernel>("decrypt_tail", total, s, d.u(), (u64)pc.L * cc.n, out, q0, tmd, (uint32_t)cc.logn, total);
 }
 inline void decrypt(const Scaler &sc, u64 t, const u64 *s_ntt, const u64 *ct, size_t nparts, u64 *out, size_t batch,
                     hipStream_t s) {
@@ -2558,16 +2561,20 @@ inline void expand(const Ksk *const *gks, size_t nlevels, const u64 *ct, u64 *ou
     // monomials -x^(N - 2^l) in Ntt form (the reference keeps them in the EvaluationKey, :467-474)
     WsGuard mono(level * PL * sizeof(u64), s), sub(((size_t)1 << (level - 1)) * batch * CT * sizeof(u64), s);
     FHE_HIP_CHECK(hipMemsetAsync(mono.u(), 0, level * PL * sizeof(u64), s));
-    FHE_LAUNCH("monomial", k::monomial_kernel, dim3(blocks_for(level * cc.L, 64)), dim3(64), 0, s, mono.u(), cc.dmods(),
-               (uint32_t)level, (uint32_t)cc.L, (uint32_t)cc.logn);
+    launch_ew<k::monomial_kernel, 64>("monomial", level * cc.L, s, mono.u(), cc.dmods(), (uint32_t)level, (uint32_t)cc.L,
+                                      (uint32_t)cc.logn);
     launch_ntt(cc, false, mono.u(), mono.u(), full_map(cc, cc.L), level, s);
     for (size_t l = 0; l < level; l++) {
         const size_t step = (size_t)1 << l, cnt = step * batch;
         const size_t nhigh = std::min(step, size - step) * batch;
         galois_apply(*gks[l], (cc.n >> l) + 1, out, sub.u(), cnt, s, keyed ? keyed + l : nullptr);
-        FHE_LAUNCH("expand_step", k::expand_step_kernel, dim3(blocks_for(PL, EW_THREADS), (unsigned)(cnt * 2)),
-                   dim3(EW_THREADS), 0, s, out, sub.u(), out + step * batch * CT, mono.u() + l * PL, cc.dmods(),
-                   (uint32_t)cc.logn, PL, (uint32_t)(nhigh * 2));
+        // (the polynomial is the grid's second dimension; a group's share of the 2 nhigh high polynomials: those after its first)
+        for_groups(cnt * 2, GRID_YZ_MAX, [&](size_t r0, size_t nr) {
+            const size_t high = std::min(nr, std::max(nhigh * 2, r0) - r0);
+            launch_rows<k::expand_step_kernel>("expand_step", PL, nr, 1, s, out + r0 * PL, sub.u() + r0 * PL,
+                                               out + step * batch * CT + r0 * PL, mono.u() + l * PL, cc.dmods(), (uint32_t)cc.logn,
+                                               PL, (uint32_t)high);
+        });
     }
 }
 
@@ -2853,9 +2860,8 @@ inline void bfv_tensor(const Mul &m, size_t la, size_t lb, const u64 *lhs, const
         const size_t nb = std::min(chunk, batch - b0);
         scale_polys(*m.ext_lhs, lhs + b0 * la * PL, ea.u(), nb * la, true, s);
         scale_polys(*m.ext_rhs, rhs + b0 * lb * PL, eb.u(), nb * lb, true, s);
-        FHE_LAUNCH("tensor_general", k::tensor_general_kernel, dim3(blocks_for(PK, EW_THREADS), (unsigned)lo, (unsigned)nb),
-                   dim3(EW_THREADS), 0, s, ea.u(), eb.u(), ten.u(), e.dmods(), (uint32_t)la, (uint32_t)lb,
-                   (uint32_t)e.logn, PK);
+        launch_rows<k::tensor_general_kernel>("tensor_general", PK, lo, nb, s, ea.u(), eb.u(), ten.u(), e.dmods(), (uint32_t)la,
+                                              (uint32_t)lb, (uint32_t)e.logn, PK);
         scale_polys(*m.down, ten.u(), out + b0 * lo * PL, nb * lo, true, s);
     }
 }
@@ -2973,13 +2979,12 @@ inline void bfv_mul(const Mul &m, const u64 *lhs, const u64 *rhs, u64 *out, size
                             (uint32_t)L, (uint32_t)L};
             launch_tensor_intt(e, ts, ten.u(), nb, s, dirflags);
         } else {
-            for (size_t t0 = 0; t0 < nb; t0 += 32768) {  // grid.y limit
-                const size_t tn = std::min<size_t>(32768, nb - t0);
-                FHE_LAUNCH("tensor", k::tensor_kernel, dim3(blocks_for(PK, EW_THREADS), (unsigned)tn), dim3(EW_THREADS), 0,
-                           s, extL + t0 * 2 * PK, (square ? extL : extR) + t0 * 2 * PK, skip_copy ? l + t0 * 2 * PL : nullptr,
-                           skip_copy ? r + t0 * 2 * PL : nullptr, ten.u() + t0 * PK, e.dmods(), (uint32_t)K, (uint32_t)L,
-                           (uint32_t)L, (uint32_t)e.logn, (u64)nb, 0u);
-            }
+            for_groups(nb, 32768, [&](size_t t0, size_t tn) {   // (the pair is the grid's second dimension)
+                launch_rows<k::tensor_kernel>("tensor", PK, tn, 1, s, extL + t0 * 2 * PK, (square ? extL : extR) + t0 * 2 * PK,
+                                              skip_copy ? l + t0 * 2 * PL : nullptr, skip_copy ? r + t0 * 2 * PL : nullptr,
+                                              ten.u() + t0 * PK, e.dmods(), (uint32_t)K, (uint32_t)L, (uint32_t)L,
+                                              (uint32_t)e.logn, (u64)nb, 0u);
+            });
         }
         if (!fused_tensor) launch_ntt(e, true, ten.u(), ten.u(), full_map(e, K), nb * 3, s);
         u64 *dst = m.mod_switch ? pre.u() : out + b0 * parts * PL;
@@ -3011,11 +3016,7 @@ inline void bfv_mul(const Mul &m, const u64 *lhs, const u64 *rhs, u64 *out, size
         } else {
             // no relinearisation: three Ntt parts, slot-major scratch -> [b][3][L][N]
             launch_ntt(b, false, d.u(), d.u(), back, nb * 3, s);
-            for (size_t slot = 0; slot < 3; slot++) {
-                const u64 total = (u64)nb * PL;
-                FHE_LAUNCH("copy_rows", k::copy_rows_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0,
-                           s, d.u() + slot * nb * PL, dst + slot * PL, PL, 3 * PL, PL, total);
-            }
+            for (size_t slot = 0; slot < 3; slot++) copy_rows(d.u() + slot * nb * PL, PL, dst + slot * PL, 3 * PL, PL, nb, s);
         }
         if (m.mod_switch) bfv_switch_down(b, parts, pre.u(), out + b0 * parts * (PL - N), nb, s);
     }
@@ -3121,7 +3122,7 @@ inline void encode(const Encoder &e, bool simd, bool scaled, size_t level, const
     if (simd && !e.tctx) throw StatusError(E_SIMD_UNAVAILABLE, "SimdUnavailable: the plaintext modulus admits no degree-N NTT");
     if (nvalues > e.n) throw StatusError(E_TOO_MANY_VALUES, "TooManyValues: more values than the degree");
     if (!batch) return;
-    require(batch * qc->L <= 0x7fffffffu, E_ARG, "encode: batch exceeds the grid limit");
+    grid_x(batch * qc->L, "encode");
     const bool f64_on = !f64_disabled();   // (read once per call: every transform of the call takes the same kind)
     const u64 qmt = e.q_mod_t[level];
     k::LiftSrc ls{values, nvalues, nvalues, e.tm, k::u64x2{qmt, shoup(qmt, e.t)}, scaled ? 1u : 0u,
@@ -3145,8 +3146,8 @@ inline void encode(const Encoder &e, bool simd, bool scaled, size_t level, const
             ls.mul_t = 0;
         } else {   // rows larger than one LDS tile: the gather as a pass of its own, then launch_ntt
             const u64 total = (u64)batch * e.n;
-            FHE_LAUNCH("encode_gather", k::perm_reduce_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
-                       values, (u64)nvalues, (u64)nvalues, e.d_inv_map.p, trows->u(), e.tm, (uint32_t)e.logn, total);
+            launch_ew<k::perm_reduce_kernel>("encode_gather", total, s, values, (u64)nvalues, (u64)nvalues, e.d_inv_map.p,
+                                             trows->u(), e.tm, (uint32_t)e.logn, total);
             launch_ntt(tc, true, trows->u(), trows->u(), full_map(tc, 1), batch, s);
         }
         ls.src = trows->u();
@@ -3159,8 +3160,7 @@ inline void encode(const Encoder &e, bool simd, bool scaled, size_t level, const
              ls, out, (uint32_t)qc->L, qc->dmods(), rows.tw());
     } else {
         const u64 total = (u64)batch * qc->L * e.n;
-        FHE_LAUNCH("encode_lift", k::encode_lift_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
-                   ls, out, (uint32_t)qc->L, qc->dmods(), (uint32_t)e.logn, total);
+        launch_ew<k::encode_lift_ew_kernel>("encode_lift", total, s, ls, out, (uint32_t)qc->L, qc->dmods(), (uint32_t)e.logn, total);
         launch_ntt(*qc, false, out, out, full_map(*qc, qc->L), batch, s);
     }
 }
@@ -3170,11 +3170,11 @@ inline void decode(const Encoder &e, bool simd, const u64 *coeffs, u64 *out, siz
     require(!e.big(), E_PARAMETER_MISMATCH, "the plaintext modulus exceeds 64 bits: the coefficients are limbs");
     if (simd && !e.tctx) throw StatusError(E_SIMD_UNAVAILABLE, "SimdUnavailable: the plaintext modulus admits no degree-N NTT");
     if (!batch) return;
-    require(batch <= 0x7fffffffu, E_ARG, "decode: batch exceeds the grid limit");
+    grid_x(batch, "decode");
     const u64 total = (u64)batch * e.n;
     if (!simd) {
-        FHE_LAUNCH("decode_poly", k::perm_reduce_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
-                   coeffs, (u64)e.n, (u64)e.n, (const uint32_t *)nullptr, out, e.tm, (uint32_t)e.logn, total);
+        launch_ew<k::perm_reduce_kernel>("decode_poly", total, s, coeffs, (u64)e.n, (u64)e.n, (const uint32_t *)nullptr, out, e.tm,
+                                         (uint32_t)e.logn, total);
         return;
     }
     const Ctx &tc = *e.tctx;
@@ -3187,11 +3187,11 @@ inline void decode(const Encoder &e, bool simd, const u64 *coeffs, u64 *out, siz
     }
     // rows larger than one LDS tile: reduce, launch_ntt, then the index map as a gather pass
     WsGuard tmp(total * sizeof(u64), s, true);
-    FHE_LAUNCH("decode_reduce", k::perm_reduce_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s, coeffs,
-               (u64)e.n, (u64)e.n, (const uint32_t *)nullptr, tmp.u(), e.tm, (uint32_t)e.logn, total);
+    launch_ew<k::perm_reduce_kernel>("decode_reduce", total, s, coeffs, (u64)e.n, (u64)e.n, (const uint32_t *)nullptr, tmp.u(),
+                                     e.tm, (uint32_t)e.logn, total);
     launch_ntt(tc, false, tmp.u(), tmp.u(), full_map(tc, 1), batch, s);
-    FHE_LAUNCH("decode_gather", k::perm_reduce_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
-               (const u64 *)tmp.u(), (u64)e.n, (u64)e.n, (const uint32_t *)e.d_map.p, out, e.tm, (uint32_t)e.logn, total);
+    launch_ew<k::perm_reduce_kernel>("decode_gather", total, s, (const u64 *)tmp.u(), (u64)e.n, (u64)e.n,
+                                     (const uint32_t *)e.d_map.p, out, e.tm, (uint32_t)e.logn, total);
 }
 
 // ------------------------------------------------------- plaintexts from packed bits ----
@@ -3208,11 +3208,12 @@ inline void launch_transcode(const void *in, bool in_bytes, size_t in_bits, u64 
                              bool out_bytes, size_t out_bits, u64 grp, u64 out_stride, size_t rows, hipStream_t s) {
     const u64 nout = transcode_count(in_bits, nin, out_bits);
     if (!rows || !nout) return;
-    const u64 bpr = (nout + EW_THREADS - 1) / EW_THREADS;
-    require(rows <= 0x7fffffffu && bpr * rows <= 0x7fffffffu, E_ARG, "transcode: batch exceeds the grid limit");
+    const u64 bpr = blocks_for(nout, EW_THREADS);
+    const u64 blocks = (u64)grid_x(rows, "transcode") * grid_x(bpr, "transcode");   // (each factor first: the product cannot wrap)
+    grid_x(blocks, "transcode");
     k::TranscodeIo io{in, out, total_in, in_stride, nin, nout, grp, out_stride, in_bytes ? 1u : 0u, (uint32_t)in_bits,
                       out_bytes ? 1u : 0u, (uint32_t)out_bits, (uint32_t)bpr};
-    FHE_LAUNCH("transcode", k::transcode_ew_kernel, dim3((unsigned)(bpr * rows)), dim3(EW_THREADS), 0, s, io);
+    launch_blocks<k::transcode_ew_kernel>("transcode", blocks, EW_THREADS, 0, s, io);
 }
 
 // fhe_util::transcode_from_bytes / transcode_to_bytes / transcode_bidirectional: rows [batch][nin] -> [batch][nout].
@@ -3253,7 +3254,7 @@ inline void encode_stream(const Encoder &e, bool scaled, size_t level, const voi
     const u64 nplain = bytes ? 1 : stream_plaintexts(e, in_bits, nseg, seg_len, nbits);
     if (!batch || !nplain) return;
     const u64 items = (u64)batch * nplain;
-    require(items * qc->L <= 0x7fffffffu, E_ARG, "encode: batch exceeds the grid limit");
+    grid_x(items * qc->L, "encode");
     const u64 qmt = e.q_mod_t[level];
     const k::u64x2 qm{qmt, shoup(qmt, e.t)};
     const k::u64x2 *delta = scaled ? e.d_delta[level]->p : nullptr;
@@ -3274,8 +3275,7 @@ inline void encode_stream(const Encoder &e, bool scaled, size_t level, const voi
     launch_transcode(src, bytes, in_bits, total, seg_len, seg_len, vals.p, false, nbits, nseg, per_item, batch * nseg, s);
     k::LiftSrc ls{vals.u(), e.n, e.n, e.tm, qm, scaled ? 1u : 0u, delta};
     const u64 all = items * qc->L * e.n;
-    FHE_LAUNCH("encode_lift", k::encode_lift_ew_kernel, dim3(blocks_for(all, EW_THREADS)), dim3(EW_THREADS), 0, s, ls, out,
-               (uint32_t)qc->L, qc->dmods(), (uint32_t)e.logn, all);
+    launch_ew<k::encode_lift_ew_kernel>("encode_lift", all, s, ls, out, (uint32_t)qc->L, qc->dmods(), (uint32_t)e.logn, all);
     launch_ntt(*qc, false, out, out, full_map(*qc, qc->L), items, s);
 }
 
@@ -3297,8 +3297,7 @@ inline size_t small_bytes(size_t count) { return (count + 15) & ~(size_t)15; }
 // pass of its own, then (to_ntt) launch_ntt; the callers' combine stages follow as element-wise passes.
 inline void small_lift(const Ctx &c, const int8_t *smp, u64 *x, size_t npolys, bool to_ntt, hipStream_t s) {
     const u64 total = (u64)npolys * c.L * c.n;
-    FHE_LAUNCH("small_lift", k::small_lift_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s, smp, x,
-               (uint32_t)c.L, c.dmods(), (uint32_t)c.logn, total);
+    launch_ew<k::small_lift_ew_kernel>("small_lift", total, s, smp, x, (uint32_t)c.L, c.dmods(), (uint32_t)c.logn, total);
     if (to_ntt) launch_ntt(c, false, x, x, full_map(c, c.L), npolys, s);
 }
 
@@ -3314,13 +3313,12 @@ struct GroupDraws {
         : smp(small_bytes(nb * kdraws * c.n), s, true) {
         const u64 ns = (u64)kdraws * c.n;
         const u64 wpd = cbd_words_per_draw(variance, c.n);
-        const dim3 grid(blocks_for(ns, k::CBD_THREADS), (unsigned)nb), block(k::CBD_THREADS);
-        if (word0)
-            FHE_LAUNCH("cbd_sample_at", k::cbd_sample_at_kernel, grid, block, k::CBD_AT_SMEM_BYTES, s, seeds, (int8_t *)smp.p,
-                       (uint32_t)variance, ns, (uint32_t)c.logn, wpd, word0);
+        if (word0)   // (the item is the grid's second dimension)
+            launch_rows<k::cbd_sample_at_kernel, k::CBD_THREADS, k::CBD_AT_SMEM_BYTES>(
+                "cbd_sample_at", ns, nb, 1, s, seeds, (int8_t *)smp.p, (uint32_t)variance, ns, (uint32_t)c.logn, wpd, word0);
         else
-            FHE_LAUNCH("cbd_sample", k::cbd_sample_kernel, grid, block, k::CBD_SMEM_BYTES, s, seeds, (int8_t *)smp.p,
-                       (uint32_t)variance, ns, (uint32_t)c.logn, wpd);
+            launch_rows<k::cbd_sample_kernel, k::CBD_THREADS, k::CBD_SMEM_BYTES>(
+                "cbd_sample", ns, nb, 1, s, seeds, (int8_t *)smp.p, (uint32_t)variance, ns, (uint32_t)c.logn, wpd);
         if (whole) return;
         xw = std::make_unique<WsGuard>(nb * kdraws * c.L * c.n * sizeof(u64), s, true);
         small_lift(c, e(), xw->u(), nb * kdraws, true, s);
@@ -3335,7 +3333,7 @@ inline void sample_small(const Ctx &c, size_t variance, const uint8_t *seeds, bo
     c.need_device();
     check_variance(variance);
     if (!batch) return;
-    require(batch <= 65535 && batch * c.L <= 0x7fffffffu, E_ARG, "sample_small: batch exceeds the grid limit");
+    require(batch <= GRID_YZ_MAX, E_ARG, "sample_small: batch exceeds the grid limit");
     const GroupDraws d(c, seeds, variance, 1, 0, batch, true, s);   // (larger rows: lifted into `out`, not into scratch)
     if (to_ntt && c.logn <= 14) {
         const RowLaunch rows(c, c.L, !f64_disabled());
@@ -3350,7 +3348,7 @@ inline void sample_small(const Ctx &c, size_t variance, const uint8_t *seeds, bo
 // Items per launch group of an encryption: the u64 scratch rows of one group (`rows_per_item` polynomials per item:
 // the seeded `a`, and for rows larger than one LDS tile the transformed samples) stay within `budget` bytes, and the
 // batch is split into groups of equal size (a small tail group would underfill the device).  `cap`: most items a launch takes.
-inline size_t encrypt_group(const Ctx &c, size_t rows_per_item, size_t batch, size_t budget, size_t cap = 65535) {
+inline size_t encrypt_group(const Ctx &c, size_t rows_per_item, size_t batch, size_t budget, size_t cap = GRID_YZ_MAX) {
     const size_t per = std::max<size_t>(1, rows_per_item) * c.L * c.n * sizeof(u64);
     const size_t most = std::max<size_t>(1, std::min<size_t>(cap, budget / per));
     const size_t groups = (batch + most - 1) / most;
@@ -3365,7 +3363,7 @@ inline void encrypt_sk(const Ctx &c, size_t variance, const u64 *s_ntt, const ui
     c.need_device();
     check_variance(variance);
     if (!batch) return;
-    require(batch * c.L <= 0x7fffffffu, E_ARG, "encrypt: batch exceeds the grid limit");
+    grid_x(batch * c.L, "encrypt");
     const bool whole = c.logn <= 14;
     const RowLaunch rows(c, c.L, !f64_disabled());   // (read once per call: every transform of the call takes the same kind)
     const u64 PL = (u64)c.L * c.n;
@@ -3387,9 +3385,8 @@ inline void encrypt_sk(const Ctx &c, size_t variance, const u64 *s_ntt, const ui
                         d.e(), (const u64 *)a.u(), s_ntt, ptb, pts, outb, (uint32_t)c.L, c.dmods(), rows.tw());
         // rows larger than one LDS tile: the epilogue as a pass of its own over the transformed samples
         const u64 total = (u64)nb * PL;
-        FHE_LAUNCH("encrypt_combine", k::encrypt_combine_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS),
-                   0, s, d.x(), (const u64 *)a.u(), s_ntt, ptb, pts, outb, (uint32_t)c.L, c.dmods(), (uint32_t)c.logn, 0u,
-                   total);
+        launch_ew<k::encrypt_combine_ew_kernel>("encrypt_combine", total, s, d.x(), (const u64 *)a.u(), s_ntt, ptb, pts, outb,
+                                                (uint32_t)c.L, c.dmods(), (uint32_t)c.logn, 0u, total);
     });
 }
 
@@ -3401,11 +3398,11 @@ inline void encrypt_pk(const Ctx &c, size_t variance, const u64 *pk, const uint8
     c.need_device();
     check_variance(variance);
     if (!batch) return;
-    require(batch * c.L <= 0x7fffffffu, E_ARG, "encrypt: batch exceeds the grid limit");
+    grid_x(batch * c.L, "encrypt");
     const bool whole = c.logn <= 14;
     const RowLaunch rows(c, c.L, !f64_disabled());
     const u64 PL = (u64)c.L * c.n;
-    const size_t group = whole ? 65535 : encrypt_group(c, 3, batch, (size_t)256 << 20);
+    const size_t group = whole ? GRID_YZ_MAX : encrypt_group(c, 3, batch, (size_t)256 << 20);
     for_groups(batch, group, [&](size_t b0, size_t nb) {
         const u64 *ptb = pt ? pt + (pt_shared ? 0 : b0 * PL) : nullptr;
         const u64 pts = pt_shared ? (u64)0 : PL;
@@ -3419,9 +3416,8 @@ inline void encrypt_pk(const Ctx &c, size_t variance, const u64 *pk, const uint8
             return;
         }
         const u64 total = (u64)nb * PL;
-        FHE_LAUNCH("encrypt_combine", k::encrypt_combine_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS),
-                   0, s, d.x(), (const u64 *)nullptr, pk, ptb, pts, outb, (uint32_t)c.L, c.dmods(), (uint32_t)c.logn, 1u,
-                   total);
+        launch_ew<k::encrypt_combine_ew_kernel>("encrypt_combine", total, s, d.x(), (const u64 *)nullptr, pk, ptb, pts, outb,
+                                                (uint32_t)c.L, c.dmods(), (uint32_t)c.logn, 1u, total);
     });
 }
 
@@ -3464,8 +3460,8 @@ struct KskCall {
         : kc(kc_), nd(nd_), Lk(kc_.L), PK((u64)nd_ * kc_.L * kc_.n), wf(ksk_f64_eligible(kc_, lb)), whole(kc_.logn <= 14),
           s(s_), cst((2 * Lk + nd * Lk + (checked ? 1 : 0)) * sizeof(u64), s_) {
         if (checked) FHE_HIP_CHECK(hipMemsetAsync(flag(), 0, sizeof(u64), s));
-        FHE_LAUNCH("ksk_consts", k::ksk_consts_kernel, dim3(blocks_for(nd * Lk, 64)), dim3(64), 0, s, kc.dmods(),
-                   (uint32_t)nd, (uint32_t)Lk, (uint32_t)lb, cst.u() + 2 * Lk, (k::u64x2 *)cst.p);
+        launch_ew<k::ksk_consts_kernel, 64>("ksk_consts", nd * Lk, s, kc.dmods(), (uint32_t)nd, (uint32_t)Lk, (uint32_t)lb,
+                                            cst.u() + 2 * Lk, (k::u64x2 *)cst.p);
     }
     const k::u64x2 *rq() const { return (const k::u64x2 *)cst.p; }
     const u64 *g() const { return cst.u() + 2 * Lk; }
@@ -3486,9 +3482,8 @@ struct KskCall {
     // and, unless check_only, the Shoup twins and F64 words.  Without check_only every word must be below its modulus.
     void twins(const k::KskOutTable &tab, size_t nb, uint32_t parts, uint32_t check_only) const {
         const u64 pairs = (u64)nb * PK / 2;
-        FHE_LAUNCH("ksk_twin", k::ksk_twin_ew_kernel, dim3(blocks_for(pairs, EW_THREADS)), dim3(EW_THREADS), 0, s, tab,
-                   parts, check_only, rq(), (uint32_t)nd, (uint32_t)Lk, (uint32_t)wf, kc.dmods(), (uint32_t)kc.logn, pairs,
-                   flag());
+        launch_ew<k::ksk_twin_ew_kernel>("ksk_twin", pairs, s, tab, parts, check_only, rq(), (uint32_t)nd, (uint32_t)Lk, (uint32_t)wf,
+                                         kc.dmods(), (uint32_t)kc.logn, pairs, flag());
     }
     // reads the flag word, waiting for `s`: a word >= q_j anywhere raised it (ksk_load_wire's one wait; ksk_finish's
     // callers wait once more before they return)
@@ -3522,13 +3517,13 @@ inline std::vector<std::unique_ptr<Ksk>> ksk_generate(const Ctx &ct, const Ctx &
     const bool whole = kk.whole;
     const RowLaunch rows(kc, Lk, !f64_disabled());   // (read once per call: every transform of the call takes the same kind)
     const size_t group = kk.group(nkeys);   // (the c1 scratch, and the transformed errors of larger rows)
-    require(group * nd * Lk <= 0x7fffffffu, E_ARG, "ksk_generate: a launch group exceeds the grid limit");
+    grid_x(group * nd * Lk, "ksk_generate");
     for_groups(nkeys, group, [&](size_t b0, size_t nb) {
         const k::KskOutTable tab = KskCall::table(&keys[b0], nb);
         WsGuard ds(nb * nd * 32, s), c1(nb * PK * sizeof(u64), s);
         const uint8_t *sd = seeds + b0 * 32;
-        FHE_LAUNCH("ksk_seeds", k::ksk_seeds_kernel, dim3(blocks_for(nb * nd, 64)), dim3(64), 0, s, sd,
-                   seeds_out ? seeds_out + b0 * 32 : nullptr, (uint8_t *)ds.p, (uint32_t)nd, (uint32_t)(nb * nd));
+        launch_ew<k::ksk_seeds_kernel, 64>("ksk_seeds", nb * nd, s, sd, seeds_out ? seeds_out + b0 * 32 : nullptr, (uint8_t *)ds.p,
+                                           (uint32_t)nd, (uint32_t)(nb * nd));
         const GroupDraws d(kc, sd, variance, nd, 4, nb, whole, s);   // the errors: nd draws per key, after K
         polys_from_seeds(kc, (const uint8_t *)ds.p, c1.u(), nb * nd, s);
         const u64 *fb = from_ntt + b0 * Lk * N;
@@ -3539,9 +3534,8 @@ inline std::vector<std::unique_ptr<Ksk>> ksk_generate(const Ctx &ct, const Ctx &
                         (uint32_t)kk.wf, kc.dmods(), rows.tw());
         // rows larger than one LDS tile: the epilogue as a pass of its own over the transformed errors
         const u64 total = (u64)nb * PK;
-        FHE_LAUNCH("ksk_combine", k::ksk_combine_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
-                   d.x(), (const u64 *)c1.u(), s_ntt, fb, kk.g(), kk.rq(), tab, (uint32_t)nd, (uint32_t)Lk, (uint32_t)kk.wf,
-                   kc.dmods(), (uint32_t)kc.logn, total);
+        launch_ew<k::ksk_combine_ew_kernel>("ksk_combine", total, s, d.x(), (const u64 *)c1.u(), s_ntt, fb, kk.g(), kk.rq(), tab,
+                                            (uint32_t)nd, (uint32_t)Lk, (uint32_t)kk.wf, kc.dmods(), (uint32_t)kc.logn, total);
     });
     return keys;
 }
@@ -3590,8 +3584,7 @@ inline void galois_from(const Ctx &ct, const Ctx &kc, const u64 *s_ntt, const si
         k::KgExps e{};
         for (size_t b = 0; b < nb; b++) e.e[b] = (uint32_t)(exponents[b0 + b] % (2 * ct.n));
         const u64 total = (u64)nb * pc;
-        FHE_LAUNCH("galois_from", k::galois_from_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
-                   s_ntt, dst + b0 * pc, e, (uint32_t)ct.L, (uint32_t)ct.logn, total);
+        launch_ew<k::galois_from_kernel>("galois_from", total, s, s_ntt, dst + b0 * pc, e, (uint32_t)ct.L, (uint32_t)ct.logn, total);
     });
     if (t) switch_up_ntt(ct, kc, t->u(), out, nkeys, s);
 }
@@ -3628,15 +3621,15 @@ inline std::vector<std::unique_ptr<Ksk>> ksk_load_wire(const Ctx &ct, const Ctx 
     // the word-granular loader: rows of >= 128 coefficients and 16-byte aligned byte pointers (see ksk_load_kernel)
     const bool words = N >= 128 && ((uintptr_t)c0b & 15) == 0 && ((uintptr_t)c1b & 15) == 0;
     const size_t group = kk.group(nkeys);
-    require(2 * group * nd * Lk <= 0x7fffffffu, E_ARG, "ksk_load_wire: a launch group exceeds the grid limit");
+    grid_x(2 * group * nd * Lk, "ksk_load_wire");
     for_groups(nkeys, group, [&](size_t b0, size_t nb) {
         const k::KskOutTable tab = KskCall::table(&keys[b0], nb);
         const uint8_t *b0p = c0b + b0 * nd * wb, *b1p = c1b ? c1b + b0 * nd * wb : nullptr;
         uint32_t ew_parts = whole ? 0u : 3u;   // what ksk_twin_ew_kernel still has to do for this group
         if (K) {
             WsGuard ds(nb * nd * 32, s);
-            FHE_LAUNCH("ksk_dseeds", k::ksk_dseeds_kernel, dim3(blocks_for(nb * nd, 64)), dim3(64), 0, s, K + b0 * 32,
-                       (uint8_t *)ds.p, (uint32_t)nd, (uint32_t)(nb * nd));
+            launch_ew<k::ksk_dseeds_kernel, 64>("ksk_dseeds", nb * nd, s, K + b0 * 32, (uint8_t *)ds.p, (uint32_t)nd,
+                                                (uint32_t)(nb * nd));
             for (size_t b = 0; b < nb; b++)
                 polys_from_seeds(kc, (const uint8_t *)ds.p + b * nd * 32, keys[b0 + b]->c1.p, nd, s);
             ew_parts |= 2u;
@@ -3703,7 +3696,7 @@ inline void mbfv_shares(const Ctx &c, size_t variance, const uint8_t *seeds, siz
     c.need_device();
     check_variance(variance);
     if (!batch) return;
-    require(batch * edraws * c.L <= 0x7fffffffu, E_ARG, "mbfv: batch exceeds the grid limit");
+    grid_x(batch * edraws * c.L, "mbfv");
     const bool whole = c.logn <= 14;
     const RowLaunch rows(c, c.L, !f64_disabled());   // (read once per call: every transform of the call takes the same kind)
     const u64 PL = (u64)c.L * c.n;
@@ -3732,8 +3725,8 @@ inline void mbfv_shares(const Ctx &c, size_t variance, const uint8_t *seeds, siz
             }
             // rows larger than one LDS tile: the epilogues as passes over the transformed draws
             const u64 total = (u64)nb * g.k * PL;
-            FHE_LAUNCH("mbfv_share", k::mbfv_share_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s,
-                       d.x(), g, (uint32_t)pt.form, outb, c.dmods(), (uint32_t)c.logn, total);
+            launch_ew<k::mbfv_share_ew_kernel>("mbfv_share", total, s, d.x(), g, (uint32_t)pt.form, outb, c.dmods(), (uint32_t)c.logn,
+                                               total);
         }
     });
 }
@@ -3777,9 +3770,8 @@ inline void mbfv_pks_share(const Ctx &c, size_t variance, const u64 *s_ntt, bool
     if (!batch) return;
     const u64 PL = (u64)c.L * c.n, total = (u64)batch * PL;
     WsGuard sc1(total * sizeof(u64), s, true);
-    FHE_LAUNCH("mbfv_mul", k::mbfv_mul_ew_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s, s_ntt,
-               mbfv_secret_stride(c, s_shared), ct + PL, ct_shared ? (u64)0 : 2 * PL, sc1.u(), (uint32_t)c.L, c.dmods(),
-               (uint32_t)c.logn, total);
+    launch_ew<k::mbfv_mul_ew_kernel>("mbfv_mul", total, s, s_ntt, mbfv_secret_stride(c, s_shared), ct + PL,
+                                     ct_shared ? (u64)0 : 2 * PL, sc1.u(), (uint32_t)c.L, c.dmods(), (uint32_t)c.logn, total);
     encrypt_pk(c, variance, pk, seeds, sc1.u(), false, out, batch, s);
 }
 
@@ -3797,8 +3789,7 @@ inline void mbfv_rlk_round1(const Ctx &c, size_t variance, const u64 *s_ntt, con
     WsGuard cst((2 * L + L * L) * sizeof(u64), s);
     k::u64x2 *rq = (k::u64x2 *)cst.p;
     u64 *g = cst.u() + 2 * L;
-    FHE_LAUNCH("ksk_consts", k::ksk_consts_kernel, dim3(blocks_for(L * L, 64)), dim3(64), 0, s, c.dmods(), (uint32_t)L,
-               (uint32_t)L, 0u, g, rq);
+    launch_ew<k::ksk_consts_kernel, 64>("ksk_consts", L * L, s, c.dmods(), (uint32_t)L, (uint32_t)L, 0u, g, rq);
     mbfv_shares(c, variance, seeds, 2 * L,
                 {{k::MBFV_AX_WY, mbfv_args(crp, 0, u_ntt, nullptr, s_ntt, g, st, 0, L, true), out_h0},
                  {k::MBFV_AX, mbfv_args(crp, 0, s_ntt, nullptr, nullptr, nullptr, st, L, L, false), out_h1}},
@@ -3833,11 +3824,11 @@ inline void mbfv_sum(const Ctx &c, const u64 *shares, size_t nshares, u64 share_
     require(((uintptr_t)shares | (uintptr_t)base | (uintptr_t)out) % 16 == 0, E_ARG, "mbfv: buffers must be 16-byte aligned");
     if (!npolys) return;
     const u64 PL = (u64)c.L * c.n;
-    require(PL / 2 <= 0x7fffffffu, E_ARG, "mbfv: polynomial exceeds the grid limit");
-    for_groups(npolys, 65535, [&](size_t j0, size_t nj) {   // (the polynomial is the grid's second dimension)
-        FHE_LAUNCH("mbfv_sum", k::mbfv_sum_kernel, dim3(blocks_for(PL / 2, EW_THREADS), (unsigned)nj), dim3(EW_THREADS), 0, s,
-                   shares + j0 * PL, (uint32_t)nshares, share_stride, base ? base + j0 * base_stride : nullptr, base_stride,
-                   out + j0 * PL, c.dmods(), (uint32_t)c.logn, (uint32_t)(PL / 2));
+    grid_x(PL / 2, "mbfv");   // (the kernel takes the pairs of a polynomial as a 32-bit count)
+    for_groups(npolys, GRID_YZ_MAX, [&](size_t j0, size_t nj) {   // (the polynomial is the grid's second dimension)
+        launch_rows<k::mbfv_sum_kernel>("mbfv_sum", PL / 2, nj, 1, s, shares + j0 * PL, (uint32_t)nshares, share_stride,
+                                        base ? base + j0 * base_stride : nullptr, base_stride, out + j0 * PL, c.dmods(),
+                                        (uint32_t)c.logn, (uint32_t)(PL / 2));
     });
 }
 
@@ -3866,11 +3857,10 @@ inline void add_plain(const Ctx &c, bool subtract, size_t nparts, const u64 *ct,
     c.need_device();
     require(nparts >= 1, E_ARG, "a ciphertext has at least one part");
     if (!batch) return;
-    require(batch <= 65535, E_ARG, "add_plain: batch exceeds the grid limit");
     const u64 pl = (u64)c.L * c.n;
-    FHE_LAUNCH("add_plain", k::add_plain_kernel, dim3(blocks_for(pl, EW_THREADS), (unsigned)batch), dim3(EW_THREADS), 0, s,
-               ct, pt, pt_shared ? (u64)0 : pl, out, c.dmods(), (uint32_t)nparts, (uint32_t)c.logn, pl,
-               subtract ? 1u : 0u, out != ct ? 1u : 0u);
+    // (the ciphertext is the grid's second dimension: a batch above GRID_YZ_MAX is refused)
+    launch_rows<k::add_plain_kernel>("add_plain", pl, batch, 1, s, ct, pt, pt_shared ? (u64)0 : pl, out, c.dmods(), (uint32_t)nparts,
+                                     (uint32_t)c.logn, pl, subtract ? 1u : 0u, out != ct ? 1u : 0u);
 }
 
 // --------------------------------------------------------------------- lift and noise ----
@@ -3913,15 +3903,14 @@ inline void launch_lift(const Ctx &c, const u64 *polys, const k::LiftSub &sub, u
                         size_t batch, hipStream_t s) {
     require(c.L <= (size_t)k::LIFT_LMAX, E_ARG, "lift: more moduli than the generic instance holds");
     const u64 nblk = blocks_for(c.n, k::LIFT_THREADS);
-    require(batch * nblk <= 0x7fffffffu, E_ARG, "lift: batch exceeds the grid limit");
+    const unsigned grid = grid_x(batch * nblk, "lift");
     const u64 *tab = lift_consts(c);
-    const dim3 grid((unsigned)(batch * nblk)), block(k::LIFT_THREADS);
     const size_t lds = BITS ? k::LIFT_SMEM_BYTES : 0;
     const char *name = BITS ? "centered_bits" : "lift";
     with_int_or_generic<1, LIFT_LC_MAX>(c.L, "lift: no moduli", [&](auto lc) {
-        launch_k<k::lift_kernel<decltype(lc)::value, BITS>>(name, grid, block, lds, s, polys, tab, sub, out, partial,
-                                                            (uint32_t)c.L, (uint32_t)w, (uint32_t)c.logn, (uint32_t)nblk,
-                                                            (uint32_t)batch);
+        launch_blocks<k::lift_kernel<decltype(lc)::value, BITS>>(name, grid, k::LIFT_THREADS, lds, s, polys, tab, sub, out, partial,
+                                                                 (uint32_t)c.L, (uint32_t)w, (uint32_t)c.logn, (uint32_t)nblk,
+                                                                 (uint32_t)batch);
     });
 }
 
@@ -3942,8 +3931,7 @@ inline void centered_bits(const Ctx &c, const u64 *polys, const k::LiftSub &sub,
     const size_t nblk = blocks_for(c.n, k::LIFT_THREADS);
     WsGuard part(batch * nblk * sizeof(uint32_t), s, true);
     launch_lift<true>(c, polys, sub, nullptr, (uint32_t *)part.p, 0, batch, s);
-    FHE_LAUNCH("noise_max", k::noise_max_kernel, dim3(blocks_for(batch, EW_THREADS)), dim3(EW_THREADS), 0, s,
-               (const uint32_t *)part.p, (uint32_t)nblk, (uint32_t)batch, out_bits);
+    launch_ew<k::noise_max_kernel>("noise_max", batch, s, (const uint32_t *)part.p, (uint32_t)nblk, (uint32_t)batch, out_bits);
 }
 
 // ------------------------------------------------------- plaintext moduli above 64 bits ----
@@ -4005,15 +3993,14 @@ inline void encode_big(const Encoder &e, bool simd, bool scaled, size_t level, c
     if (nvalues > e.n) throw StatusError(E_TOO_MANY_VALUES, "TooManyValues: more values than the degree");
     if (!batch) return;
     const u64 total = (u64)batch * e.n;
-    require(blocks_for(total, k::BIGT_THREADS) <= 0x7fffffffu, E_ARG, "encode: batch exceeds the grid limit");
+    grid_x(blocks_for(total, k::BIGT_THREADS), "encode");
     with_int<2, k::BIGT_WMAX>(e.wt, "encode: unsupported plaintext limbs", [&](auto w) {
         constexpr int WT = decltype(w)::value;
         k::BigVal<WT> qmt;
         for (int i = 0; i < WT; i++) qmt.w[i] = e.q_mod_t_big[level][i];
-        launch_k<k::bigt_project_kernel<WT>>("bigt_project", dim3(blocks_for(total, k::BIGT_THREADS)), dim3(k::BIGT_THREADS),
-                                             0, s, values, (u64)nvalues, out, (uint32_t)qc->L, qc->dmods(),
-                                             (const k::u64x2 *)e.d_delta[level]->p, bigt_consts<WT>(e), qmt,
-                                             scaled ? 1u : 0u, (uint32_t)e.logn, total);
+        launch_ew<k::bigt_project_kernel<WT>, k::BIGT_THREADS>("bigt_project", total, s, values, (u64)nvalues, out, (uint32_t)qc->L,
+                                                               qc->dmods(), (const k::u64x2 *)e.d_delta[level]->p,
+                                                               bigt_consts<WT>(e), qmt, scaled ? 1u : 0u, (uint32_t)e.logn, total);
     });
     launch_ntt(*qc, false, out, out, full_map(*qc, qc->L), batch, s);
 }
@@ -4028,15 +4015,14 @@ inline void reduce_big(const Encoder &e, const u64 *polys, size_t rows, u64 *out
     if (!batch) return;
     require(pc.L <= (size_t)k::LIFT_LMAX, E_ARG, "reduce: more plaintext-context moduli than the generic instance holds");
     const u64 nblk = blocks_for(pc.n, k::BIGT_THREADS);
-    require(batch * nblk <= 0x7fffffffu, E_ARG, "reduce: batch exceeds the grid limit");
+    const unsigned grid = grid_x(batch * nblk, "reduce");
     const u64 *tab = lift_consts(pc);
-    const dim3 grid((unsigned)(batch * nblk)), block(k::BIGT_THREADS);
     with_int<2, k::BIGT_WMAX>(e.wt, "reduce: unsupported plaintext limbs", [&](auto w) {
         constexpr int WT = decltype(w)::value;
         const k::BigT<WT> bt = bigt_consts<WT>(e);
         with_int_or_generic<WT, BIGT_PC_MAX>(pc.L, "reduce: plaintext context shorter than the plaintext modulus", [&](auto p) {
-            launch_k<k::bigt_tail_kernel<decltype(p)::value, WT>>("bigt_tail", grid, block, 0, s, polys, tab, bt, out,
-                                                                  (uint32_t)pc.L, (uint32_t)pc.logn, (uint32_t)nblk);
+            launch_blocks<k::bigt_tail_kernel<decltype(p)::value, WT>>("bigt_tail", grid, k::BIGT_THREADS, 0, s, polys, tab, bt, out,
+                                                                       (uint32_t)pc.L, (uint32_t)pc.logn, (uint32_t)nblk);
         });
     });
 }
@@ -4092,8 +4078,7 @@ inline void measure_noise_big(const Encoder &e, const Scaler &sc, size_t level, 
     if (!batch) return;
     const u64 PL = (u64)cc.L * cc.n;
     WsGuard ph(batch * PL * sizeof(u64), s, true), mp(batch * PL * sizeof(u64), s, true);
-    FHE_LAUNCH("phase", k::phase_kernel, dim3(blocks_for(PL, EW_THREADS), (unsigned)batch), dim3(EW_THREADS), 0, s, ct,
-               s_ntt, ph.u(), cc.dmods(), (uint32_t)nparts, (uint32_t)cc.logn, PL);
+    launch_phase(cc, s_ntt, ct, nparts, ph.u(), batch, s);
     std::unique_ptr<WsGuard> dec;
     if (!m) {
         dec = std::make_unique<WsGuard>(batch * cc.n * e.wt * sizeof(u64), s, true);

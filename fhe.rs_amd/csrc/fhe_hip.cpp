@@ -591,8 +591,7 @@ struct MulShoup : Paired {   // MulAssign<&Poly<NttShoup>>
         const Ctx &c = *dev;
         const u64 total = (u64)n * c.L * c.n;
         if (!total) return;
-        FHE_LAUNCH("mul_shoup", k::mul_shoup_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0, s, d[0],
-                   d[1], d[2], c.dmods(), (uint32_t)c.L, (uint32_t)c.logn, total);
+        launch_ew<k::mul_shoup_kernel>("mul_shoup", total, s, d[0], d[1], d[2], c.dmods(), (uint32_t)c.L, (uint32_t)c.logn, total);
     }
 };
 fhe_status fhe_poly_mul_shoup(const fhe_ctx *ctx, uint64_t *a, const uint64_t *b, const uint64_t *b_shoup,
@@ -1001,10 +1000,7 @@ static void relinearize_polys(const Ksk &ks, const u64 *ct3, u64 *out, size_t n,
     const u64 PL = (u64)cc.L * cc.n;
     if (!n) return;
     WsGuard c2(n * PL * sizeof(u64), s);
-    k::RowMap m = full_map(cc, cc.L);
-    m.src_poly_stride = 3 * PL;
-    m.dst_poly_stride = PL;
-    launch_ntt(cc, true, ct3 + 2 * PL, c2.u(), m, n, s);
+    launch_ntt(cc, true, ct3 + 2 * PL, c2.u(), strided_map(cc, cc.L, 3 * PL, PL), n, s);
     // (c2 in Ntt form doubles as the transforms of digit j under key modulus j)
     key_switch_add(ks, c2.u(), PL, ct3, ct3 + PL, 3 * PL, out, out + PL, 2 * PL, n, s, ct3 + 2 * PL, 3 * PL, 0, nullptr, keyed);
 }
@@ -2418,9 +2414,8 @@ fhe_status fhe_synth_uniform_dev(const fhe_ctx *ctx, uint64_t seed, uint64_t ct0
         const u64 total = (u64)batch * nparts * c.L * c.n;
         if (!total) return;
         need(out, "out");
-        FHE_LAUNCH("synth", k::synth_kernel, dim3(blocks_for(total, EW_THREADS)), dim3(EW_THREADS), 0,
-                   as_stream(stream), out, c.dmods(), (uint32_t)c.L, (uint32_t)c.logn, (uint32_t)nparts, seed, ct0,
-                   part0, total);
+        launch_ew<k::synth_kernel>("synth", total, as_stream(stream), out, c.dmods(), (uint32_t)c.L, (uint32_t)c.logn,
+                                   (uint32_t)nparts, seed, ct0, part0, total);
     });
 }
 size_t fhe_workspace_trim(void) {
