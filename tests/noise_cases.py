@@ -47,6 +47,30 @@ def lift_sets(n):
     return sets
 
 
+# The compile-time instances lift_kernel<L, BITS> that no set above reaches (with_int_or_generic<1, 16> makes L = 1 ... 16):
+# one set per L, widths that mix general, narrow and sub-2^50 moduli, at N = 256 (one workgroup per polynomial).
+LIFT_MORE_N = 256
+LIFT_MORE_SIZES = [
+    [62, 60, 55, 50, 45, 36],
+    [61] * 3 + [49] * 4,
+    [60] * 8,
+    [62, 61, 60, 59, 58, 57, 56, 55, 54, 53],
+    [48] * 11,
+    [62] * 6 + [36] * 6,
+    [58] * 13,
+    [50, 62] * 7,
+    [62] * 15,
+]
+
+
+def lift_more_sets(n=LIFT_MORE_N):
+    """[(moduli)] for LIFT_MORE_SIZES over degree n: exactly the L that lift_sets() leaves out."""
+    sets = [generate_moduli(s, n) for s in LIFT_MORE_SIZES]
+    assert [len(m) for m in sets] == [6, 7, 8, 10, 11, 12, 13, 14, 15]
+    assert {len(m) for m in sets} | {len(s) for s in LIFT_SIZES} == set(range(1, 17))
+    return sets
+
+
 def ints_of(fhe, x, got, w):
     """What Context.lift returned -> [batch][N] Python ints (numpy in: already ints; device in: W limbs each)."""
     if not x.dev:

@@ -23,9 +23,15 @@ def sets16():
 
 
 def test_lift_every_set(fhe, sets16):
-    """L = 1, 2, 3, 4, 5, 9, 16; 36 ... 62-bit moduli; bitlen(q) below, on and above a multiple of 64."""
+    """L = 1, 2, 3, 4, 5, 9, 16; 36 ... 62-bit moduli; bitlen(q) below, on and above a multiple of 64.  Then every other
+    compile-time L (6, 7, 8, 10 ... 15) at N = 256."""
     for moduli in sets16:
         N.case_lift(fhe, False, 16, moduli)
+    # L = 6, 7, 8, 10 ... 15 at N = 256: with the sets above, every compile-time instance L = 1 ... 16
+    more = N.lift_more_sets()
+    assert {len(m) for m in more} | {len(m) for m in sets16} == set(range(1, 17))
+    for moduli in more:
+        N.case_lift(fhe, False, N.LIFT_MORE_N, moduli)
 
 
 @pytest.mark.parametrize("n,sizes", [(512, [50, 50, 40]), (512, [60] * 16), (4096, [62, 45, 36])], ids=["512x3", "512x16", "4096x3"])
@@ -47,6 +53,8 @@ def test_lift_device_arrays(fhe, sets16):
 def test_centered_bits_every_set(fhe, sets16):
     for moduli in sets16:
         N.case_centered_bits(fhe, False, 16, moduli)
+    for moduli in N.lift_more_sets():
+        N.case_centered_bits(fhe, False, N.LIFT_MORE_N, moduli)
 
 
 @pytest.mark.parametrize("sizes", [[62], [44, 42, 42], [60, 60, 60, 60], [52, 51, 51, 51, 51], [57] * 8 + [56], [62] * 16],

@@ -47,12 +47,20 @@ def stock(fhe, n):
 
 def test_lift_every_set(fhe):
     """L = 1, 2, 3, 4, 5, 9, 16; 36 ... 62-bit moduli; bitlen(q) below, on and above a multiple of 64; N = 1024 (four
-    workgroups per polynomial)."""
+    workgroups per polynomial).  Then every other compile-time L (6, 7, 8, 10 ... 15) at N = 256."""
     sets = N.lift_sets(1024)
     seen = instances(fhe, lambda: [N.case_lift(fhe, True, 1024, m, columns=range(0, 1024, 7)) for m in sets])
     assert seen == {(L, False) for L in (1, 2, 3, 4, 5, 9, 16)}, seen
     seen = instances(fhe, lambda: [N.case_centered_bits(fhe, True, 1024, m) for m in sets])
     assert seen == {(L, True) for L in (1, 2, 3, 4, 5, 9, 16)}, seen
+    # the remaining compile-time instances (L = 6, 7, 8, 10 ... 15) at N = 256: with the sets above, every L = 1 ... 16
+    more = N.lift_more_sets()
+    rest = (6, 7, 8, 10, 11, 12, 13, 14, 15)
+    seen = instances(fhe, lambda: [N.case_lift(fhe, True, N.LIFT_MORE_N, m) for m in more])
+    assert seen == {(L, False) for L in rest}, seen
+    seen = instances(fhe, lambda: [N.case_centered_bits(fhe, True, N.LIFT_MORE_N, m) for m in more])
+    assert seen == {(L, True) for L in rest}, seen
+    assert {L for L in rest} | {1, 2, 3, 4, 5, 9, 16} == set(range(1, 17))
 
 
 def test_generic_instance(fhe):
