@@ -40,25 +40,6 @@ inline void require(bool cond, int code, const char *msg) {
     if (!cond) throw StatusError(code, msg);
 }
 
-// The release library reads NO environment variable: FHE_LAB_FLAG / FHE_LAB_INT are compile-time constants there
-// (the variable names do not even reach the binary).  -DFHE_LAB builds (A/B tooling, never loaded by the package)
-// read FHE_LAB_* switches that choose between exact kernel variants; FHE_LAB_SYNC synchronises after every launch.
-#if defined(FHE_LAB)
-inline bool lab_env_flag(const char *name) { return std::getenv(name) != nullptr; }
-inline int lab_env_int(const char *name, int dflt) {
-    const char *e = std::getenv(name);
-    return e ? std::atoi(e) : dflt;
-}
-#define FHE_LAB_FLAG(name) ::fhe::lab_env_flag("FHE_LAB_" name)
-#define FHE_LAB_INT(name, dflt) ::fhe::lab_env_int("FHE_LAB_" name, dflt)
-#else
-#define FHE_LAB_FLAG(name) false
-#define FHE_LAB_INT(name, dflt) (dflt)
-#endif
-inline bool debug_sync() {
-    static const bool on = FHE_LAB_FLAG("SYNC");
-    return on;
-}
 // The F64 kernels for moduli below 2^50 (round 6) are the product default.  fhe_engine_set_f64(0) sends every launch to
 // the integer kernels instead -- an execution option like fhe_ksk_set_mode (same results either way; tests run both, A/B
 // timings flip it inside one process).  Read once per launch.
@@ -182,7 +163,6 @@ private:
             hipLaunchKernelGGL(kernel, grid, block, smem, stream, __VA_ARGS__);          \
         }                                                                                \
         FHE_HIP_CHECK(hipGetLastError());                                                \
-        if (debug_sync()) FHE_HIP_CHECK(hipStreamSynchronize(stream));                   \
     } while (0)
 
 // --------------------------------------------------------------- device allocations ----
@@ -911,16 +891,6 @@ inline void for_groups(size_t batch, size_t group, F &&f) {
     for (size_t b0 = 0; b0 < batch; b0 += group) f(b0, std::min(group, batch - b0));
 }
 
-#if defined(FHE_LAB)
-// rejected kernel variants, selected by FHE_LAB_* environment switches in lab builds only (lab/lab_engine.hpp)
-struct Ksk;
-inline bool lab_try_ntt_fwd(const Ctx &c, unsigned rows_total, bool narrow, const u64 *in, u64 *out, const k::RowMap &map,
-                            hipStream_t s);
-template <int LOGN>
-inline bool lab_try_ks_pair(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0, u64 *o1, u64 out_stride, const u64 *a0,
-                            const u64 *a1, u64 a_stride, size_t npolys, hipStream_t s);
-#endif
-
 // One launch of ntt_kernel on `grid` tiles of 2^logm points.  hr != 0 (Ctx::f64_rows: whole rows of 4096 / 8192 / 16384
 // points, every modulus of the launch below 2^50): the F64 instances, under the label name_f64.
 // (GATHER: galois_apply folds the substitution from N = 4096 on: three tile sizes)
@@ -959,7 +929,7 @@ inline void launch_ntt(const Ctx &c, bool inverse, const u64 *in, u64 *out, k::R
     const unsigned rows_total = grid_x(npolys * map.rows, "ntt");
     const size_t first = (size_t)((int32_t)map.row_begin + map.mod_offset);
     // every modulus of the launch below 2^60: the transform without per-stage conditional subtractions
-    bool narrow = !FHE_LAB_FLAG("NO_NARROW") && c.below_2p60(first, map.rows);
+    const bool narrow = c.below_2p60(first, map.rows);
     // (inverse: with subst_exp the source rows are read through the substitution x -> x^subst_exp, galois_apply)
     auto inverse_lds = [&](uint32_t logm, int hr, size_t grid) {
         with_bool(map.subst_exp != 0, [&](auto gather) {
@@ -971,17 +941,12 @@ inline void launch_ntt(const Ctx &c, bool inverse, const u64 *in, u64 *out, k::R
         // every modulus of the launch below 2^50: the FP64-FMA instances (round 6)
         const int hr = c.f64_rows(first, map.rows);
         if (inverse) return inverse_lds(logn, hr, rows_total);
-#if defined(FHE_LAB)
-        if (!hr && lab_try_ntt_fwd(c, rows_total, narrow, in, out, map, s)) return;   // lab/lab_engine.hpp
-#endif
         launch_ntt_lds<false>(c, "ntt_fwd", "ntt_fwd_f64", logn, narrow, hr, rows_total, s, in, out, map, logn);
         return;
     }
     const uint32_t logm = 13, g0 = logn - logm;
     const size_t tiles = (size_t)rows_total << g0;
-    // the LDS halves take the bound-tracked narrow passes here too (round 4; rounds 1-3 ran rows larger than LDS on the
-    // general passes whatever the moduli)
-    narrow = narrow && !FHE_LAB_FLAG("NO_NARROW_SUB");
+    // (the LDS halves take the bound-tracked narrow passes here too)
     k::RowMap inplace = map;
     inplace.src_poly_stride = map.dst_poly_stride;
     inplace.src_row_fixed = -1;
@@ -1060,7 +1025,7 @@ inline void launch_tensor_intt_rows(const Ctx &e, const k::TensorSrc &ts, u64 *o
 
 inline void launch_tensor_intt(const Ctx &e, const k::TensorSrc &ts, u64 *out, size_t nb, hipStream_t s, bool reverse) {
     // maximal runs of rows of the same kind (moduli below 2^60 or not): one launch each (reverse: last run first)
-    bool allow = !FHE_LAB_FLAG("NO_NARROW");
+    bool allow = true;
     // A launch that does not fill the device anyway (its workgroups all run at once: a single ciphertext pair, a handful)
     // takes ONE workgroup's time whatever its passes cost, so two launches -- narrow rows, then general rows -- take twice
     // that: such a launch runs every row on the general passes (valid for any modulus below 2^62) in one go.
@@ -1581,7 +1546,7 @@ inline void ksk_alloc(Ksk &k_) {
 
 // The two instance rules every form of the key switch reads.  narrow: key moduli below 2^60, the transform runs without
 // most conditional subtractions (fwd_butterfly_narrow).  rns: residue-row digits of same-width moduli (lift_mode 1).
-inline bool ks_narrow(const Ctx &kc) { return !FHE_LAB_FLAG("NO_NARROW") && kc.below_2p60(0, kc.L); }
+inline bool ks_narrow(const Ctx &kc) { return kc.below_2p60(0, kc.L); }
 inline bool ks_rns(const Ksk &k_) { return k_.digit_arg() == (1u << 8); }
 
 template <int LOGN>
@@ -1589,26 +1554,18 @@ inline void launch_ks_fused(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0, 
                             const u64 *a0, const u64 *a1, u64 a_stride, size_t npolys, hipStream_t s,
                             const u64 *xhat, u64 xhat_stride, uint32_t gal) {
     const Ctx &kc = *k_.ksk_ctx;
-#if defined(FHE_LAB)
-    if (!gal && lab_try_ks_pair<LOGN>(k_, p, p_stride, o0, o1, out_stride, a0, a1, a_stride, npolys, s)) return;   // lab/lab_engine.hpp
-#endif
     const size_t lds = (k::lds_words(1u << LOGN) + (k::ks_acc1_in_lds_c(LOGN) ? (size_t)1 << LOGN : 0)) * sizeof(u64);
     const bool narrow = ks_narrow(kc);
-    // N = 16384 (ks_fused_kernel's GM): radix-8 while the twiddles are scalar, radix-4 after (GM_MIXED).  Lab builds:
-    // FHE_LAB_KS14_PLAN = 8 radix-8 passes throughout (24 VGPRs spilled), 4 radix-4 passes throughout.
-    static const int plan14 = FHE_LAB_INT("KS14_PLAN", 0);
     // N = 8192: one workgroup owns a CU (132 KiB of LDS), so the items of a launch go to one resident workgroup per
-    // CU, each prefetching its next item's first row across its epilogue (lab builds, FHE_LAB_KS_PERSIST=0: one
-    // workgroup per item)
-    static const int ks_persist = FHE_LAB_INT("KS_PERSIST", 1);
+    // CU, each prefetching its next item's first row across its epilogue
     const uint32_t items = grid_x(npolys * kc.L, "key switch");
     unsigned ks_grid = items;
 #if defined(FHE_HOST_EMULATION)
     constexpr bool ks_persist_size = true;   // (every size, so that the emulated suite walks the item loop)
 #else
-    constexpr bool ks_persist_size = LOGN == 13 || (FHE_KS_PERSIST14 && LOGN == 14);
+    constexpr bool ks_persist_size = LOGN == 13;
 #endif
-    if (ks_persist_size && ks_persist > 0) ks_grid = std::min<unsigned>(items, device_cus(kc.device) * ks_persist);
+    if (ks_persist_size) ks_grid = std::min<unsigned>(items, device_cus(kc.device));
     // RNS instances (N = 4096, 8192): residue-row digits of same-width moduli, see the kernel.  (Not at N = 16384: in
     // round 3 that instance spilled 52 B; it no longer does, and measured again at C3 in round 4 it changes nothing --
     // relinearise of 512: 4.09 / 4.18 / 4.18 ms against 4.17 / 4.14 / 4.13, profiles/r04_ks14_rns_ab.jsonl.)
@@ -1626,10 +1583,12 @@ inline void launch_ks_fused(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0, 
     if constexpr (LOGN >= 12 && LOGN <= 14) {
         const int hr = (k_.c0f.p && k_.log_base == 0) ? kc.f64_class(0, kc.L) : 0;
         if (hr) {
-            // Geometry of the F64 instances.  N = 16384: the tile's own 1024 threads x 16 coefficients.  N = 8192 (and 4096 in
-            // the same shape): 512 (256) threads x 16 coefficients, BOTH accumulator sets in registers, tile-only LDS, one
-            // workgroup per item -- TWO (four) workgroups per CU, so one's barriers and LDS round trips hide behind the other's
-            // arithmetic.  Rounds 3 and 6 measured this cut slower with the passes it could afford then (mixed radix-8 /
+            // Geometry of the F64 instances.  N = 16384: the tile's own 1024 threads x 16 coefficients.  N = 8192:
+            // 512 threads x 16 coefficients, BOTH accumulator sets in registers, tile-only LDS, one
+            // workgroup per item -- TWO workgroups per CU, so one's barriers and LDS round trips hide behind the other's
+            // arithmetic.  (The same shape at N = 4096, 256 threads: 1,024 / 256 relinearisations -2 %, 64 +23 %,
+            // profiles/r06_l_f64_geometry_ab.jsonl -- N = 4096 keeps 512 threads x 8.)
+            // Rounds 3 and 6 measured this cut slower with the passes it could afford then (mixed radix-8 /
             // radix-4: profiles/r03_ks13_t512_rns_ab.txt, r06_ks13_f64_t512_ab_rejected.jsonl); with one-word per-lane twiddles
             // radix-8 passes fit (126 VGPRs, no scratch) and it is ahead: relinearise of 1,024 at the stock n = 8192 set 1.114
             // -> 1.032 ms, of 64 0.114 -> 0.106 (profiles/r06_ks13_f64_t512_radix8_ab.jsonl, same digest).
@@ -1637,7 +1596,7 @@ inline void launch_ks_fused(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0, 
             // threads (N = 8192: 1024 x 8, c1 accumulators in LDS, resident item loop) finish a single workgroup sooner --
             // 0.052-0.055 ms against 0.062-0.070 for up to 256 workgroups (profiles/r06_l_f64_ks_modes.jsonl,
             // r06_m_f64_ks_modes_grid.jsonl) -- so the 512-thread instance is taken from the second workgroup per CU on.
-            constexpr int F64_TT = (LOGN == 13 || (LOGN == 12 && FHE_KS12_F64_T256)) ? (1 << LOGN) / 16 : 0;
+            constexpr int F64_TT = LOGN == 13 ? (1 << LOGN) / 16 : 0;
             const bool two_per_cu = F64_TT != 0 && npolys * kc.L > (size_t)device_cus(kc.device);
             constexpr int GMV = k::KS_GMAX;   // radix-8 passes at every size: one-word twiddles leave the N = 16384 tile room
             with_row_kind<LOGN>(false, hr, [&](auto, auto h) {
@@ -1655,43 +1614,6 @@ inline void launch_ks_fused(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0, 
             return;
         }
     }
-#if defined(FHE_LAB)
-    if constexpr (LOGN == 13) {
-        // FHE_LAB_KS13_T512 = 1: 512 threads x 16 coefficients, both accumulator sets in registers, tile-only LDS (two
-        // workgroups per CU), mixed radix-8 / radix-4 passes; = 2: the same with radix-4 passes throughout
-        static const int t512 = FHE_LAB_INT("KS13_T512", 0);
-        if (t512 && !gal) {   // (the 512-thread lab instances have no gathering loader: a folded rotation takes the product launch)
-            auto launch512 = [&](auto gm) {
-                with_bool(narrow, [&](auto nw) {
-                    with_bool(rns, [&](auto r) {
-                        launch("key_switch_fused",
-                               kernel_c<k::ks_fused_kernel<LOGN, decltype(nw)::value, decltype(gm)::value, 512, decltype(r)::value>>{},
-                               items, 512, lds_tile, false);
-                    });
-                });
-            };
-            if (t512 == 2) launch512(int_c<2>{});
-            else if (t512 == 3) launch512(int_c<k::KS_GMAX>{});
-            else launch512(int_c<k::GM_MIXED>{});
-            return;
-        }
-    }
-    if constexpr (LOGN == 14) {
-        // FHE_LAB_KS14_T512 = 1: 512 threads x 32 coefficients, 256 VGPRs (two waves per SIMD), both accumulator sets in
-        // registers, radix-16 passes (GM = 4), the RNS loader; = 2: the same with radix-8 passes
-        static const int t512 = FHE_LAB_INT("KS14_T512", 0);
-        if (t512 && !gal && ks_rns(k_)) {
-            with_bool(narrow, [&](auto nw) {
-                with_bool(t512 == 2, [&](auto radix8) {
-                    launch("key_switch_fused",
-                           kernel_c<k::ks_fused_kernel<LOGN, decltype(nw)::value, decltype(radix8)::value ? 3 : 4, 512, true>>{},
-                           items, 512, lds_tile, false);
-                });
-            });
-            return;
-        }
-    }
-#endif
     if constexpr (LOGN < 12) require(!gal, E_ARG, "folded Galois substitution below N = 4096");
     // the integer instances with GM = gm
     auto launch_gm = [&](auto gm) {
@@ -1709,11 +1631,10 @@ inline void launch_ks_fused(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0, 
             });
         });
     };
-    if constexpr (LOGN == 14) {   // (radix-4 passes at N = 8192 measured slower: 0.559 vs 0.532 ms per launch)
-        if (plan14 == 4) return launch_gm(int_c<2>{});
-        if (plan14 != 8) return launch_gm(int_c<k::GM_MIXED>{});
-    }
-    launch_gm(int_c<k::KS_GMAX>{});
+    // N = 16384 (ks_fused_kernel's GM): radix-8 while the twiddles are scalar, radix-4 after (GM_MIXED; radix-8 throughout
+    // spills 24 VGPRs).  (radix-4 passes at N = 8192 measured slower: 0.559 vs 0.532 ms per launch)
+    if constexpr (LOGN == 14) launch_gm(int_c<k::GM_MIXED>{});
+    else launch_gm(int_c<k::KS_GMAX>{});
 }
 
 // ---- unfused key switch (kernels_ks.hpp: ks_ntt_kernel + ks_mac_kernel) ----
@@ -1745,8 +1666,7 @@ inline bool ks_use_unfused(const Ksk &k_, int mode, size_t npolys) {
     if (mode == KS_UNFUSED || mode == KS_UNFUSED_SUB) return true;
     if (mode == KS_FUSED || mode == KS_FUSED_SUB) return false;
     const Ctx &kc = *k_.ksk_ctx;
-    if (kc.logn >= (size_t)FHE_LAB_INT("KS_UNFUSED_MIN_LOGN", 99)) return true;
-    if (FHE_LAB_FLAG("NO_KS_SMALL_UNFUSED") || kc.logn < 12 || k_.ndigits < 3) return false;
+    if (kc.logn < 12 || k_.ndigits < 3) return false;
     const size_t fused_wg = (npolys * kc.L) << (kc.logn > 14 ? kc.logn - 14 : 0);
     const size_t cus = (size_t)device_cus(kc.device);
     // (rows larger than LDS with short digit loops: the 8192-point fused sub-blocks take over earlier -- N = 32768, 4
@@ -1956,7 +1876,6 @@ inline void key_switch_polys(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0,
                              const u64 *a0, const u64 *a1, u64 a_stride, size_t npolys, hipStream_t s,
                              const u64 *xhat = nullptr, u64 xhat_stride = 0, uint32_t gal = 0,
                              const KsExtraFwd *extra = nullptr, const KsKeyed *keyed = nullptr) {
-    if (FHE_LAB_FLAG("NO_KS_XHAT") && !gal) xhat = nullptr;
     require(!gal || (xhat != nullptr && a1 == nullptr), E_ARG, "galois key switch: needs the Ntt rows, adds to c0 only");
     if (keyed != nullptr) {   // one key per group of polynomials: `k_` is the set's first key
         require(extra == nullptr, E_ARG, "keyed batches take no extra rows");
@@ -1976,13 +1895,7 @@ inline void key_switch_polys(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0,
         }
     }
     if (extra != nullptr && extra->rows != nullptr) ks_extra_forward(kc, *extra, s);   // (a fused launch: their transform is its own)
-    // N = 16384: whole-row kernel (1024 threads x 16 coefficients, 24 VGPRs spilled) or two 8192-point sub-blocks
-    // with the first stage folded into the loader (FHE_KS_SPLIT14=1)
-    static const bool split14 = FHE_LAB_INT("KS_SPLIT14", 0) != 0;
-    // lab builds, FHE_LAB_KS_HALF13=1: N = 8192 as two 4096-point sub-blocks (512 threads, 34 KiB tile + 32 KiB of LDS
-    // accumulators: two workgroups per CU), the first stage folded into the loader
-    static const bool half13 = FHE_LAB_INT("KS_HALF13", 0) != 0;
-    if (kc.logn <= 12 || (kc.logn == 13 && !half13) || (kc.logn == 14 && !split14)) {
+    if (kc.logn <= 14) {   // rows that fit LDS: the whole-row kernel
         with_logn<3, 14>(kc.logn, "unsupported key-switch row size", [&](auto ln) {
             launch_ks_fused<decltype(ln)::value>(k_, p, p_stride, o0, o1, out_stride, a0, a1, a_stride, npolys, s, xhat, xhat_stride,
                                                  gal);
@@ -1991,21 +1904,20 @@ inline void key_switch_polys(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0,
     }
     // Rows larger than LDS (N >= 32768): one workgroup per part of a row, the first stages folded into its loader.
     const bool narrow = ks_narrow(kc);
-    // N = 32768 / 65536 as two / four 16384-point parts on the N = 16384 kernel (one / two folded stages, knobs.hpp
-    // FHE_KS_HALF15: 1 the generic loader, 2 the RNS loader where the key's digits are residue rows) -- 15 % ahead of the
+    // N = 32768 / 65536 as two / four 16384-point parts on the N = 16384 kernel (one / two folded stages; the RNS
+    // loader where the key's digits are residue rows, the generic loader otherwise) -- 15 % ahead of the
     // 8192-point sub-blocks below once a launch fills the device (profiles/r04_ks_half15_ab.txt).  A launch whose
     // 8192-point sub-blocks all fit the device at once (one workgroup per CU) is a different regime: its time is ONE
     // workgroup's, and a 16384-point part takes 1.7 x as long as an 8192-point one (N = 65536, 4 moduli, 8 polynomials:
     // 128 parts 0.158 ms, 256 sub-blocks 0.129 ms, profiles/r04_final3_n65536_ab.jsonl) -- KS_AUTO takes the small tiles
     // there; KS_FUSED / KS_FUSED_SUB force either form.
-    static const int half15 = FHE_LAB_INT("KS_HALF15", FHE_KS_HALF15);
     const int ks_mode = k_.mode.load(std::memory_order_relaxed);
     const bool fits_at_once = ((npolys * kc.L) << (kc.logn - 13)) <= (size_t)device_cus(kc.device);
-    const bool parts16k = half15 && ks_mode != KS_FUSED_SUB && (ks_mode == KS_FUSED || !fits_at_once);
+    const bool parts16k = ks_mode != KS_FUSED_SUB && (ks_mode == KS_FUSED || !fits_at_once);
     if ((kc.logn == 15 || kc.logn == 16) && parts16k) {
         const size_t lds_ = k::lds_words(1u << 14) * sizeof(u64);
         const unsigned grid = grid_x((npolys * kc.L) << (kc.logn - 14), "key switch");
-        const bool rns = half15 == 2 && ks_rns(k_);
+        const bool rns = ks_rns(k_);
         with_bool(kc.logn == 15, [&](auto one) {
             with_bool(narrow, [&](auto nw) {
                 with_bool(rns, [&](auto r) {
@@ -2022,8 +1934,8 @@ inline void key_switch_polys(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0,
         return;
     }
     // 8192-point sub-blocks, logn - 13 folded stages (ks_fused_split_kernel; rounds 1-3: every launch)
-    auto launch_split = [&](auto g0, auto lm) {
-        constexpr int G0 = decltype(g0)::value, LM = decltype(lm)::value;
+    auto launch_split = [&](auto g0) {
+        constexpr int G0 = decltype(g0)::value, LM = 13;
         const size_t lds_ = (k::lds_words(1u << LM) + ((size_t)1 << LM)) * sizeof(u64);
         with_bool(narrow, [&](auto nw) {
             with_bool(ks_rns(k_), [&](auto r) {
@@ -2034,11 +1946,8 @@ inline void key_switch_polys(const Ksk &k_, const u64 *p, u64 p_stride, u64 *o0,
             });
         });
     };
-#if defined(FHE_LAB)
-    if (kc.logn == 13) return launch_split(int_c<1>{}, int_c<12>{});
-#endif
-    with_logn<14, 16>(kc.logn, "unsupported key-switch row size",
-                      [&](auto ln) { launch_split(int_c<decltype(ln)::value - 13>{}, int_c<13>{}); });
+    with_logn<15, 16>(kc.logn, "unsupported key-switch row size",
+                      [&](auto ln) { launch_split(int_c<decltype(ln)::value - 13>{}); });
 }
 
 // Poly::<PowerBasis>::switch_down_to (M/rq/mod.rs:498-507): `iters` applications of switch_down.
@@ -2170,7 +2079,7 @@ inline void galois_apply(const Ksk &ks, size_t exponent, const u64 *ct, u64 *out
     // (before: substitute_kernel wrote both permuted parts -- 2 polynomials out, 3 row sets read back: 9 % of a rotation)
     // (the consumers gather from `ct` while `out` is being written: a caller that rotates in place takes the copying path)
     const bool overlap = out < ct + batch * 2 * PL && ct < out + batch * 2 * PL;
-    if (cc.logn >= 12 && ks.ksk_ctx->niterations_to(cc) == 0 && !overlap && !FHE_LAB_FLAG("NO_GALOIS_FOLD")) {
+    if (cc.logn >= 12 && ks.ksk_ctx->niterations_to(cc) == 0 && !overlap) {
         WsGuard c2(batch * PL * sizeof(u64), s);
         k::RowMap m = strided_map(cc, cc.L, 2 * PL, PL);
         m.subst_exp = (uint32_t)e;
@@ -2881,7 +2790,7 @@ inline void bfv_mul(const Mul &m, const u64 *lhs, const u64 *rhs, u64 *out, size
     const size_t chunk = plan.chunk;
     // the extenders copy the shared prefix rows verbatim; when both share all L rows the tensor
     // kernel reads those rows from the inputs directly and the copy is skipped
-    const bool skip_copy = m.ext_lhs->ncommon == L && m.ext_rhs->ncommon == L && !FHE_LAB_FLAG("NO_SKIP_COPY");
+    const bool skip_copy = m.ext_lhs->ncommon == L && m.ext_rhs->ncommon == L;
     struct ChunkWs {   // (ext: the extended lhs parts of the chunk, then the extended rhs parts)
         WsGuard ext, ten, d, pre;
         ChunkWs(size_t chunk, u64 PK, u64 PL, size_t pre_bytes, hipStream_t st)
@@ -2913,16 +2822,12 @@ inline void bfv_mul(const Mul &m, const u64 *lhs, const u64 *rhs, u64 *out, size
     const bool square = lhs == rhs && m.ext_lhs == m.ext_rhs;
     // Both operands through the same extender (Multiplicator::default; not the second HPS strategy): the two
     // extensions are ONE pass of three launches over 4 nb polynomials (scale_polys_pair) -- round 4,
-    // profiles/r04_merged_ext_ab.txt.  Otherwise, for a batch that is one chunk, the two extension chains run side by
+    // profiles/r04_merged_ext_ab.txt, r04_merged_ext_dirflags_ab.txt: batch 1024 unchanged, batch 64 -5 %, batch 16
+    // -12.5 %.  Otherwise, for a batch that is one chunk, the two extension chains run side by
     // side on the caller's and the internal stream (round 3's split_ext).
-    const bool merged_ext = !square && m.ext_lhs == m.ext_rhs && FHE_LAB_INT("MUL_MERGED_EXT", FHE_MUL_MERGED_EXT) != 0;
-    // Every kernel of the chain starts on what its producer wrote last (knobs.hpp FHE_MUL_DIRFLAGS): the extension ends
-    // ascending, so the tensor kernel runs descending, the down-scaler ascending, the transform of c0 / c1 descending
-    // and the key switch ascending again.  (Rows larger than LDS keep round 3's order: their transforms are two
-    // kernels each and the global halves run ascending.)
-    const bool dirflags = b.logn <= 14 && FHE_LAB_INT("MUL_DIRFLAGS", FHE_MUL_DIRFLAGS) != 0;
+    const bool merged_ext = !square && m.ext_lhs == m.ext_rhs;
     const bool split_ext = !dual && !square && !merged_ext && m.streams.load(std::memory_order_relaxed) >= 2 &&
-                           batch <= chunk && FHE_LAB_INT("MUL_SPLIT_EXT", 1) != 0;
+                           batch <= chunk;
     hipEvent_t ext_done = nullptr;
     struct EventBack {
         hipEvent_t &e;
@@ -2972,12 +2877,12 @@ inline void bfv_mul(const Mul &m, const u64 *lhs, const u64 *rhs, u64 *out, size
         // TENSOR (mul.rs:198-201) + the inverse NTT of the down-scaler (M/rq/scaler.rs:69-79):
         // ten [3][nb][K][N] ends up in PowerBasis.  Rows that fit LDS: one fused kernel;
         // larger rows: element-wise tensor kernel, then the two-kernel inverse NTT.
-        const bool fused_tensor = e.logn <= 16 && !FHE_LAB_FLAG("NO_TENSOR_FUSION");
+        const bool fused_tensor = e.logn <= 16;
         if (fused_tensor) {
             require(nb <= 32768, E_ARG, "chunk too large for the fused tensor kernel");  // 3*K*nb blocks in a 1-D grid
             k::TensorSrc ts{extL, square ? extL : extR, skip_copy ? l : nullptr, skip_copy ? r : nullptr,
                             (uint32_t)L, (uint32_t)L};
-            launch_tensor_intt(e, ts, ten.u(), nb, s, dirflags);
+            launch_tensor_intt(e, ts, ten.u(), nb, s);
         } else {
             for_groups(nb, 32768, [&](size_t t0, size_t tn) {   // (the pair is the grid's second dimension)
                 launch_rows<k::tensor_kernel>("tensor", PK, tn, 1, s, extL + t0 * 2 * PK, (square ? extL : extR) + t0 * 2 * PK,
@@ -2989,10 +2894,8 @@ inline void bfv_mul(const Mul &m, const u64 *lhs, const u64 *rhs, u64 *out, size
         if (!fused_tensor) launch_ntt(e, true, ten.u(), ten.u(), full_map(e, K), nb * 3, s);
         u64 *dst = m.mod_switch ? pre.u() : out + b0 * parts * PL;
         // DOWN-SCALE (mul.rs:204-206) to PowerBasis rows of d [3][nb][L][N]
-        // (dirflags: the tensor kernel ran backwards and ended on the first polynomials: the scaler starts there)
-        launch_scale(*m.down, ten.u(), PK, d.u(), PL, nb * 3, s, dirflags && fused_tensor);
-        k::RowMap back = full_map(b, L);
-        back.reverse = (dirflags && fused_tensor) ? 1u : 0u;   // ... and the forward transform where the scaler ended
+        launch_scale(*m.down, ten.u(), PK, d.u(), PL, nb * 3, s);
+        const k::RowMap back = full_map(b, L);
         if (m.rk) {
             // c0, c1 go back to Ntt; c2 stays in PowerBasis for the key switch (the reference
             // transforms c2 forward and, at mul.rs:212, back again; iNTT(NTT(x)) = x exactly).
@@ -3002,8 +2905,7 @@ inline void bfv_mul(const Mul &m, const u64 *lhs, const u64 *rhs, u64 *out, size
             // sits at the ciphertext's level, the forward transform of (c0, c1) rides on its stage-A launch -- one launch
             // less on the critical path of a small call (C2, one pair: 0.088 -> 0.077 ms, profiles/r05_merged_fwd_ab.jsonl)
             const bool ride = m.rk->ksk_ctx->niterations_to(*m.rk->ct_ctx) == 0 && b.logn <= 14 &&
-                              ks_use_unfused(*m.rk, m.rk->mode.load(std::memory_order_relaxed), nb) &&
-                              !FHE_LAB_FLAG("NO_MERGED_FWD");
+                              ks_use_unfused(*m.rk, m.rk->mode.load(std::memory_order_relaxed), nb);
             KsExtraFwd ex;
             ex.rows = d.u();
             ex.poly_stride = PL;
@@ -4123,7 +4025,3 @@ inline void measure_noise(const Encoder &e, const Scaler &sc, const u64 *s_ntt, 
 }
 
 }  // namespace fhe
-
-#if defined(FHE_LAB)
-#include "lab/lab_engine.hpp"
-#endif

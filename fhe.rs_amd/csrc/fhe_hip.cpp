@@ -2521,16 +2521,4 @@ fhe_status fhe_prof_get_symbol(size_t index, char *symbol, size_t symbol_cap) {
     });
 }
 
-#if defined(FHE_LAB) && defined(FHE_PHASE_TIMING)
-// Lab builds only (not in the header): reads and clears the phase-timing slots of kernels.hpp.
-fhe_status fhe_debug_phase_timing(uint64_t *out, size_t n) {
-    return guard([&] {
-        static unsigned long long h[FHE_TS_TOTAL_SLOTS], z[FHE_TS_TOTAL_SLOTS];
-        FHE_HIP_CHECK(hipMemcpyFromSymbol(h, HIP_SYMBOL(fhe::k::g_phase_ts), sizeof(h)));
-        FHE_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(fhe::k::g_phase_ts), z, sizeof(z)));
-        for (size_t i = 0; i < n && i < FHE_TS_TOTAL_SLOTS; i++) out[i] = h[i];
-    });
-}
-#endif
-
 }  // extern "C"

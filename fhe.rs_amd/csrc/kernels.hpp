@@ -46,7 +46,7 @@
 //                           SecretKey::try_decrypt   F/bfv/plaintext_vec.rs:105-132, plaintext.rs:172-197, secret_key.rs:238-250
 //   encode_stream_kernel, transcode_ew_kernel   plaintexts from packed bits: fhe_util::transcode_* + Plaintext::try_encode
 //                           (encode_database, the SealPIR fold)   fhe-util lib.rs:71-190, examples/util.rs:97-145, sealpir.rs:176-200
-// Compile-time knobs live in knobs.hpp (pinned in the release build); rejected kernel variants in tools/lab/ (lab builds only).
+// There are no build variants: measured-and-rejected alternatives are listed in docs/HISTORY.md, their code is in git.
 #pragma once
 #include "kernels_common.hpp"
 #include "kernels_passes.hpp"
@@ -65,13 +65,3 @@
 #include "kernels_mbfv.hpp"
 #include "kernels_bigt.hpp"
 #include "kernels_transcode.hpp"
-
-namespace fhe {
-namespace k {
-
-#if defined(FHE_LAB)
-#include "lab/lab_kernels.hpp"   // measured-and-rejected variants: lab builds only
-#endif
-
-}  // namespace k
-}  // namespace fhe

@@ -1,5 +1,5 @@
 // kernels_common.hpp -- what every kernel family shares: the row map, LDS padding, scalar-register / wave-local
-// helpers and the phase-timing hook.  (Part of kernels.hpp, split by family in round 3 for reviewability.)
+// helpers.  (Part of kernels.hpp, split by family in round 3 for reviewability.)
 #pragma once
 #include <type_traits>
 
@@ -15,8 +15,8 @@ struct u64x2 {
 
 // Streaming accesses: data that ONE lane reads or writes once (a database row of the PIR loop, a ciphertext that is
 // multiplied by a plaintext and never looked at again) is marked non-temporal, so that it does not push the operands
-// other workgroups re-read (shared queries, keys, tables) out of L2 / the Infinity Cache.  (FHE_STREAM_NT, knobs.hpp)
-#if defined(__HIP_DEVICE_COMPILE__) && FHE_STREAM_NT
+// other workgroups re-read (shared queries, keys, tables) out of L2 / the Infinity Cache.
+#if defined(__HIP_DEVICE_COMPILE__)
 typedef u64 u64v2_native __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ u64x2 load_stream(const u64x2 *p) {
     const u64v2_native v = __builtin_nontemporal_load(reinterpret_cast<const u64v2_native *>(p));
@@ -32,7 +32,7 @@ __device__ __forceinline__ u64x2 load_stream(const u64x2 *p) { return *p; }
 __device__ __forceinline__ void store_stream(u64x2 *p, u64x2 v) { *p = v; }
 #endif
 
-// (last-use loads of the multiply pipeline, knobs.hpp FHE_PIPE_NT)
+// (last-use loads of the multiply pipeline, PIPE_NT_* below)
 template <bool NT>
 __device__ __forceinline__ u64 load_last(const u64 *p) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -42,22 +42,18 @@ __device__ __forceinline__ u64 load_last(const u64 *p) {
 }
 template <bool NT>
 __device__ __forceinline__ u64x2 load_last2(const u64x2 *p) {
-#if defined(__HIP_DEVICE_COMPILE__) && FHE_STREAM_NT
+#if defined(__HIP_DEVICE_COMPILE__)
     if constexpr (NT) return load_stream(p);
 #endif
     return *p;
 }
 
-// FHE_TS(k): phase-timing stamps of one wave, compiled to nothing except in -DFHE_LAB -DFHE_PHASE_TIMING builds
-// (tools/ks_phase_timing.py).
-#if defined(FHE_LAB) && defined(FHE_PHASE_TIMING)
-#include "lab/phase_timing.hpp"
-#else
-#define FHE_TS(k) do { } while (0)
-#define FHE_TSK(k) do { } while (0)
-#define FHE_TS_BEGIN() do { } while (0)
-#define FHE_TS_END() do { } while (0)
-#endif
+// Multiply pipeline: non-temporal LOADS where a kernel reads data for the last time.  Measured (profiles/r04_pipe_nt_ab.txt):
+// scalers + forward NTT are 0.6 % ahead of none in six of six same-box comparisons at C2 / 1024; the inverse transform's
+// tile (which the tensor kernel reads again) is noise.
+constexpr bool PIPE_NT_SCALER = true;   // the scalers' input columns
+constexpr bool PIPE_NT_FWD = true;      // the forward transforms' rows
+constexpr bool PIPE_NT_INV = false;     // the inverse transform's tile
 
 // Maps a workgroup index to (polynomial, row) and to source/destination addresses.
 // block b -> poly = b / rows, r = row_begin + b % rows;
@@ -115,12 +111,10 @@ FHE_HD uint32_t galois_src_index(uint32_t d, uint32_t e, uint32_t logn) {
 // patterns; built, bit-exact, and measured in a drift-cancelling ABBA run: every kernel within +-1 %
 // (profiles/r02_lds_pad_ab.txt).  LDS time is not on these kernels' critical path; this layout (2 KiB smaller per
 // tile) stays and the alternative is not carried in the source.
-// Round 6: with the F64 instances the arithmetic of a pass shrank by a third and LDS time came closer to the critical path, so
-// the alternative layout is back as a lab knob (FHE_LDS_PAD=1: i + 3 (i >> 5); per-element offsets of a group stay additive,
-// (base mod 32) + (offset mod 32) < 32 by the same argument as below).  Measured again (profiles/r06_lds_pad_ab_rejected.jsonl, two lab builds alternating three times, same digest): transforms on 60-bit / 62-bit / F64
-// rows, the stock and C2 multiplies, C3 relinearise -- every cell within -2.9 ... +2.4 %, medians within 1 %: still not on the critical path.  Off.
-FHE_HD uint32_t padi(uint32_t i) { return FHE_LDS_PAD ? i + 3 * (i >> 5) : i + (i >> 4); }
-FHE_HD uint32_t lds_words(uint32_t n) { return FHE_LDS_PAD ? n + 3 * (n >> 5) + 4 : n + (n >> 4) + 2; }
+// Round 6: with the F64 instances LDS time came closer to the critical path; measured again
+// (profiles/r06_lds_pad_ab_rejected.jsonl): every cell within -2.9 ... +2.4 %, medians within 1 %: still not on it.
+FHE_HD uint32_t padi(uint32_t i) { return i + (i >> 4); }
+FHE_HD uint32_t lds_words(uint32_t n) { return n + (n >> 4) + 2; }
 
 constexpr int GMAX = 4;  // radix-16: up to four butterfly stages per LDS round trip
 

@@ -14,10 +14,6 @@ namespace k {
 // F/bfv/ops/mul.rs:224-225; rotation adds substitute(c0) to c0 only); canonical outputs.
 // ks_threads_c(LOGN) threads; thread t owns the 16-byte chunks {c*T + t}, c < CH (or the single
 // coefficient t when the row is smaller than one chunk per thread).
-// (FHE_KS_TWPF=true: the transforms' per-lane twiddles requested one pass ahead at N = 8192 -- 112 VGPRs, no scratch,
-// and no change in same-box A/B, profiles/r02_ks_twpf_ab.txt)
-// (FHE_KS_PERSIST14=1: resident workgroups at N = 16384 as well -- no row-prefetch registers there, so nothing to
-// overlap: C3 relinearise 108.1-109.7 k against 111.0-111.3 k ops/s, profiles/r02_ks_persist_ab.txt)
 // TT (threads per workgroup, 0 = ks_threads_c(LOGN)): TT = N / 16 at N = 8192 is the two-workgroups-per-CU cut -- 512
 // threads x 16 coefficients, BOTH accumulator sets in registers (64 VGPRs, as at N = 16384), only the 68 KiB row tile
 // in LDS, so that a second workgroup is resident and runs its butterflies while this one sits in a barrier.
@@ -25,9 +21,6 @@ constexpr int ks_threads_tt(int logn, int tt) { return tt ? tt : ks_threads_c(lo
 constexpr bool ks_acc1_in_lds_tt(int logn, int tt) { return tt == 0 && ks_acc1_in_lds_c(logn); }
 // RNS (the host sets it for LOGN >= 12 when digit_arg says so): the digits are residue rows of same-width moduli
 // (digit_shift_bits == 0, lift_mode == 1 -- relinearisation and Galois keys), lifted by one conditional subtraction.
-// (TT = 512 at N = 16384, lab: 32 coefficients per thread and a 256-register budget -- two waves per SIMD -- so that
-// both accumulator sets AND a radix-16 pass fit: 4 passes instead of 6, see engine.hpp FHE_LAB_KS14_T512)
-constexpr int ks_min_waves(int logn, int tt) { return (logn == 14 && tt == 512) ? 2 : 4; }
 // G0 > 0 (round 4; LOGN = 14: N = 32768 as two 16384-point halves, N = 65536 as four quarters): the tile is one of 2^G0
 // parts of a row of 2^(LOGN+G0) points and the first G0 Cooley-Tukey stages are folded into the loader.  G0 = 1: half
 // `sub` needs x[e] +/- w x[e + 2^LOGN] -- ONE Shoup product per coefficient (what a regular stage costs per butterfly
@@ -47,7 +40,7 @@ constexpr int ks_min_waves(int logn, int tt) { return (logn == 14 && tt == 512) 
 // 126 VGPRs, no scratch -- the two-workgroups-per-CU cut that lost with two-word twiddles is 6 % ahead here, engine.hpp
 // launch_ks_fused), TT = 0 otherwise.  The integer instances (F64 = 0) are the round-5 kernels bit for bit (tests/test_isa_guards.py).
 template <int LOGN, bool NARROW = false, int GM = KS_GMAX, int TT = 0, bool RNS = false, int G0 = 0, bool GAL = false, int F64 = 0>
-__global__ void __launch_bounds__(ks_threads_tt(LOGN, TT), ks_min_waves(LOGN, TT))
+__global__ void __launch_bounds__(ks_threads_tt(LOGN, TT), 4)
     ks_fused_kernel(const u64 *__restrict__ pin, u64 src_poly_stride, u64 *__restrict__ out0, u64 *__restrict__ out1,
                     u64 out_poly_stride, const u64 *__restrict__ addend0, const u64 *__restrict__ addend1,
                     u64 addend_poly_stride, const u64 *__restrict__ k0, const u64 *__restrict__ k0s,
@@ -64,6 +57,7 @@ __global__ void __launch_bounds__(ks_threads_tt(LOGN, TT), ks_min_waves(LOGN, TT
     constexpr int NS = 1 << G0;
     static_assert(G0 == 0 || (G0 <= 2 && !ks_acc1_in_lds_tt(LOGN, TT) && tile_chunks_c(LOGN, ks_threads_tt(LOGN, TT)) >= 2),
                   "the folded first stages are written for the register-accumulator form (N = 16384 tiles)");
+    static_assert(TT == 0 || (F64 > 0 && TT == N / 16), "TT: the F64 instances' two-workgroups-per-CU cut only");
     static_assert(F64 == 0 || (RNS && G0 == 0 && !NARROW && tile_chunks_c(LOGN, ks_threads_tt(LOGN, TT)) >= 1),
                   "the F64 instances: RNS digits, whole-row tiles");
     // F64 bounds (units: zq_f64.hpp).  The transform leaves values below VB; they are reduced before the products when that
@@ -96,11 +90,10 @@ __global__ void __launch_bounds__(ks_threads_tt(LOGN, TT), ks_min_waves(LOGN, TT
 #if defined(FHE_HOST_EMULATION)
     constexpr bool ITEM_LOOP = true;    // (every size, so that the emulated suite walks the loop)
 #else
-    constexpr bool ITEM_LOOP = (LOGN == 13 && TT == 0) || (FHE_KS_PERSIST14 && LOGN == 14);
+    constexpr bool ITEM_LOOP = LOGN == 13 && TT == 0;
 #endif
     uint32_t item = blockIdx.x;
     if (item >= total) return;
-    FHE_TS_BEGIN();
     do {
     const uint32_t bj = item >> G0, sub = item & (NS - 1);
     const uint32_t b = to_sgpr(bj / lk), j = bj - b * lk;
@@ -195,7 +188,6 @@ __global__ void __launch_bounds__(ks_threads_tt(LOGN, TT), ks_min_waves(LOGN, TT
     }
     const uint32_t nloop = ndigits - (own ? 1u : 0u);          // digits that go through the transform
     auto digit_of = [&](uint32_t ii) -> uint32_t { return ii + ((own && ii >= j) ? 1u : 0u); };
-    FHE_TSK(20);   // item prologue: index arithmetic, accumulator clears, the caller's own Ntt row (xhat)
     // The workgroup is alone on its CU (LDS), so nothing else hides the row load: digit i+1's
     // row is fetched into registers while digit i goes through its passes.
     constexpr bool PREFETCH = ks_acc1_in_lds_tt(LOGN, TT);   // (needs the VGPRs the LDS accumulators free)
@@ -213,7 +205,6 @@ __global__ void __launch_bounds__(ks_threads_tt(LOGN, TT), ks_min_waves(LOGN, TT
         const uint32_t i = digit_of(ii);
         const uint32_t tid = opaque(tid0);
         const uint32_t sh = i * digit_shift_bits;
-        FHE_TSK(0);
         // RNS instances: one conditional subtraction per coefficient.  The generic lambda keeps the shift, the mask
         // and three uniform branches PER ELEMENT (round 3, from the ISA).
         if constexpr (PREFETCH) {
@@ -342,9 +333,7 @@ __global__ void __launch_bounds__(ks_threads_tt(LOGN, TT), ks_min_waves(LOGN, TT
                 tile_to_lds<CH, N, T>(lds, src, tid, [&](u64 v) { return lift((v >> sh) & mask_i); });
             }
         }
-        FHE_TSK(1);
         FHE_BARRIER();
-        FHE_TSK(2);
         if constexpr (PREFETCH) {
             if (ii + 1 < nloop) {
                 const u64x2 *nx = reinterpret_cast<const u64x2 *>(src0 + (u64)digit_of(ii + 1) * dstride);
@@ -360,11 +349,10 @@ __global__ void __launch_bounds__(ks_threads_tt(LOGN, TT), ks_min_waves(LOGN, TT
             // transform, so their L2 latency is spent waiting for the other waves, not after them
             constexpr bool KPF = PREFETCH && CH >= 2;
             // (twiddle prefetch measured: no gain here; NARROW: values < 16p on exit, fine for the Shoup MAC)
-            ntt_fwd_lds<LOGN, T, GM, FHE_KS_TWPF && LOGN == 13, !KPF, (F64 ? -(F64 | 8) : NARROW ? (G0 ? 4 : 1) : 0), NoSrc, KS_LATE>(lds, twr, NS + sub, pm, tid);
-            FHE_TSK(7);
+            ntt_fwd_lds<LOGN, T, GM, false, !KPF, (F64 ? -(F64 | 8) : NARROW ? (G0 ? 4 : 1) : 0), NoSrc, KS_LATE>(lds, twr, NS + sub, pm, tid);
             // (all four chunks prefetched -- 118 VGPRs, no scratch: no change; three: 2 % slower.  ABBA runs in
             // profiles/r02_ks_kpf_ab.txt: the key words' latency is not what the MAC waits for)
-            constexpr int KPFN = KPF ? (FHE_KS_KPF_CHUNKS < CH ? FHE_KS_KPF_CHUNKS : CH) : 0;   // chunks whose key words are prefetched
+            constexpr int KPFN = KPF ? (KS_KPF_CHUNKS < CH ? KS_KPF_CHUNKS : CH) : 0;   // chunks whose key words are prefetched
             u64x2 kq[KPF ? 4 * KPFN : 1];
             if constexpr (KPF) {
 #pragma unroll
@@ -372,9 +360,7 @@ __global__ void __launch_bounds__(ks_threads_tt(LOGN, TT), ks_min_waves(LOGN, TT
                     const uint32_t ci = c * T + tid;
                     kq[4 * c] = a0[ci], kq[4 * c + 1] = a0s[ci], kq[4 * c + 2] = a1[ci], kq[4 * c + 3] = a1s[ci];
                 }
-                FHE_TSK(3);
                 FHE_BARRIER();
-                FHE_TSK(4);
             }
 #pragma unroll
             for (int c = 0; c < CH; c++) {
@@ -433,9 +419,7 @@ __global__ void __launch_bounds__(ks_threads_tt(LOGN, TT), ks_min_waves(LOGN, TT
         if constexpr (F64 > 0) f64_terms = f64_terms >= (uint32_t)F64_CAP ? 2u : f64_terms + 1;   // (a reduced accumulator counts as one term)
         // (wave-contiguous chunk ownership, which makes this barrier and the one before the MAC wave-local as
         // well, was measured: nothing beyond what the late pass plan already gives)
-        FHE_TSK(5);
         FHE_BARRIER();
-        FHE_TSK(6);
     }
     // (FHE_DEBUG_KS_NOMEM -- every polynomial aliased to the first: rows, addends and outputs out of L2 -- makes this
     // kernel 11 % faster at C2: what its one workgroup per CU cannot hide.  Requesting the addends during the last
@@ -525,9 +509,7 @@ __global__ void __launch_bounds__(ks_threads_tt(LOGN, TT), ks_min_waves(LOGN, TT
         out0[ooff + tid] = r0;
         out1[ooff + tid] = r1;
     }
-    FHE_TSK(21);   // epilogue: next item's row prefetch, final reductions, addends, stores
     } while (ITEM_LOOP && (item += gridDim.x) < total);
-    FHE_TS_END();
 }
 
 // The same for rows that do not fit LDS (N = 2^(13+G0) >= 32768): one workgroup per (ciphertext,
@@ -546,6 +528,7 @@ __global__ void __launch_bounds__((1 << LOGM) / 8, 4)
                           const DevMod *__restrict__ mods, const u64x2 *__restrict__ tw, uint32_t ndigits, uint32_t lk,
                           uint32_t digit_arg, const u64 *__restrict__ xhat, u64 xhat_poly_stride, uint32_t gal) {
     FHE_DYN_SMEM(u64, lds);   // (gal: see ks_fused_kernel)
+    static_assert(LOGM == 13, "sub-blocks are 8192 points: rows of 16384-point parts go through ks_fused_kernel<14, ..., G0>");
     constexpr int M = 1 << LOGM, T = M / 8, CH = M / (2 * T), NS = 1 << G0;
     constexpr u64 N = (u64)M << G0;
     const uint32_t tid0 = threadIdx.x;

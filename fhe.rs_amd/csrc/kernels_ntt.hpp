@@ -54,18 +54,9 @@ __global__ void __launch_bounds__(ntt_threads_c(LOGM), 4)
         auto to_f = [](u64 v) { return bits_of_f64(f64_from_u64(v)); };
         auto to_c = [&](u64 v) { return to_u64_canonical(f64_of_bits(v), pf); };
         if constexpr (!INVERSE) {
-            auto ld = [&](uint32_t i, uint32_t) { return to_f(load_last<(FHE_PIPE_NT & 2) != 0>(src + i)); };
-            if constexpr (FHE_FWD_DIRECT_STORE && plan_np(LOGM, GMAX) > 1) {
-                constexpr int GL = fwd_plan_g<LOGM, GMAX, plan_np(LOGM, GMAX) - 1, false>();
-                ntt_fwd_lds<LOGM, T, GMAX, true, true, -F64, decltype(ld), false, 1>(lds, twr, nsub + sub, pmf, tid, ld, 0, [&](uint32_t base, const u64 (&x)[1 << GL]) {
-                    u64x2 *d2 = reinterpret_cast<u64x2 *>(dst + base);
-#pragma unroll
-                    for (int e = 0; e < (1 << GL); e += 2) d2[e / 2] = u64x2{to_c(x[e]), to_c(x[e + 1])};
-                });
-            } else {
-                ntt_fwd_lds<LOGM, T, GMAX, true, true, -F64>(lds, twr, nsub + sub, pmf, tid, ld);
-                lds_to_tile<CH, M, T>(lds, dst, tid, to_c);
-            }
+            auto ld = [&](uint32_t i, uint32_t) { return to_f(load_last<PIPE_NT_FWD>(src + i)); };
+            ntt_fwd_lds<LOGM, T, GMAX, true, true, -F64>(lds, twr, nsub + sub, pmf, tid, ld);
+            lds_to_tile<CH, M, T>(lds, dst, tid, to_c);
         } else {
             InvTwFirst<LOGM, T> tw0;
             inv_tw_load(tw0, twr, logn, sub, tid);
@@ -75,7 +66,7 @@ __global__ void __launch_bounds__(ntt_threads_c(LOGM), 4)
 #pragma unroll 8
                 for (uint32_t i = tid; i < (uint32_t)M; i += T) lds[padi(i)] = to_f(row[galois_src_index(sub * M + i, e, logn)]);
             } else {
-                tile_to_lds<CH, M, T, (FHE_PIPE_NT & 4) != 0>(lds, src, tid, to_f);
+                tile_to_lds<CH, M, T, PIPE_NT_INV>(lds, src, tid, to_f);
             }
             FHE_BARRIER();
             ntt_inv_lds<LOGM, T, 0, 0, false, F64>(lds, twr, logn, sub, pmf, tid, true, ninv[2 * mi], ninv[2 * mi + 1], tw0);
@@ -83,22 +74,7 @@ __global__ void __launch_bounds__(ntt_threads_c(LOGM), 4)
         }
     } else if constexpr (!INVERSE) {
         // the first pass reads its groups straight from global memory (no tile staging)
-        if constexpr (FHE_FWD_DIRECT_STORE && plan_np(LOGM, GMAX) > 1) {
-            constexpr int GL = fwd_plan_g<LOGM, GMAX, plan_np(LOGM, GMAX) - 1, false>();
-            auto ld = [&](uint32_t i, uint32_t) { return load_last<(FHE_PIPE_NT & 2) != 0>(src + i); };
-            const u64 p4 = p2 << 1, p8 = p2 << 2, np4 = pm.np2 << 1, np8 = pm.np2 << 2;
-            auto canon = [&](u64 v) {
-                if constexpr (NARROW) v = csub_n(csub_n(v, p8, np8), p4, np4);   // < 16p -> < 4p
-                return csub_n(csub_n(v, p2, pm.np2), p, pm.np);
-            };
-            ntt_fwd_lds<LOGM, T, GMAX, true, true, (NARROW ? FWD_B0 : 0), decltype(ld), false, 1>(lds, twr, nsub + sub, pm, tid, ld, 0, [&](uint32_t base, const u64 (&x)[1 << GL]) {
-                u64x2 *d2 = reinterpret_cast<u64x2 *>(dst + base);
-#pragma unroll
-                for (int e = 0; e < (1 << GL); e += 2) d2[e / 2] = u64x2{canon(x[e]), canon(x[e + 1])};
-            });
-            return;
-        }
-        ntt_fwd_lds<LOGM, T, GMAX, true, true, (NARROW ? FWD_B0 : 0)>(lds, twr, nsub + sub, pm, tid, [&](uint32_t i, uint32_t) { return load_last<(FHE_PIPE_NT & 2) != 0>(src + i); });
+        ntt_fwd_lds<LOGM, T, GMAX, true, true, (NARROW ? FWD_B0 : 0)>(lds, twr, nsub + sub, pm, tid, [&](uint32_t i, uint32_t) { return load_last<PIPE_NT_FWD>(src + i); });
         if constexpr (NARROW) {  // < 16p -> canonical
             const u64 p4 = p2 << 1, p8 = p2 << 2, np4 = pm.np2 << 1, np8 = pm.np2 << 2;
             lds_to_tile<CH, M, T>(lds, dst, tid, [&](u64 v) {
@@ -119,7 +95,7 @@ __global__ void __launch_bounds__(ntt_threads_c(LOGM), 4)
 #pragma unroll 8
             for (uint32_t i = tid; i < (uint32_t)M; i += T) lds[padi(i)] = row[galois_src_index(sub * M + i, e, logn)];
         } else {
-            tile_to_lds<CH, M, T, (FHE_PIPE_NT & 4) != 0>(lds, src, tid, [](u64 v) { return v; });
+            tile_to_lds<CH, M, T, PIPE_NT_INV>(lds, src, tid, [](u64 v) { return v; });
         }
         FHE_BARRIER();
         ntt_inv_lds<LOGM, T, 0, 0, NARROW>(lds, twr, logn, sub, pm, tid, whole, ninv[2 * mi], ninv[2 * mi + 1], tw0);
@@ -219,7 +195,7 @@ __global__ void __launch_bounds__(ntt_threads_c(LOGM), 4)
     };
     // the first inverse pass's per-lane twiddles (56 VGPRs at N = 8192) are requested half-way through the products,
     // when half of the operand registers are free again: their L2 latency then hides behind the remaining
-    // products and the barrier instead of following it (FHE_TENSOR_TW_EARLY=0: after the products, as before)
+    // products and the barrier instead of following it
     const u64x2 *twr = itw + ((u64)r << logn);
     InvTwFirst<LOGM, T> tw0;
     if constexpr (CH > 0) {
@@ -235,7 +211,7 @@ __global__ void __launch_bounds__(ntt_threads_c(LOGM), 4)
             }
 #pragma unroll
             for (int c = 0; c < CH; c++) {
-                if (FHE_TENSOR_TW_EARLY && CH > 1 && c == CH / 2) {
+                if (CH > 1 && c == CH / 2) {
                     sched_fence();
                     inv_tw_load(tw0, twr, logn, sub, tid);
                 }
@@ -264,7 +240,7 @@ __global__ void __launch_bounds__(ntt_threads_c(LOGM), 4)
             }
 #pragma unroll
             for (int c = 0; c < HALF; c++) {
-                if (FHE_TENSOR_TW_EARLY && CH > 1 && h + HALF >= CH && c == HALF / 2) {   // (last batch, half done)
+                if (CH > 1 && h + HALF >= CH && c == HALF / 2) {   // (last batch, half done)
                     sched_fence();
                     inv_tw_load(tw0, twr, logn, sub, tid);
                 }
@@ -278,7 +254,7 @@ __global__ void __launch_bounds__(ntt_threads_c(LOGM), 4)
     } else {
         for (uint32_t i = tid; i < M; i += T) lds[padi(i)] = prod(a0[i], a1[i], b0[i], b1[i]);
     }
-    if (!(FHE_TENSOR_TW_EARLY && CH > 1)) inv_tw_load(tw0, twr, logn, sub, tid);   // in flight across the barrier
+    if (CH <= 1) inv_tw_load(tw0, twr, logn, sub, tid);   // in flight across the barrier
     FHE_BARRIER();
     u64 *dst = out + ((u64)slot * nb + b) * pk + roff;
     // (a block-uniform branch between the narrow and the general inverse passes inside one kernel was measured:

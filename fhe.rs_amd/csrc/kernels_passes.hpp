@@ -12,8 +12,11 @@ namespace k {
 // of 2^G coefficients per thread.  NTT: 16 coefficients per thread (one radix-16 group);
 // key switch: 8 per thread (leaves registers for the two accumulator sets).
 constexpr int ntt_threads_c(int logm) { return (1 << logm) / 16 > 64 ? ((1 << logm) / 16 > 1024 ? 1024 : (1 << logm) / 16) : 64; }
-constexpr bool KS_LATE = FHE_KS_LATE;  // key-switch transforms: wider radix passes last (wave-local exchanges)
+constexpr bool KS_LATE = true;  // key-switch transforms: wider radix passes last (wave-local exchanges)
 constexpr int KS_GMAX = 3;  // radix-8 passes inside the key switch: room for the accumulators
+// chunks of key words requested before the barrier that ends a digit's transform (all four: no change; three: 2 % slower,
+// profiles/r02_ks_kpf_ab.txt)
+constexpr int KS_KPF_CHUNKS = 2;
 constexpr int ks_threads_c(int logn) { return (1 << logn) / 8 > 64 ? ((1 << logn) / 8 > 1024 ? 1024 : (1 << logn) / 8) : 64; }
 // 16-byte chunks per thread (0: tile smaller than one chunk per thread -> scalar loop)
 constexpr int tile_chunks_c(int logm, int threads) { return (1 << logm) >= 2 * threads ? (1 << logm) / (2 * threads) : 0; }
@@ -79,16 +82,11 @@ __device__ __forceinline__ void fwd_tw_load(FwdTw<G, LOGM, S0, T> &tw_regs, cons
 // (canonical residues, or digit rows of another modulus of the launch); values leave below f64_fwd_out_bound().
 // NT > 1: the same pass on NT tiles that lie `tile_words` apart in LDS (the key switch transforms two digits
 // under one modulus at once): addresses and twiddles are formed once and serve every tile.
-// `Dst` (last pass only, lab knob FHE_FWD_DIRECT_STORE): a functor (first index, x[]) that takes the group's 2^G
-// CONSECUTIVE results straight from the registers (the stride-1 pass: lo_bits == 0) instead of the tile.
-template <int G, int LOGM, int S0, int T, bool PRE, int NARROW = 0, class Src = NoSrc, int NT = 1, bool WLX = false,
-          class Dst = NoSrc>
+template <int G, int LOGM, int S0, int T, bool PRE, int NARROW = 0, class Src = NoSrc, int NT = 1, bool WLX = false>
 __device__ __forceinline__ void fwd_pass(u64 *lds, const u64x2 *__restrict__ tw, uint32_t kbase, const PM pm,
                                          uint32_t tid, const FwdTw<G, LOGM, S0, T> &tw_regs, Src src = Src{},
-                                         uint32_t tile_words = 0, Dst dst = Dst{}) {
+                                         uint32_t tile_words = 0) {
     constexpr bool DIRECT = !std::is_same<Src, NoSrc>::value;
-    constexpr bool DIRECT_OUT = !std::is_same<Dst, NoSrc>::value;
-    static_assert(!DIRECT_OUT || (S0 + G == LOGM && NT == 1), "direct stores: the last (stride-1) pass of one tile");
     constexpr uint32_t R = 1u << G;
     constexpr uint32_t lo_bits = LOGM - S0 - G;
     constexpr uint32_t ngroups = 1u << (LOGM - G);
@@ -160,12 +158,8 @@ __device__ __forceinline__ void fwd_pass(u64 *lds, const u64x2 *__restrict__ tw,
                 }
             }
         }
-        if constexpr (DIRECT_OUT) {
-            dst(base, x);
-        } else {
 #pragma unroll
         for (uint32_t e = 0; e < R; e++) g[padi(e << lo_bits)] = x[e];
-        }
         if constexpr (NT > 1) sched_fence();   // one tile's group in registers at a time
         }
     }
@@ -217,21 +211,16 @@ constexpr bool fwd_wl_after(int logm, int gm, bool late, int pass) {
 // TWPF: fetch the next pass's per-lane twiddles before the barrier (costs their registers across
 // it: the key-switch kernels, which also hold accumulators, leave it off).
 // FSYNC = false: the caller places the barrier after the last pass itself (it has loads to issue first).
-template <int LOGM, int T, int GM, bool TWPF, bool FSYNC, int NARROW, int PASS, int S0, bool LATE, int NT, class W, class Src,
-          class Dst = NoSrc>
+template <int LOGM, int T, int GM, bool TWPF, bool FSYNC, int NARROW, int PASS, int S0, bool LATE, int NT, class W, class Src>
 __device__ __forceinline__ void ntt_fwd_lds_rec(u64 *lds, const u64x2 *__restrict__ tw, uint32_t kbase, const PM pm,
-                                                uint32_t tid, const W &tw_regs, Src src, uint32_t tile_words, Dst dst = Dst{}) {
+                                                uint32_t tid, const W &tw_regs, Src src, uint32_t tile_words) {
     constexpr int G = fwd_plan_g<LOGM, GM, PASS, LATE>();
-    constexpr bool OUT = !std::is_same<Dst, NoSrc>::value && PASS + 1 == fwd_np(LOGM, GM);   // this pass stores to `dst`
     constexpr bool WLX = fwd_wl_after(LOGM, GM, LATE, PASS) || fwd_wl_after(LOGM, GM, LATE, PASS - 1);
     static_assert(!WLX || T % 64 == 0, "wave-local exchanges need whole 64-lane waves");
-    if constexpr (OUT && PASS != 0)
-        fwd_pass<G, LOGM, S0, T, TWPF, NARROW, NoSrc, NT, WLX, Dst>(lds, tw, kbase, pm, tid, tw_regs, NoSrc{}, tile_words, dst);
-    else if constexpr (PASS == 0)
+    if constexpr (PASS == 0)
         fwd_pass<G, LOGM, S0, T, TWPF, NARROW, Src, NT, WLX>(lds, tw, kbase, pm, tid, tw_regs, src, tile_words);   // (Src != NoSrc: reads `src`, not LDS)
     else
         fwd_pass<G, LOGM, S0, T, TWPF, NARROW, NoSrc, NT, WLX>(lds, tw, kbase, pm, tid, tw_regs, NoSrc{}, tile_words);
-    FHE_TS(8 + 2 * PASS);
     if constexpr (PASS + 1 < fwd_np(LOGM, GM)) {
         constexpr int GN = fwd_plan_g<LOGM, GM, PASS + 1, LATE>();
         FwdTw<GN, LOGM, S0 + G, T> next;
@@ -242,22 +231,20 @@ __device__ __forceinline__ void ntt_fwd_lds_rec(u64 *lds, const u64x2 *__restric
             wave_sync();
         else
             FHE_BARRIER();
-        FHE_TS(9 + 2 * PASS);
         ntt_fwd_lds_rec<LOGM, T, GM, TWPF, FSYNC, NARROW, PASS + 1, S0 + G, LATE, NT>(lds, tw, kbase, pm, tid, next, NoSrc{},
-                                                                                      tile_words, dst);
+                                                                                      tile_words);
     } else {
-        if constexpr (FSYNC && !OUT) FHE_BARRIER();
+        if constexpr (FSYNC) FHE_BARRIER();
     }
 }
 template <int LOGM, int T, int GM = GMAX, bool TWPF = true, bool FSYNC = true, int NARROW = 0, class Src = NoSrc,
-          bool LATE = false, int NT = 1, class Dst = NoSrc>
+          bool LATE = false, int NT = 1>
 __device__ __forceinline__ void ntt_fwd_lds(u64 *lds, const u64x2 *__restrict__ tw, uint32_t kbase, const PM pm,
-                                            uint32_t tid, Src src = Src{}, uint32_t tile_words = 0, Dst dst = Dst{}) {
+                                            uint32_t tid, Src src = Src{}, uint32_t tile_words = 0) {
     constexpr int G = fwd_plan_g<LOGM, GM, 0, LATE>();
-    static_assert(std::is_same<Dst, NoSrc>::value || fwd_np(LOGM, GM) > 1, "direct stores need a pass of their own");
     FwdTw<G, LOGM, 0, T> first;
     if constexpr (TWPF) fwd_tw_load(first, tw, kbase, tid);
-    ntt_fwd_lds_rec<LOGM, T, GM, TWPF, FSYNC, NARROW, 0, 0, LATE, NT>(lds, tw, kbase, pm, tid, first, src, tile_words, dst);
+    ntt_fwd_lds_rec<LOGM, T, GM, TWPF, FSYNC, NARROW, 0, 0, LATE, NT>(lds, tw, kbase, pm, tid, first, src, tile_words);
 }
 
 // ---------------------------------------------------------------- inverse passes ----
@@ -301,12 +288,12 @@ __device__ __forceinline__ void inv_tw_load(InvTw<G, LOGM, V0, T> &tw_regs, cons
 // multiplication and is below 2p again -- and `bnd[]` tracks every register's bound (in units of p)
 // through the fully unrolled stages, so the conditional subtractions shrink to the few needed to keep
 // sums below 16p and to hand the next pass values below 2p (7 instead of 12 per radix-8 group).
-// FHE_APPROX_SHOUP (zq_dev.hpp): the narrow passes also take the three-partial-product quotient -- the product is
+// The narrow passes also take (zq_dev.hpp mulhi64_approx) the three-partial-product quotient -- the product is
 // then below 3p instead of 2p, `bnd[]` holds any integer up to 16, conditional subtractions pick the multiple of p
 // (8p, 4p, 2p, p) that leaves the smallest bound, and values travel between passes below BIN / BOUT = 4 p (first
 // pass in: 2p; last pass out: 2p, through the exact quotient of the folded last stage): one v_mul_hi_u32 less per
 // butterfly for one more conditional subtraction per radix-8 group (8 instead of 7; 20 instead of 16 per radix-16).
-constexpr int INV_NARROW_MID = FHE_APPROX_SHOUP ? 4 : 2;
+constexpr int INV_NARROW_MID = 4;
 constexpr int inv_best_c(int bd) {   // the power of two c <= 8, c < bd, that minimises max(c, bd - c)
     int best = 1, bv = bd - 1;
     for (int c = 2; c <= 8; c *= 2)
@@ -416,14 +403,10 @@ __device__ __forceinline__ void inv_pass(u64 *lds, const u64x2 *__restrict__ itw
                             x[b] = mul_shoup_lazy_n<true>(diff, zninv.x, zninv.y, pm.np);
                         } else {
                             x[a] = y + t;
-#if FHE_APPROX_SHOUP
                             x[b] = shoup_lo<UNIFORM, false>(0, diff, zv.x, mulhi64_approx<UNIFORM>(diff, zv.y), pm.np);   // below 3p
-#else
-                            x[b] = mul_shoup_lazy_n<UNIFORM>(diff, zv.x, zv.y, pm.np);
-#endif
                         }
                         bnd[a] = bnd[a] + bnd[b];  // (kept independent of the run-time `fold`)
-                        bnd[b] = FHE_APPROX_SHOUP ? 3 : 2;
+                        bnd[b] = 3;
                     } else if (V0 + G == LOGM && u == G - 1 && fold) {
                         const u64 t = x[a], y = x[b];
                         x[a] = mul_shoup_lazy_n<true>(y + t, ninv.x, ninv.y, pm.np);

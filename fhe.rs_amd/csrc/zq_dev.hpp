@@ -14,8 +14,6 @@
 #pragma once
 #include <cstdint>
 
-#include "knobs.hpp"
-
 #if defined(__HIPCC__) || defined(__HIP__)
 #define FHE_HD __host__ __device__ __forceinline__
 #else
@@ -36,7 +34,7 @@ struct DevMod {  // layout == hostmath.hpp ModConsts
 // (Round 2 priced the instruction stream with timing-only builds that computed WRONG residues on purpose -- fewer
 // partial products, no barriers, a pseudo-Mersenne fold; results in DESIGN.md section 6, sources in the history up to
 // commit db30352.  None of that is in this file any more: every path here is exact.)
-// The high product through v_mad_u64_u32's carry-out (FHE_MAD_CARRY, default on; the device compiler has no way to
+// The high product through v_mad_u64_u32's carry-out (the device compiler has no way to
 // ask for it): the two cross products are summed by the multiply-add itself, their carry leaves in an SGPR pair and
 // joins the upper half of the sum as the 64-bit addend of the last multiply -- one v_mul_hi, three multiply-adds, a
 // move and a select instead of the four multiplies plus ~six moves / 64-bit adds of the generic expansion (gfx950
@@ -44,7 +42,7 @@ struct DevMod {  // layout == hostmath.hpp ModConsts
 // SU: `b` is wave-uniform and stays in scalar registers (one constant-bus operand per instruction).
 // Every asm statement is a single instruction, so the scheduler still interleaves neighbouring butterflies; the
 // s_nop covers the two wait states gfx950 wants between a VALU write of an SGPR and a VALU read of it.
-#if defined(__HIP_DEVICE_COMPILE__) && FHE_MAD_CARRY
+#if defined(__HIP_DEVICE_COMPILE__)
 #define FHE_HAVE_MAD_CARRY 1
 template <bool SU>
 __device__ __forceinline__ u64 mad64_carry(uint32_t a, uint32_t b, u64 add, u64 &carry) {
@@ -85,49 +83,15 @@ __device__ __forceinline__ u64 mulhi64_approx_c(u64 a, u64 b) {
 #endif
 
 // add + a*b + q*np (mod 2^64): the low word of a lazy Shoup product, with an optional addend.
-// FHE_MAD_CROSS: the four 32-bit cross products (a0*b1, a1*b0, q0*np1, q1*np0: only their low words count) are
-// summed by a chain of v_mad_u64_u32 used as a 32-bit multiply-add (the upper half of its result is junk), and
-// their sum joins the upper word with one add -- 6 multiply-adds + 1 add against the compiler's 2 multiply-adds,
-// 4 v_mul_lo_u32 and 2 v_add3_u32.  SU: b is wave-uniform (np always is).
+// SU: b is wave-uniform (np always is).
 template <bool SU = false, bool ADD = true>
 FHE_HD u64 shoup_lo(u64 add, u64 a, u64 b, u64 q, u64 np) {
-#if defined(__HIP_DEVICE_COMPILE__) && FHE_MAD_CROSS
-    const uint32_t a0 = (uint32_t)a, a1 = (uint32_t)(a >> 32), b0 = (uint32_t)b, b1 = (uint32_t)(b >> 32);
-    const uint32_t q0 = (uint32_t)q, q1 = (uint32_t)(q >> 32), n0 = (uint32_t)np, n1 = (uint32_t)(np >> 32);
-    u64 t, r, sd;
-    constexpr bool no_add = !ADD;   // (no addend: the inline constant 0, not a register pair holding it)
-    if constexpr (SU) {
-        asm("v_mad_u64_u32 %0, %1, %2, %3, 0" : "=v"(t), "=s"(sd) : "v"(a0), "s"(b1));
-        asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(t), "=s"(sd) : "v"(a1), "s"(b0), "v"(t));
-        if constexpr (no_add)
-            asm("v_mad_u64_u32 %0, %1, %2, %3, 0" : "=v"(r), "=s"(sd) : "v"(a0), "s"(b0));
-        else
-            asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(sd) : "v"(a0), "s"(b0), "v"(add));
-    } else {
-        asm("v_mad_u64_u32 %0, %1, %2, %3, 0" : "=v"(t), "=s"(sd) : "v"(a0), "v"(b1));
-        asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(t), "=s"(sd) : "v"(a1), "v"(b0), "v"(t));
-        if constexpr (no_add)
-            asm("v_mad_u64_u32 %0, %1, %2, %3, 0" : "=v"(r), "=s"(sd) : "v"(a0), "v"(b0));
-        else
-            asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(sd) : "v"(a0), "v"(b0), "v"(add));
-    }
-    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(t), "=s"(sd) : "v"(q0), "s"(n1), "v"(t));
-    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(t), "=s"(sd) : "v"(q1), "s"(n0), "v"(t));
-    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(sd) : "v"(q0), "s"(n0), "v"(r));
-    // (written as a 64-bit add the compiler builds the pair {0, t.lo} with two moves and adds it with v_lshl_add_u64)
-    uint32_t rh;
-    asm("v_add_u32 %0, %1, %2" : "=v"(rh) : "v"((uint32_t)(r >> 32)), "v"((uint32_t)t));
-    return ((u64)rh << 32) | (uint32_t)r;
-#else
     return (ADD ? add : 0) + a * b + q * np;
-#endif
 }
 
 FHE_HD u64 mulhi64(u64 a, u64 b) {
-#if defined(__HIP_DEVICE_COMPILE__) && FHE_MAD_CARRY
+#if FHE_HAVE_MAD_CARRY
     return mulhi64_c<false>(a, b);
-#elif defined(__HIP_DEVICE_COMPILE__)
-    return __umul64hi(a, b);
 #else
     return (u64)(((u128_t)a * b) >> 64);
 #endif
@@ -284,11 +248,11 @@ FHE_HD void fwd_butterfly(u64 &x, u64 &y, u64 w, u64 ws, const PM &m) {
 // (t < 2p whatever y is); fwd_narrow_bound() tracks b over the stages of a transform whose input is
 // below b0*p (1: canonical) and says where the one strong correction (x < 16p -> x < 4p) has to sit.
 //
-// FHE_APPROX_SHOUP (default on): the headroom also pays for a cheaper quotient.  floor(y * ws / 2^64) is formed
+// The headroom also pays for a cheaper quotient.  floor(y * ws / 2^64) is formed
 // from three of its four 32 x 32 partial products (y0 * ws0 only feeds a carry): the estimate is the true quotient
 // or one less, so t = y*w - q'*p is below 3p instead of 2p -- one multiply and its register shuffling less per
 // butterfly -- and every stage grows the bound by 3p: outputs x + t and x + 3p - t are below (b + 3) p.
-constexpr int FWD_NARROW_STEP = FHE_APPROX_SHOUP ? 3 : 2;
+constexpr int FWD_NARROW_STEP = 3;
 constexpr int fwd_narrow_bound(int stage, int b0 = 1) {  // b before `stage`, b0 before stage 0
     int b = b0;
     for (int s = 0; s < stage; s++) b = (b > 16 - FWD_NARROW_STEP ? 4 : b) + FWD_NARROW_STEP;
@@ -316,13 +280,8 @@ FHE_HD void fwd_butterfly_narrow(u64 &x, u64 &y, u64 w, u64 ws, const PM &m, boo
     }
     // (x + t formed inside the product chain, x + pk - t as (2x + pk) - (x + t): see fwd_butterfly; 2x may wrap
     // around 2^64, the difference is exact because x + pk - t < 16p < 2^64)
-#if FHE_APPROX_SHOUP
     const u64 xt = shoup_lo<SU>(x, y, w, mulhi64_approx<SU>(y, ws), m.np);   // t below 3p
     const u64 pk = m.p2 + m.p;
-#else
-    const u64 xt = shoup_lo<SU>(x, y, w, mulhi64_t<SU>(y, ws), m.np);
-    const u64 pk = m.p2;
-#endif
 #if defined(FHE_HOST_EMULATION)
     if (xt - x >= pk || x > ~0ull - pk) __builtin_trap();  // range tracking broken
 #endif

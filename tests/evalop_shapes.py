@@ -4,8 +4,9 @@ fixed list of shapes that reaches every instance a release build can launch.
 
 A cell is (family, template arguments as the profiler prints them, run-time coordinates).  The tables follow the
 dispatcher of csrc/engine.hpp (with_logn, with_row_kind, with_bool, with_tile, launch_ntt, launch_tensor_intt,
-launch_ks_fused, launch_ks_ntt, key_switch_polys) for the release build: knobs.hpp pins FHE_KS_HALF15 = 2,
-FHE_KS12_F64_T256 = 0, FHE_KS_PERSIST14 = 0, no lab path exists, and N = 16384 runs GM_MIXED (32) passes.
+launch_ks_fused, launch_ks_ntt, key_switch_polys): rows larger than LDS run as 16384-point parts on the RNS loader
+where the key's digits are residue rows, the F64 key switch at N = 4096 keeps 512 threads x 8, only N = 8192 runs the
+resident item loop, and N = 16384 runs GM_MIXED (32) passes.
 
 Row kinds, as in devop_shapes: general (a modulus >= 2^60), narrow (all below 2^60), and for whole rows of 4096 ... 16384
 points the F64 classes 3 / 4 / 5 (widest modulus in [2^49, 2^50) / [2^48, 2^49) / below 2^48).
@@ -100,23 +101,15 @@ COUNTS = {"ntt_kernel": 82, "ntt_global_kernel": 4, "tensor_intt_kernel": 35, "k
           "ks_fused_split_kernel": 8, "ks_ntt_kernel": 51, "ks_mac_kernel": 1}
 assert {f: len(c) for f, c in REACHABLE.items()} == COUNTS and tuple(REACHABLE) == FAMILIES
 
-# compiled, and called by no release path
-UNREACHABLE = {
-    ("ks_fused_split_kernel", _a(1, 13, nw, rns)): "key_switch_polys instantiates the split kernel through with_logn<14, 16>, "
-    "but N = 16384 always takes ks_fused_kernel<14> (the two-sub-block form is a lab switch, FHE_LAB_KS_SPLIT14)"
-    for nw in (False, True) for rns in (False, True)}
-# (found by tests/test_evalop_isa.py: the issue's count did not have them)
-UNREACHABLE.update({
-    ("ks_fused_kernel", _a(14, nw, gm, 0, False, 0, gal, 0)): "launch_ks_fused<14> names the radix-4 (GM = 2) and radix-8 "
-    "(GM = 3) plans behind `plan14`, which is the constant 0 outside lab builds (FHE_LAB_KS14_PLAN): GM_MIXED always runs"
-    for nw in (False, True) for gm in (2, KS_GMAX) for gal in (False, True)})
+# compiled, and called by no release path: {(family, args): reason}
+UNREACHABLE = {}
 
 
 def all_cells():
     return set().union(*REACHABLE.values())
 
 
-assert len(all_cells()) == 259 and len(UNREACHABLE) == 12 and not all_cells() & set(UNREACHABLE)
+assert len(all_cells()) == 259 and not UNREACHABLE
 
 
 # ---- run-time coordinates ------------------------------------------------------------------------------------------------

@@ -26,11 +26,7 @@ def test_table_counts():
     assert S.COUNTS == {"ntt_kernel": 82, "ntt_global_kernel": 4, "tensor_intt_kernel": 35, "ks_fused_kernel": 78,
                         "ks_fused_split_kernel": 8, "ks_ntt_kernel": 51, "ks_mac_kernel": 1}
     assert len(S.all_cells()) == 259
-    by_family = {}
-    for fam, _args in S.UNREACHABLE:
-        by_family[fam] = by_family.get(fam, 0) + 1
-    assert by_family == {"ks_fused_split_kernel": 4, "ks_fused_kernel": 8}
-    assert all(reason for reason in S.UNREACHABLE.values())
+    assert S.UNREACHABLE == {}   # no family has an instance that is compiled and cannot be launched
     # every coordinate names a reachable cell
     assert {(f, a) for f, a, _c in S.required_coords()} <= S.all_cells()
 

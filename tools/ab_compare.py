@@ -2,7 +2,7 @@
 """A/B harness used for every kernel experiment of the round: runs the C2 ct x ct + relinearise
 pipeline (batch 1024) three times per library and prints the per-kernel HIP-event totals of 5
 steps, alternating between the tree's build ("default") and any other builds dropped into
-tools/_variants/*.so (e.g. the previous build, or one compiled with an experiment macro).
+tools/_variants/*.so (e.g. the previous build, or a release build of another commit).
 Alternation within ONE gpurun call matters: boxes of the pool differ by several percent.
 
     cp fhe.rs_amd/libfhe_hip.so tools/_variants/libB.so   # keep the old build

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Relinearise (= one key switch + the add) timed on one shape with the in-tree library or a lab variant:
+"""Relinearise (= one key switch + the add) timed on one shape with the in-tree library or another release build (tools/_variants/):
 usage: python tools/ks_relin_time.py <lib|default> <n> <nmoduli> <batch> [<batch> ...]   -- prints {batch: ms per call}"""
 import json
 import os

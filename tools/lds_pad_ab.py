@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One JSON object per process: the workloads of the LDS-padding A/B (round 6: FHE_LDS_PAD, two lab builds) -- batch transforms
+"""One JSON object per process: the workloads of the LDS-padding A/B (round 6: two builds of the library that differ in padi / lds_words; the alternative layout is retired, docs/HISTORY.md) -- batch transforms
 on 60-bit / 62-bit / F64 rows, the stock n = 8192 set's relinearise and multiply, the C2 multiply, C3's relinearise."""
 import json
 import os
