@@ -7,7 +7,7 @@ The directory is literally called `fhe.rs_amd`, which Python cannot import by st
 from . import _lib  # noqa: F401
 from .api import *  # noqa: F401,F403
 from .api import (Context, Scaler, Switcher, KeySwitchingKey, RelinearizationKey, GaloisKey, EvaluationKey, KeySet, EvaluationKeySet,
-                  HoistedRotations, BsgsRotations, RGSWCiphertext,
+                  HoistedRotations, KeyedHoistedRotations, BsgsRotations, RGSWCiphertext,
                   BfvParameters, Encoder, SecretKey, PublicKey, Multiplicator, FheError, Stream, DeviceArray,
                   CommonRandomPoly, PublicKeyShare, SecretKeySwitchShare, DecryptionShare, PublicKeySwitchShare,
                   RelinKeyGenerator, RelinKeyShare)  # noqa: F401

@@ -139,6 +139,8 @@ SIGNATURES = {
     "fhe_bfv_expand_keyed_dev": (i32, [C.POINTER(vp), sz, vp, vp, sz, sz, vp]),
     "fhe_bfv_galois_hoisted_dev": (i32, [vp, szp, sz, vp, vp, sz, vp]),
     "fhe_bfv_matvec_hoisted_dev": (i32, [vp, szp, sz, vp, vp, i32, vp, vp, sz, vp]),
+    "fhe_bfv_galois_hoisted_keyed_dev": (i32, [vp, sz, szp, sz, vp, vp, sz, vp]),
+    "fhe_bfv_matvec_hoisted_keyed_dev": (i32, [vp, sz, szp, sz, vp, vp, i32, vp, vp, sz, vp]),
     "fhe_bfv_matvec_bsgs_dev": (i32, [vp, szp, sz, vp, szp, sz, vp, vp, i32, vp, sz, vp]),
     "fhe_mul_create": (i32, [vp, vp, vp, vp, i32, C.POINTER(vp)]),
     "fhe_mul_destroy": (None, [vp]),

@@ -1372,6 +1372,50 @@ class KeySet:
                                            None if p0 is None else _dptr(p0), _dptr(out), b, _stream()))
         return out.download() if host else out
 
+    def relinearize_hoisted_keyed(self, nclients, exponents, ct):
+        """Hoisted rotations with one Galois key set per client (fhe_bfv_galois_hoisted_keyed_dev): the set holds
+        nclients * R keys CLIENT-MAJOR, entry c * R + r being client c's key for exponents[r]; items [c * m, (c + 1) * m),
+        m = batch / nclients, belong to client c.  [batch, 2, L, N] Ntt -> [batch, R, 2, L, N], word for word one
+        relinearize_hoisted call per client on the client's keys and slice of the batch (not the reference's words)."""
+        L = _lib.lib()
+        ctx = self.ctx_ciphertext
+        if ct.shape[-3] != 2:
+            raise FheError(-13, "InvalidPolynomialCount: rotation expects 2 parts")
+        exps = [int(e) for e in exponents]
+        arr = (C.c_size_t * max(len(exps), 1))(*exps)
+        b = ctx._batch(ct) // 2
+        oshape = tuple(ct.shape[:-3]) + (len(exps),) + tuple(ct.shape[-3:])
+        return self._run(ct, [oshape], lambda d, o: L.fhe_bfv_galois_hoisted_keyed_dev(
+            self._h, int(nclients), arr, len(exps), _dptr(d), _dptr(o[0]), b, _stream()))[0]
+
+    def matvec_hoisted_keyed(self, nclients, exponents, ct, pts, pt0=None):
+        """Hoisted matrix-vector product with one Galois key set per client (fhe_bfv_matvec_hoisted_keyed_dev): the set and
+        the ownership rule of relinearize_hoisted_keyed, the shapes of matvec_hoisted -- pts [R, L, N] shared by the WHOLE
+        batch or [batch, R, L, N], pt0 None, [L, N] or [batch, L, N] likewise -> [batch, 2, L, N], of ct's kind.  Word for
+        word one matvec_hoisted call per client on the client's keys and slices of ct, pts and pt0."""
+        L = _lib.lib()
+        ctx = self.ctx_ciphertext
+        if ct.shape[-3] != 2:
+            raise FheError(-13, "InvalidPolynomialCount: rotation expects 2 parts")
+        exps = [int(e) for e in exponents]
+        arr = (C.c_size_t * max(len(exps), 1))(*exps)
+        lead = tuple(ct.shape[:-3])
+        b = ctx._batch(ct) // 2
+        shared = len(pts.shape) == 3
+        want = ((len(exps),) if shared else lead + (len(exps),)) + (ctx.nmoduli, ctx.degree)
+        if tuple(pts.shape) != want:
+            raise FheError(-1, "DotProductLengthMismatch: diagonals %s, expected %s" % (tuple(pts.shape), want))
+        if pt0 is not None and tuple(pt0.shape) != (() if shared else lead) + (ctx.nmoduli, ctx.degree):
+            raise FheError(-1, "DotProductLengthMismatch: the identity diagonal follows the diagonals' batch shape")
+        host = not _is_dev(ct)
+        dev = max(self.ctx_ksk.device, 0)
+        stage = (lambda a: DeviceArray.from_numpy(_np(a), dev)) if host else (lambda a: a)
+        d, p, p0 = stage(ct), stage(pts), (None if pt0 is None else stage(pt0))
+        out = DeviceArray(tuple(ct.shape), dev) if host else _empty_dev(d, tuple(ct.shape))
+        check(L.fhe_bfv_matvec_hoisted_keyed_dev(self._h, int(nclients), arr, len(exps), _dptr(d), _dptr(p), 1 if shared else 0,
+                                                 None if p0 is None else _dptr(p0), _dptr(out), b, _stream()))
+        return out.download() if host else out
+
     def matvec_bsgs(self, baby_exps, giant_set, giant_exps, ct, pts):
         """Baby-step/giant-step hoisted matrix-vector product (fhe_bfv_matvec_bsgs_dev): this set holds ONE client's baby
         Galois keys (key r for baby_exps[r]), `giant_set` the giant keys.  ct [batch, 2, L, N] Ntt (or [2, L, N]); pts
@@ -1434,6 +1478,25 @@ class EvaluationKeySet:
         self._need([e], "ColumnRotation")
         return self.sets[e].relinearize(e, ct)
 
+    def hoisted(self, column_rotations=(), row_rotation=False):
+        """EvaluationKey.hoisted for every client at once: the rotations `column_rotations` (steps, in this order) and
+        then the row rotation as ONE hoisted call per batch, each ciphertext under its owner's keys -- a
+        `KeyedHoistedRotations`.  A missing key or a bad step raises what EvaluationKey.hoisted raises."""
+        exps = []
+        for i in column_rotations:
+            if not (1 <= i < self.degree // 2):
+                raise FheError(-1, "InvalidRotationStep")
+            e = pow(3, i, 2 * self.degree)
+            self._need([e], "ColumnRotation")
+            exps.append(e)
+        if row_rotation:
+            e = 2 * self.degree - 1
+            self._need([e], "RowRotation")
+            exps.append(e)
+        if not exps:
+            raise FheError(-1, "hoisted rotations: no rotation was asked for")
+        return KeyedHoistedRotations(self.nclients, [[self.sets[e].keys[c] for e in exps] for c in range(self.nclients)])
+
     def computes_inner_sum(self, ct):
         """EvaluationKey::computes_inner_sum (evaluation_key.rs:56-100) per client."""
         n = self.degree
@@ -1470,6 +1533,30 @@ class EvaluationKeySet:
         b = first.ctx_ciphertext._batch(ct) // 2
         return first._run(ct, [(size,) + tuple(ct.shape)], lambda d, o: L.fhe_bfv_expand_keyed_dev(
             handles, level, _dptr(d), _dptr(o[0]), size, b, _stream()))[0]
+
+
+class KeyedHoistedRotations:
+    """`EvaluationKeySet.hoisted(...)`: HoistedRotations for many clients in one call (KeySet.relinearize_hoisted_keyed,
+    KeySet.matvec_hoisted_keyed).  `set` is ONE KeySet over the clients' Galois keys in client-major order (client c's
+    key for exponents[r] at c * R + r), built once; items [c * m, (c + 1) * m) of a batch belong to client c.
+    rotate(ct): [batch, 2, L, N] -> [batch, R, 2, L, N]; matvec(ct, pts, pt0): pt0 * ct + sum_r pts[r] * rotation_r(ct)
+    -> [batch, 2, L, N], the diagonals shared by the whole batch or one set per item.  Word for word HoistedRotations
+    client by client, and like it not the reference's words (include/fhe_hip.h)."""
+
+    def __init__(self, nclients, client_keys):
+        self.nclients = int(nclients)
+        self.keys = [list(row) for row in client_keys]
+        self.exponents = [g.exponent for g in self.keys[0]]
+        self.set = KeySet([g.ksk for row in self.keys for g in row])
+
+    def __len__(self):
+        return len(self.exponents)
+
+    def rotate(self, ct):
+        return self.set.relinearize_hoisted_keyed(self.nclients, self.exponents, ct)
+
+    def matvec(self, ct, pts, pt0=None):
+        return self.set.matvec_hoisted_keyed(self.nclients, self.exponents, ct, pts, pt0)
 
 
 class RGSWCiphertext:

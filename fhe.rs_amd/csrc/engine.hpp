@@ -2108,10 +2108,16 @@ inline void galois_apply(const Ksk &ks, size_t exponent, const u64 *ct, u64 *out
 // b0 and nb still count ciphertexts.  The budget rule is the same with a ciphertext costing `granule`
 // rows per digit and key modulus; where the budget is below one ciphertext's items at one key modulus the chunk is one
 // ciphertext (pc = max(1, ...)).  granule = 1: the ciphertexts themselves, what galois_hoisted and matvec_hoisted launch.
-inline std::vector<uint32_t> hoist_exponents(const KskSet &set, const size_t *exponents, size_t nrot, const std::string &what) {
+// nclients (the keyed forms): the set holds nclients x nrot keys, client-major, and the list has one exponent per rotation.
+inline std::vector<uint32_t> hoist_exponents(const KskSet &set, const size_t *exponents, size_t nrot, const std::string &what,
+                                             size_t nclients = 1) {
     const Ctx &kc = *set.ksk_ctx, &cc = *set.ct_ctx;
     require(exponents != nullptr, E_ARG, "null argument: exponents");
-    require(nrot == set.keys.size(), E_ARG, (what + ": one exponent per key of the set").c_str());
+    if (nclients == 1)
+        require(nrot == set.keys.size(), E_ARG, (what + ": one exponent per key of the set").c_str());
+    else
+        require(nclients != 0 && nrot == set.keys.size() / nclients && nclients * nrot == set.keys.size(), E_ARG,
+                (what + ": one exponent per key of a client, clients x exponents keys in the set").c_str());
     std::vector<uint32_t> exps(nrot);
     for (size_t r = 0; r < nrot; r++) {
         exps[r] = (uint32_t)(exponents[r] % (2 * kc.n));
@@ -2199,6 +2205,36 @@ inline void galois_hoisted(const KskSet &set, const size_t *exponents, size_t nr
     });
 }
 
+// Hoisted rotations with one Galois key set per client (kernels_kshoistkeyed.hpp): `set` holds nclients x nrot keys,
+// client-major (entry c * nrot + r: client c's key for exponents[r]); with m = batch / nclients, ciphertexts
+// [c m, (c + 1) m) belong to client c.  Word for word galois_hoisted client by client on each client's nrot keys and slice
+// of `ct`, in galois_hoisted's launches: stage A reads no key, so hoist_each_w serves as it stands (its b0 is the
+// item0 of a launch: a chunk need not end on a client boundary), and on each W one hoist_mac_keyed_kernel launch per
+// k::HOIST_ROTS rotations, however many clients there are.
+inline void galois_hoisted_keyed(const KskSet &set, size_t nclients, const size_t *exponents, size_t nrot, const u64 *ct, u64 *out,
+                                 size_t batch, hipStream_t s) {
+    const Ctx &kc = *set.ksk_ctx, &cc = *set.ct_ctx;
+    const std::vector<uint32_t> exps = hoist_exponents(set, exponents, nrot, "keyed hoisted rotations", nclients);
+    require(batch % nclients == 0, E_ARG, "keyed hoisted rotations: the batch is a multiple of the clients");
+    if (!batch) return;
+    const size_t per_client = batch / nclients;
+    const u64 PL = (u64)cc.L * kc.n;
+    require(!(out < ct + batch * 2 * PL && ct < out + batch * nrot * 2 * PL), E_ARG,
+            "hoisted rotations: `out` overlaps `ct` (every rotation gathers from the whole input)");
+    hoist_each_w(set, ct, batch, s, [&](size_t b0, size_t nb, size_t j0, size_t njg, const u64 *w) {
+        for (size_t r0 = 0; r0 < nrot; r0 += k::HOIST_ROTS) {
+            const size_t nr = std::min<size_t>(k::HOIST_ROTS, nrot - r0);
+            const k::HoistExps he = hoist_exps_arg(exps, r0, nr);
+            const unsigned grid_b = hoist_grid_b(kc, njg, nb, nr);
+            u64 *o = out + (b0 * nrot + r0) * 2 * PL;
+            FHE_LAUNCH("hoist_mac_keyed", k::hoist_mac_keyed_kernel, dim3(grid_b), dim3(256), 0, s, w, o, o + PL,
+                       (u64)nrot * 2 * PL, 2 * PL, ct + b0 * 2 * PL, 2 * PL, set.table.p, (uint32_t)b0, (uint32_t)per_client,
+                       (uint32_t)nclients, (uint32_t)nrot, (uint32_t)r0, he, kc.dmods(), (uint32_t)set.ndigits, (uint32_t)kc.L,
+                       (uint32_t)j0, (uint32_t)njg, (uint32_t)kc.logn, ct + b0 * 2 * PL + PL, 2 * PL, (uint32_t)nb, (uint32_t)nr);
+        }
+    });
+}
+
 // The rotation groups of one hoist_matvec_kernel launch over nr rotations (the ONE statement of the rule).  A block per
 // (ciphertext, key range) leaves a small batch short of the device -- batch 1 at N = 8192 x 4 moduli is 64 blocks -- so
 // the rotations are cut into groups whose blocks run side by side until the launch has two blocks per compute unit
@@ -2281,6 +2317,59 @@ inline void matvec_hoisted(const KskSet &set, const size_t *exponents, size_t nr
                        l.r0 == 0 && pt0 ? pt0 + (pts_shared ? 0 : b0 * PL) : nullptr, pts_shared ? (u64)0 : PL, kc.dmods(),
                        (uint32_t)set.ndigits, (uint32_t)kc.L, (uint32_t)j0, (uint32_t)njg, (uint32_t)kc.logn, (uint32_t)nb,
                        (uint32_t)l.nr, (uint32_t)l.rpg, (uint32_t)l.ngroups);
+        }
+    });
+    parts.close(cc, batch, out, s);
+}
+
+// Hoisted matrix-vector product with one Galois key set per client (hoist_matvec_keyed_kernel): matvec_hoisted client by
+// client on each client's nrot keys and slices of `ct`, `pts` and `pt0`, word for word, in matvec_hoisted's launches -- the
+// set and the ownership rule of galois_hoisted_keyed, the layouts, refusals, rotation groups and partial sums of
+// matvec_hoisted.  One stage-B launch per W and k::HOIST_ROTS rotations, however many clients there are.
+inline void matvec_hoisted_keyed(const KskSet &set, size_t nclients, const size_t *exponents, size_t nrot, const u64 *ct,
+                                 const u64 *pts, bool pts_shared, const u64 *pt0, u64 *out, size_t batch, hipStream_t s) {
+    const Ctx &kc = *set.ksk_ctx, &cc = *set.ct_ctx;
+    const std::vector<uint32_t> exps = hoist_exponents(set, exponents, nrot, "keyed hoisted matvec", nclients);
+    require(batch % nclients == 0, E_ARG, "keyed hoisted matvec: the batch is a multiple of the clients");
+    if (!batch) return;
+    const size_t per_client = batch / nclients;
+    const u64 PL = (u64)cc.L * kc.n;
+    auto overlaps = [&](const u64 *p, u64 words) { return p != nullptr && out < p + words && p < out + batch * 2 * PL; };
+    require(!overlaps(ct, batch * 2 * PL), E_ARG,
+            "hoisted matvec: `out` overlaps `ct` (every rotation gathers from the whole input)");
+    require(!overlaps(pts, (pts_shared ? 1 : batch) * nrot * PL), E_ARG, "hoisted matvec: `out` overlaps `pts`");
+    require(!overlaps(pt0, (pts_shared ? 1 : batch) * PL), E_ARG, "hoisted matvec: `out` overlaps `pt0`");
+    require((((uintptr_t)ct | (uintptr_t)pts | (uintptr_t)pt0 | (uintptr_t)out) & 15) == 0, E_ARG,
+            "hoisted matvec: buffers must be 16-byte aligned");
+    const size_t forced = set.rot_split.load(std::memory_order_relaxed);
+    struct Launch {
+        size_t r0, nr, rpg, ngroups, first;   // as matvec_hoisted's
+    };
+    std::vector<Launch> plan;
+    HoistPartials parts;
+    hoist_each_w(set, ct, batch, s, [&](size_t b0, size_t nb, size_t j0, size_t njg, const u64 *w) {
+        parts.plan_on_first_w([&] {
+            size_t total = 0;
+            for (size_t r0 = 0; r0 < nrot; r0 += k::HOIST_ROTS) {
+                const size_t nr = std::min<size_t>(k::HOIST_ROTS, nrot - r0);
+                const size_t rpg = hoist_rot_group(kc, forced, nb, njg, nr);
+                const size_t ng = (nr + rpg - 1) / rpg;
+                plan.push_back({r0, nr, rpg, ng, total});
+                total += ng;
+            }
+            return total;
+        }, (u64)batch * 2 * PL, s);
+        for (const Launch &l : plan) {
+            const k::HoistExps he = hoist_exps_arg(exps, l.r0, l.nr);
+            const unsigned grid_b = hoist_grid_b(kc, njg, nb, l.ngroups);
+            u64 *o = parts.dest(out, l.first) + b0 * 2 * PL;
+            const u64 *c = ct + b0 * 2 * PL;
+            FHE_LAUNCH("hoist_matvec_keyed", k::hoist_matvec_keyed_kernel, dim3(grid_b), dim3(256), 0, s, w, o, o + PL, 2 * PL,
+                       parts.part_words, c, c + PL, 2 * PL, set.table.p, (uint32_t)b0, (uint32_t)per_client, (uint32_t)nclients,
+                       (uint32_t)nrot, (uint32_t)l.r0, he, pts + (pts_shared ? 0 : b0 * nrot * PL) + l.r0 * PL,
+                       pts_shared ? (u64)0 : (u64)nrot * PL, PL, l.r0 == 0 && pt0 ? pt0 + (pts_shared ? 0 : b0 * PL) : nullptr,
+                       pts_shared ? (u64)0 : PL, kc.dmods(), (uint32_t)set.ndigits, (uint32_t)kc.L, (uint32_t)j0, (uint32_t)njg,
+                       (uint32_t)kc.logn, (uint32_t)nb, (uint32_t)l.nr, (uint32_t)l.rpg, (uint32_t)l.ngroups);
         }
     });
     parts.close(cc, batch, out, s);

@@ -1511,6 +1511,52 @@ fhe_status fhe_bfv_matvec_hoisted_dev(const fhe_kskset *gks, const size_t *expon
         matvec_hoisted(set, exponents, nrot, ct, pts, pts_shared != 0, pt0, out, batch, as_stream(stream));
     });
 }
+// The two hoisted calls with one Galois key set per client (engine.hpp: galois_hoisted_keyed, matvec_hoisted_keyed): the
+// refusals of the client count, in this order, then those of the unkeyed calls.
+static void hoisted_keyed_counts(const char *what, const KskSet &set, size_t nclients, size_t nrot, size_t batch) {
+    if (nclients == 0)
+        throw StatusError(FHE_E_ARG, std::string(what) + ": 0 clients for a set of " + std::to_string(set.keys.size()) + " keys");
+    if (nrot != set.keys.size() / nclients || nclients * nrot != set.keys.size())
+        throw StatusError(FHE_E_ARG, std::string(what) + ": " + std::to_string(nclients) + " clients x " + std::to_string(nrot) +
+                                         " exponents for a set of " + std::to_string(set.keys.size()) + " keys");
+    if (batch % nclients != 0)
+        throw StatusError(FHE_E_ARG, std::string(what) + ": batch " + std::to_string(batch) + " is not a multiple of the " +
+                                         std::to_string(nclients) + " clients");
+}
+fhe_status fhe_bfv_galois_hoisted_keyed_dev(const fhe_kskset *gks, size_t nclients, const size_t *exponents, size_t nrot,
+                                            const uint64_t *ct, uint64_t *out, size_t batch, void *stream) {
+    return guard([&] {
+        need(gks, "gks");
+        need(exponents, "exponents");
+        const KskSet &set = *gks->s;
+        hoisted_keyed_counts("keyed hoisted rotations", set, nclients, nrot, batch);
+        set.ksk_ctx->need_device();
+        set_device(*set.ksk_ctx);
+        if (batch) {
+            need(ct, "ct");
+            need(out, "out");
+        }
+        galois_hoisted_keyed(set, nclients, exponents, nrot, ct, out, batch, as_stream(stream));
+    });
+}
+fhe_status fhe_bfv_matvec_hoisted_keyed_dev(const fhe_kskset *gks, size_t nclients, const size_t *exponents, size_t nrot,
+                                            const uint64_t *ct, const uint64_t *pts, int pts_shared, const uint64_t *pt0,
+                                            uint64_t *out, size_t batch, void *stream) {
+    return guard([&] {
+        need(gks, "gks");
+        need(exponents, "exponents");
+        const KskSet &set = *gks->s;
+        hoisted_keyed_counts("keyed hoisted matvec", set, nclients, nrot, batch);
+        set.ksk_ctx->need_device();
+        set_device(*set.ksk_ctx);
+        if (batch) {
+            need(ct, "ct");
+            need(pts, "pts");
+            need(out, "out");
+        }
+        matvec_hoisted_keyed(set, nclients, exponents, nrot, ct, pts, pts_shared != 0, pt0, out, batch, as_stream(stream));
+    });
+}
 // Baby-step/giant-step hoisted matrix-vector product (engine.hpp: matvec_bsgs).
 fhe_status fhe_bfv_matvec_bsgs_dev(const fhe_kskset *baby, const size_t *baby_exps, size_t nbaby, const fhe_kskset *giant,
                                    const size_t *giant_exps, size_t ngiant, const uint64_t *ct, const uint64_t *pts,

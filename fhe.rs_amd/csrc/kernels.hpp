@@ -20,6 +20,8 @@
 //                           registers (a plaintext matrix times an encrypted vector; hoist_mac_kernel + dot_kernel's words)
 //   bsgs_baby_kernel<GT>, bsgs_giant_kernel   the baby-step/giant-step form of that product: G inner sums from one digit
 //                           loop per baby rotation, then the giants' key switches summed in registers (kernels_bsgs.hpp)
+//   hoist_mac_keyed_kernel, hoist_matvec_keyed_kernel   hoist_mac_kernel / hoist_matvec_kernel with one Galois key set per
+//                           client: the key of (ciphertext, rotation) from a client-major table (kernels_kshoistkeyed.hpp)
 //   scale_kernel            RnsScaler::scale per column             M/rns/scaler.rs:249-352, M/rq/scaler.rs:85-94
 //   switch_down_kernel      Poly::switch_down                       M/rq/mod.rs:433-492
 //   substitute_kernel       Poly::substitute                        M/rq/mod.rs:360-412
@@ -55,6 +57,7 @@
 #include "kernels_kskeyed.hpp"
 #include "kernels_kshoist.hpp"
 #include "kernels_bsgs.hpp"
+#include "kernels_kshoistkeyed.hpp"
 #include "kernels_scaler.hpp"
 #include "kernels_misc.hpp"
 #include "kernels_encode.hpp"

@@ -167,8 +167,5 @@ __global__ void __launch_bounds__(256)
     *reinterpret_cast<u64x2 *>(out1 + ooff) = r1;
 }
 
-#undef FHE_KS_DIGIT_LOOP
-#undef FHE_KS_IDENTITY_DIAG
-
 }  // namespace k
 }  // namespace fhe

@@ -1,6 +1,7 @@
 // kernels_ksmac.hpp -- what the stage B kernels of the unfused key switch share, each piece stated once: ks_mac_kernel
 // (kernels_ks.hpp), ks_mac_keyed_kernel (kernels_kskeyed.hpp), hoist_mac_kernel and hoist_matvec_kernel
-// (kernels_kshoist.hpp), bsgs_baby_kernel<GT> and bsgs_giant_kernel (kernels_bsgs.hpp).  All of them form
+// (kernels_kshoist.hpp), bsgs_baby_kernel<GT> and bsgs_giant_kernel (kernels_bsgs.hpp), hoist_mac_keyed_kernel and
+// hoist_matvec_keyed_kernel (kernels_kshoistkeyed.hpp).  All of them form
 //   sum_i x_i[j] (.) (k0, k1)[i][j]   (x_i: row (i, j) of W, or the caller's Ntt row where i == j)
 // with one lane per 16-byte chunk of an output row under key modulus j; they differ in where the key, the digit words
 // and the result come from and go to.  Included from kernels_ks.hpp.
@@ -82,7 +83,7 @@ struct KsMacQuad {
 // ks_mac_keyed_kernel), or a cached gathered load with the own row from c1 (the other four).  A macro body, as
 // FHE_GARNER_HORNER is: as a function template over the loader the loop costs instructions and registers (hoist_mac_kernel:
 // 1160 against 1145 instructions, 86 against 79 VGPRs), and even a lambda for X moves ks_mac_kernel's code.  Undefined
-// after its last use (kernels_bsgs.hpp).
+// after its last use (kernels_kshoistkeyed.hpp).
 #define FHE_KS_DIGIT_LOOP(acc, ndigits, md, kp0, kp1, lk, n, X)                                            \
     for (uint32_t i0 = 0; i0 < (ndigits); i0 += 16) {                                                      \
         const uint32_t i1 = i0 + 16 < (ndigits) ? i0 + 16 : (ndigits);                                     \

@@ -509,6 +509,34 @@ fhe_status fhe_bfv_matvec_hoisted_dev(const fhe_kskset *gks, const size_t *expon
 fhe_status fhe_bfv_matvec_bsgs_dev(const fhe_kskset *baby, const size_t *baby_exps, size_t nbaby, const fhe_kskset *giant,
                                    const size_t *giant_exps, size_t ngiant, const uint64_t *ct, const uint64_t *pts,
                                    int pts_shared, uint64_t *out, size_t batch, void *stream);
+/* Hoisted rotations and the hoisted matrix-vector product with ONE GALOIS KEY SET PER CLIENT (keyed batches x hoisting;
+ * hoist_mac_keyed_kernel and hoist_matvec_keyed_kernel): a server that multiplies its plaintext matrix by each client's
+ * encrypted vector, every client under their own keys, in the launches of one batch.
+ * gks: a set of nclients * nrot RNS-digit Galois keys at the ciphertext's level in CLIENT-MAJOR order: entry c * nrot + r is
+ * client c's key for exponents[r].  `batch` is a multiple of nclients; with m = batch / nclients, items [c * m, (c + 1) * m)
+ * belong to client c (the rule of the keyed calls above).
+ * THE SPECIFICATION IS A COMPOSITION: the result equals, word for word, one call of fhe_bfv_galois_hoisted_dev /
+ * fhe_bfv_matvec_hoisted_dev per client, on a set of that client's nrot keys and the client's slice of ct -- and, for the
+ * matvec, of pts (when not shared) and pt0.  LIKE THOSE CALLS', THE OUTPUT IS NOT THE REFERENCE'S WORDS (tests/hoist_ref.py,
+ * tests/hoistmv_ref.py restate it).  The words do not depend on the W budget, the rotation split or the chunking: a
+ * launch cut by fhe_kskset_set_w_budget need not end on a client boundary.
+ * Layouts, alignment, overlap rules and the pts_shared / pt0 conventions are those of the unkeyed calls: ct
+ * [batch][2][L][N] Ntt; pts [nrot][L][N] shared by the WHOLE batch (every client's), or [batch][nrot][L][N]; pt0 NULL,
+ * [L][N] or [batch][L][N] by the same flag; out [batch][nrot][2][L][N] for the rotations, [batch][2][L][N] for the matvec.
+ * fhe_kskset_set_w_budget and fhe_kskset_set_rot_split apply as they do to the unkeyed calls.  One stage-A launch per
+ * chunk and key-modulus group and one stage-B launch per 64 rotations of it, however many clients there are.
+ * Device-pointer forms only; the calls only enqueue: nothing is uploaded.
+ * Refused: everything the unkeyed calls refuse, with their texts; nclients == 0, nclients * nrot != fhe_kskset_size(gks),
+ * batch % nclients != 0 -> FHE_E_ARG, each with a text that names both numbers.  batch == 0 is a no-op (NULL buffers
+ * allowed).  A refused call leaves `out` untouched.
+ * Not offered: keyed x BSGS (fhe_bfv_matvec_bsgs_dev takes the two key sets of one client); per-client diagonals as a
+ * third `pts` form (one set of diagonals per client: pass them per item); any automatic choice between the keyed call
+ * and a loop of single-client calls (tools/bench_hoisted_keyed.py measures both; STATE.md). */
+fhe_status fhe_bfv_galois_hoisted_keyed_dev(const fhe_kskset *gks, size_t nclients, const size_t *exponents, size_t nrot,
+                                            const uint64_t *ct, uint64_t *out, size_t batch, void *stream);
+fhe_status fhe_bfv_matvec_hoisted_keyed_dev(const fhe_kskset *gks, size_t nclients, const size_t *exponents, size_t nrot,
+                                            const uint64_t *ct, const uint64_t *pts, int pts_shared, const uint64_t *pt0,
+                                            uint64_t *out, size_t batch, void *stream);
 
 /* ------------------------------------------------------------- Multiplicator ---- */
 /* Multiplicator::new_leveled_internal + enable_relinearization + enable_mod_switching

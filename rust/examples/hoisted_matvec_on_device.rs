@@ -1,7 +1,7 @@
 //! A plaintext matrix times an encrypted SIMD vector by the diagonal method: every column rotation of the ciphertext
 //! from ONE digit decomposition (`HipKskSet::galois_hoisted_dev`), then the products with the diagonals and their sum in
 //! one `dot_product_scalar_dev`.  The rotations are not the reference's words (include/fhe_hip.h); they decrypt to the
-//! same plaintexts.
+//! same plaintexts.  The last function runs the product for many clients at once, each under their own keys.
 //! (No Rust toolchain exists in the build image: reviewed source, not compiled there.)
 use std::sync::Arc;
 
@@ -45,4 +45,19 @@ pub fn matrix_times_vector_bsgs(baby_keys: &[&HipKsk], baby_exps: &[usize], gian
         baby.set_bsgs_tile(tile)?;
     }
     baby.matvec_bsgs_dev(baby_exps, &giant, giant_exps, ct, grid, s)
+}
+
+/// The same two calls for MANY CLIENTS at once, each under their own Galois keys (`HipKskSet::galois_hoisted_keyed_dev`,
+/// `HipKskSet::matvec_hoisted_keyed_dev`): `client_keys[c][r]` is client c's key of element `exponents[r]`, `ct` holds
+/// `ct.batch / clients` ciphertexts per client, client by client, and `diagonals` / `diagonal0` serve the whole batch.
+/// The set is client-major; the results are those of one `matrix_times_vector` per client, word for word.
+pub fn matrix_times_vectors_of_many_clients(client_keys: &[Vec<&HipKsk>], exponents: &[usize], ct: &DeviceCiphertexts,
+                                            diagonals: &DeviceBuffer, diagonal0: &DeviceBuffer, keep_rotations: bool, s: &Stream)
+                                            -> Result<(DeviceCiphertexts, Option<DeviceCiphertexts>), HipError> {
+    let flat: Vec<&HipKsk> = client_keys.iter().flat_map(|keys| keys.iter().copied()).collect();
+    let set = HipKskSet::new(&flat)?;                                         // built once per group of clients
+    let clients = client_keys.len();
+    let rotations = if keep_rotations { Some(set.galois_hoisted_keyed_dev(clients, exponents, ct, s)?) } else { None };
+    let product = set.matvec_hoisted_keyed_dev(clients, exponents, ct, diagonals, Some(diagonal0), s)?;
+    Ok((product, rotations))
 }

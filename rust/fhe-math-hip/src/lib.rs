@@ -757,6 +757,45 @@ impl<'k> HipKskSet<'k> {
         })?;
         Ok(out)
     }
+    /// `galois_hoisted_dev` with one Galois key set per client (`fhe_bfv_galois_hoisted_keyed_dev`): the set holds
+    /// `nclients * exponents.len()` keys CLIENT-MAJOR -- entry `c * R + r` is client `c`'s key for `exponents[r]` -- and with
+    /// `m = ct.batch / nclients` ciphertexts `[c * m, (c + 1) * m)` belong to client `c`.  Word for word one
+    /// `galois_hoisted_dev` call per client on the client's keys and slice of the batch; the same layout of the result.
+    pub fn galois_hoisted_keyed_dev(&self, nclients: usize, exponents: &[usize], ct: &DeviceCiphertexts, stream: &Stream)
+                                    -> Result<DeviceCiphertexts> {
+        self.first.check_resident("galois_hoisted_keyed_dev", ct, 2)?;
+        expect_len("galois_hoisted_keyed_dev clients x exponents", nclients * exponents.len(), self.len)?;
+        let out = DeviceCiphertexts::alloc_on(self.first.ct_ctx().device(), ct.batch * exponents.len(), 2, ct.rows, ct.degree, ct.level,
+                                              stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_galois_hoisted_keyed_dev(self.ptr, nclients, exponents.as_ptr(), exponents.len(), ct.buf.as_ptr(),
+                                                  out.buf.as_mut_ptr(), ct.batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
+    /// `matvec_hoisted_dev` with one Galois key set per client (`fhe_bfv_matvec_hoisted_keyed_dev`): the set and the
+    /// ownership rule of `galois_hoisted_keyed_dev`, the diagonals of `matvec_hoisted_dev` -- `[R][L][N]` shared by the
+    /// WHOLE batch or `[batch][R][L][N]`, `pt0` the same way.  Word for word one `matvec_hoisted_dev` call per client.
+    pub fn matvec_hoisted_keyed_dev(&self, nclients: usize, exponents: &[usize], ct: &DeviceCiphertexts, diagonals: &DeviceBuffer,
+                                    pt0: Option<&DeviceBuffer>, stream: &Stream) -> Result<DeviceCiphertexts> {
+        self.first.check_resident("matvec_hoisted_keyed_dev", ct, 2)?;
+        expect_len("matvec_hoisted_keyed_dev clients x exponents", nclients * exponents.len(), self.len)?;
+        let (poly, nrot) = (ct.rows * ct.degree, exponents.len());
+        let shared = diagonals.len() == nrot * poly;
+        if !shared {
+            expect_len("matvec_hoisted_keyed_dev diagonals", diagonals.len(), ct.batch * nrot * poly)?;
+        }
+        if let Some(p) = pt0 {
+            expect_len("matvec_hoisted_keyed_dev identity diagonal", p.len(), if shared { poly } else { ct.batch * poly })?;
+        }
+        let out = DeviceCiphertexts::alloc_on(self.first.ct_ctx().device(), ct.batch, 2, ct.rows, ct.degree, ct.level, stream)?;
+        check(unsafe {
+            ffi::fhe_bfv_matvec_hoisted_keyed_dev(self.ptr, nclients, exponents.as_ptr(), exponents.len(), ct.buf.as_ptr(),
+                                                  diagonals.as_ptr(), shared as c_int, pt0.map_or(ptr::null(), |p| p.as_ptr()),
+                                                  out.buf.as_mut_ptr(), ct.batch, stream.as_ptr())
+        })?;
+        Ok(out)
+    }
     /// Baby-step/giant-step hoisted matrix-vector product (`fhe_bfv_matvec_bsgs_dev`; not in the reference): `self` holds
     /// the baby Galois keys (key `r` for `baby_exps[r]`), `giant` the giant keys; with `G = giant.len() + 1` groups of
     /// `B = self.len() + 1` diagonals the result is the sum over `g` of giant rotation `g` of the sum over `b` of
